@@ -124,6 +124,28 @@ def synth_inputs(B, rank, device, inertia):
     return dict(x=t(np.linspace(0.0, 200.0, N)), E=t(200e9), I=t(I), fix=t(fix, torch.uint8), Fy=t(Fy), wy=t(-1000.0))
 
 
+DUMP_BUDGET = 60 << 20          # bytes of array data --dump-outputs writes at most (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, sol):
+    """--dump-outputs: every field of `sol` (a BeamSolution / FrameSolution of the timed path's last step, batch-major) as path/<field>.npy in
+    float64 (status exactly, as its int32 value).  When the whole batch exceeds DUMP_BUDGET, the same fixed, seeded sample of batch rows
+    (sorted) from every field.  Returns the record for the JSON line."""
+    os.makedirs(path, exist_ok=True)
+    rows = int(sol[0].shape[0])
+    per_row = sum(8 * (t[0].numel() if rows else 0) for t in sol)
+    keep = rows if per_row * rows <= DUMP_BUDGET else DUMP_BUDGET // per_row
+    idx = None
+    if keep < rows:
+        idx = torch.as_tensor(np.sort(np.random.default_rng(SEED).choice(rows, size=keep, replace=False)), device=sol[0].device)
+    for name, t in zip(sol._fields, sol):
+        a = (t if idx is None else t.index_select(0, idx)).cpu().numpy().astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": [n + ".npy" for n in sol._fields], "dtype": "f64", "rows": keep, "batch_rows": rows,
+            "sample": None if idx is None else f"{keep} of {rows} batch rows, numpy default_rng({SEED}).choice without replacement, sorted",
+            "what": "outputs of the last timed step (rank 0's shard)"}
+
+
 def cpu_baseline(B_hint):
     """Oracle (plain-C port, OpenMP over beams) on the host cores, bounded sample (~10-20 s)."""
     from oracle import beam_oracle as bo
@@ -179,26 +201,33 @@ def usable_cores():
     return runtime.usable_cores()
 
 
+GENERATOR_MAX_JOBS = 4      # pool workers of the generator leg: each one opens the GPU (see generator_baseline), so the pool is kept
+                            # small -- a GPU shared with other jobs should not be held open by a process per host core
+
+
 def generator_baseline(cores):
     """CPU counterpart of MultiCore.py's main (MC:242-283): a process pool of `n_jobs` workers (the reference hard-codes 22,
-    MC:52; here every host core), batches of samples handed out one per task, every sample the sequential per-epoch loop.
+    MC:52; here min(host cores, GENERATOR_MAX_JOBS)), batches of samples handed out one per task, every sample the sequential per-epoch loop.
+    Every worker opens the GPU although it computes on the CPU only: on a ROCm build of torch the autograd engine counts the HIP devices
+    (which initialises the HIP runtime) at a process's first backward pass, so the pool is capped.
     Must run BEFORE this process touches the GPU (fork).  r06: ONE batch of the reference (500 samples, MC:246) or as many
-    rounds of one-sample-per-core as 10 s hold, whichever ends first -- r05 measured 2 samples per worker in 0.85 s."""
+    rounds of one-sample-per-worker as 10 s hold, whichever ends first -- r05 measured 2 samples per worker in 0.85 s."""
     try:
         import multiprocessing as mp
         batch, budget_s = 500, 10.0
+        jobs = max(1, min(cores, GENERATOR_MAX_JOBS))
         ctx = mp.get_context("fork")
         t0 = time.perf_counter()
         ep, n = [], 0
-        with ctx.Pool(processes=cores) as pool:
+        with ctx.Pool(processes=jobs) as pool:
             pool.map(_gen_one, [SEED + 7], chunksize=1)                    # pool start-up + first-call costs stay outside
             t1 = time.perf_counter()
             while n < batch and (n == 0 or time.perf_counter() - t1 < budget_s):
-                m = min(batch - n, max(cores, 8))                          # a round: one sample per worker
+                m = min(batch - n, max(jobs, 8))                           # a round: one sample per worker
                 ep += pool.map(_gen_one, [SEED + 100 + n + i for i in range(m)], chunksize=1)
                 n += m
             dt = time.perf_counter() - t1
-        return {"samples_per_s": n / dt, "samples_per_s_per_core": n / dt / cores, "samples": n, "seconds": dt, "n_jobs": cores,
+        return {"samples_per_s": n / dt, "samples_per_s_per_core": n / dt / jobs, "samples": n, "seconds": dt, "n_jobs": jobs,
                 "pool_startup_s": t1 - t0, "mean_epochs_per_sample": float(np.mean(ep)), "reference_batch": batch,
                 "what": "process pool of n_jobs workers, rounds of one sample per worker until one batch of the reference (500 samples, MC:246) or "
                         "10 s, per-sample sequential loop of the reference (MultiCore.py:242-283 structure; FE solve through the C port, torch CPU "
@@ -386,10 +415,10 @@ FRAME_BATCH = {"15x16": 12288, "10x10": 16384, "5x5": 32768, "3x3": 65536}      
                                                                     # its 100 (bays, stories) draws, 11 -- r06: 16 lanes per frame)
 
 
-def frames_measure(dev, rank, local_rank, world, bays, stories, B, K, W):
+def frames_measure(dev, rank, local_rank, world, bays, stories, B, K, W, dump=None):
     """BASELINE config 5: K launches of the batched frame solve over B frames of `bays` x `stories` per GPU (independent shards, no
     collective), HIP events on the launch stream, barriers outside them, max over ranks.  Every rank calls it; returns the record
-    (the same on every rank)."""
+    (the same on every rank).  `dump`: directory for rank 0's outputs of the last timed step (--dump-outputs)."""
     import torch.distributed as dist
     from openpystruct_amd import _cabi, frames
 
@@ -419,6 +448,7 @@ def frames_measure(dev, rank, local_rank, world, bays, stories, B, K, W):
     barrier()
     dev_ms = e0.elapsed_time(e1)
     assert int(sol.status.abs().sum()) == 0
+    dumped = dump_outputs(dump, sol) if dump and rank == 0 else None
     if is_dp(world):
         tt = torch.tensor([wall, dev_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -478,7 +508,7 @@ def frames_measure(dev, rank, local_rank, world, bays, stories, B, K, W):
     achieved = io_frame * B / (us * 1e-6) / 1e9
     flops = 2.0 * topo.n_eq * topo.kd * topo.kd / 2.0            # band LDL^T multiply-adds (n kd^2 / 2), counted as 2 flop
     tr = profiled_frame_traffic(B, bays, stories)
-    return {
+    rec = {
         "metric": f"frame FE solves/s ({topo.Ne}-elem, batched)", "value": world * B * K / (dev_ms * 1e-3), "unit": "frame FE solves/s",
         "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": dev_ms / K, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f64", "data": "synthetic", "value_host_clock": world * B * K / wall,
@@ -504,6 +534,9 @@ def frames_measure(dev, rank, local_rank, world, bays, stories, B, K, W):
                      "fp64_vector_frac": flops * B / (us * 1e-6) / 78.6e12, "fp64_vector_peak_tflops": 78.6,
                      "flop_per_frame": flops},
     }
+    if dumped:
+        rec["dump_outputs"] = dumped
+    return rec
 
 
 def bench_frames(args, rank, local_rank, world, dev):
@@ -511,7 +544,7 @@ def bench_frames(args, rank, local_rank, world, dev):
     import torch.distributed as dist
     bays, stories = (int(v) for v in args.frame.split("x"))
     B = args.batch if args.batch != 10000 else FRAME_BATCH.get(args.frame, 12288)
-    rec = frames_measure(dev, rank, local_rank, world, bays, stories, B, min(args.steps, 50), args.warmup)
+    rec = frames_measure(dev, rank, local_rank, world, bays, stories, B, args.steps, args.warmup, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(rec), flush=True)
     if is_dp(world):
@@ -538,7 +571,12 @@ def main():
                     help="also time N PINN / TFD training epochs on 50 000 generated cases per GPU (second half of the "
                          "BASELINE metric: data-parallel over the N ranks, one RCCL all-reduce per step); default: 5 at --gpus 1, "
                          "3 for N > 1; 0 switches it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's solution arrays) as DIR/<name>.npy, "
+                         "float64, at most 64 MB (a fixed, seeded sample of batch rows when the batch is larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -582,10 +620,11 @@ def main():
         if is_dp(world):
             dist.barrier(device_ids=[local_rank]) if dist.get_backend() == "nccl" else dist.barrier()
 
-    def measure(Bm, Km, Wm, n_sets, tiling, stream_out=False, warm_chip=True, own_warm=True):
+    def measure(Bm, Km, Wm, n_sets, tiling, stream_out=False, warm_chip=True, own_warm=True, dump=None):
         """K launches over `Bm` beams, rotating over `n_sets` distinct input / output buffer sets, captured in ONE HIP
         graph and replayed once between two HIP events on the launch stream.  Barriers and host synchronisation sit
-        strictly OUTSIDE the event pair.  Returns (event ms, wall s, kernel name, launch mode)."""
+        strictly OUTSIDE the event pair.  `dump`: directory for rank 0's outputs of the last timed launch (--dump-outputs).
+        Returns (event ms, wall s, kernel name, launch mode, dump record or None)."""
         base = synth_inputs(Bm, rank, dev, args.inertia)
         sets = [base]
         for k in range(1, n_sets):      # distinct HBM: same geometry, rolled case order (values stay inside the distribution)
@@ -638,15 +677,16 @@ def main():
         dev_ms = e0.elapsed_time(e1)             # HIP events on the launch stream
         for o in outs:
             assert int(o.status.abs().sum()) == 0
+        dumped = dump_outputs(dump, outs[(Km - 1) % n_sets]) if dump and rank == 0 else None      # the set the last launch wrote
         if is_dp(world):
             tt = torch.tensor([wall, dev_ms], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             wall, dev_ms = float(tt[0]), float(tt[1])
         del outs, sets
-        return dev_ms, wall, oa.kernel_name(Bm, N_ELEM, tiling), ("eager" if graph is None else f"one HIP graph of {Km} kernel nodes")
+        return dev_ms, wall, oa.kernel_name(Bm, N_ELEM, tiling), ("eager" if graph is None else f"one HIP graph of {Km} kernel nodes"), dumped
 
     def sub_record(Bm, Km, n_sets, tiling, what, stream_out=False, warm=None, warm_chip=True, own_warm=True):
-        dev_ms, wall, kname, mode = measure(Bm, Km, min(W, 2 * n_sets) if warm is None else warm, n_sets, tiling, stream_out, warm_chip, own_warm)
+        dev_ms, wall, kname, mode, _ = measure(Bm, Km, min(W, 2 * n_sets) if warm is None else warm, n_sets, tiling, stream_out, warm_chip, own_warm)
         us = dev_ms / Km * 1e3
         ach = BYTES_PER_SOLVE * Bm / (us * 1e-6) / 1e9
         return {"what": what, "beams_per_launch_per_gpu": Bm, "launches": Km, "buffer_sets": n_sets,
@@ -664,7 +704,7 @@ def main():
     fe_guard.daemon = True
     if is_dp(world):
         fe_guard.start()
-    dev_ms, wall, kname, mode = measure(B, K, W, max(1, args.sets), args.tiling)
+    dev_ms, wall, kname, mode, dumped = measure(B, K, W, max(1, args.sets), args.tiling, dump=args.dump_outputs)
 
     if rank == 0:
         kernel_ms = dev_ms / K
@@ -765,6 +805,8 @@ def main():
                     break                # the ranks may have diverged inside the collective timing: no further frame collectives
     fe_guard.cancel()
     if rank == 0:
+        if dumped:
+            rec["dump_outputs"] = dumped
         rec.update(extras)
         if frames_rec:
             rec["frames"] = frames_rec
