@@ -81,12 +81,38 @@ EXPORTS = (
     "ops_physics_loss_part_doubles",
     "ops_physics_loss_fwd",
     "ops_physics_loss_bwd",
+    "ops_bayes_sample_f32",
+    "ops_bayes_grad_fold_f32",
+    "ops_bayes_mlp_mc_f32",
+    "ops_mc_moments_f32",
 )
 
 OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = 0, 1, 2, 3
 FIX_UY, FIX_RZ = 1, 2
 
 _lib = None
+
+
+# Bayesian layers of the BTFD / BTFDM surrogates (include/openpystruct_amd.h, csrc/bayes_mlp.hip)
+BAYES_MAX_LAYERS = 8
+BAYES_EPS_DRAW, BAYES_EPS_WRITE, BAYES_EPS_READ = 0, 1, 2
+BAYES_MC_NONE, BAYES_MC_DIFFUSION, BAYES_MC_HEAD = 0, 1, 2
+BAYES_MC_MAX_KH, BAYES_MC_MAX_K, BAYES_MC_MAX_H = 1024, 256, 768
+
+
+class BayesLayer(ctypes.Structure):
+    """Mirror of `ops_bayes_layer`."""
+    _fields_ = [("out_f", ctypes.c_int32), ("in_f", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in (
+        "w_mu", "w_ls", "b_mu", "b_ls", "w", "b", "w16", "w_eps", "b_eps", "dw", "db", "d_wmu", "d_wls", "d_bmu", "d_bls")]
+
+
+class BayesMcArgs(ctypes.Structure):
+    """Mirror of `ops_bayes_mc_args`."""
+    _vp, _i, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
+    _fields_ = [("S", _i), ("rows_per_sample", _i), ("K", _i), ("H", _i), ("N", _i), ("x", _vp), ("ldx", _i),
+                ("w1_mu", _vp), ("w1_ls", _vp), ("b1_mu", _vp), ("b1_ls", _vp), ("ln_g", _vp), ("ln_b", _vp), ("ln_eps", _f), ("slope", _f),
+                ("w2_mu", _vp), ("w2_ls", _vp), ("b2_mu", _vp), ("b2_ls", _vp), ("seed", ctypes.c_ulonglong), ("epilogue", _i), ("y", _vp),
+                ("Nc", _i), ("T", _i), ("acp", _vp), ("row_base", ctypes.c_longlong), ("cls", _vp), ("pe", _vp), ("t_out", _vp), ("xeps_out", _vp), ("out_scale", _vp), ("eps_out", _vp), ("h_ws", _vp), ("xn_ws", _vp)]
 
 
 class SizingParams(ctypes.Structure):
@@ -366,6 +392,14 @@ def load():
     lib.ops_linear_wgrad_accumulate.argtypes = [it, it, it, vp, vp, vp, vp, vp]
     lib.ops_act_dropout_bwd.restype = it
     lib.ops_act_dropout_bwd.argtypes = [lg, vp, vp, vp, fl, fl, ull, vp, vp]
+    lib.ops_bayes_sample_f32.restype = it
+    lib.ops_bayes_sample_f32.argtypes = [it, ctypes.POINTER(BayesLayer), ull, vp, it, vp]
+    lib.ops_bayes_grad_fold_f32.restype = it
+    lib.ops_bayes_grad_fold_f32.argtypes = [it, ctypes.POINTER(BayesLayer), ull, vp, it, fl, fl, fl, vp]
+    lib.ops_bayes_mlp_mc_f32.restype = it
+    lib.ops_bayes_mlp_mc_f32.argtypes = [ctypes.POINTER(BayesMcArgs), vp]
+    lib.ops_mc_moments_f32.restype = it
+    lib.ops_mc_moments_f32.argtypes = [it, lg, it, vp, vp, vp, vp, vp, vp]
     lib.ops_amd_max_elements.restype = it
     lib.ops_amd_abi_version.restype = it
     lib.ops_amd_last_error.restype = ctypes.c_char_p

@@ -41,7 +41,7 @@ import torch.nn as nn
 from torch.optim.lr_scheduler import ExponentialLR
 
 from .dataprep import SurrogateData
-from .surrogates import fused_loss, ChainGNN, CompositeLoss, FNO1dModel, FNNPlain, FNNWithResidual, ModelOnePassTransformerWithDiffusion, TrainableL1L2Loss
+from .surrogates import fused_loss, BayesianTransformerWithDiffusion, ChainGNN, CompositeLoss, FNO1dModel, FNNPlain, FNNWithResidual, ModelOnePassTransformerWithDiffusion, TrainableL1L2Loss
 
 
 @dataclass
@@ -92,6 +92,44 @@ class TfdConfig:
     max_len: int = 512
     diffusion_hidden_dim: int = 256
     diffusion_T: int = 512
+
+
+@dataclass
+class BtfdConfig:
+    """OpenPyStruct_Bayesian_TFDModule_MultiCase_Beta.py:36-66.  kl: "none" reproduces the script as it runs (its KL sum
+    is over modules with a `kl_loss` method: none); "gaussian" adds bnn_kl_scale * bayes.bayesian_kl(model)."""
+    n_cases: int = 6
+    nelem: int = 100
+    box_constraint_coeff: float = 5e-1
+    hidden_units: int = 512
+    dropout_rate: float = 0.1
+    num_epochs: int = 500
+    batch_size: int = 512
+    patience: int = 10
+    learning_rate: float = 3e-4
+    weight_decay: float = 1e-6
+    train_split: float = 0.8
+    sigma_0: float = 0.01
+    gamma_noise: float = 0.95
+    gamma: float = 0.99
+    initial_alpha: float = 0.5
+    c: float = 0.5
+    bnn_kl_scale: float = 1e-6
+    num_transformer_layers: int = 4
+    dim_feedforward: int = 512
+    num_heads: int = 24
+    max_len: int = 512
+    diffusion_hidden_dim: int = 512
+    diffusion_T: int = 512
+    kl: str = "none"
+
+
+@dataclass
+class BtfdmConfig(BtfdConfig):
+    """The _Meta_ script: n_cases 8, dropout 0.01, c 1 (and the model's trainable output_scales)."""
+    n_cases: int = 8
+    dropout_rate: float = 0.01
+    c: float = 1.0
 
 
 @dataclass
@@ -572,6 +610,11 @@ def build_model_and_loss(kind: str, cfg, data: SurrogateData, device):
                                                      cfg.num_transformer_layers, cfg.num_heads, cfg.dim_feedforward,
                                                      cfg.dropout_rate, cfg.max_len, cfg.diffusion_hidden_dim, cfg.diffusion_T)  # TFD:664-676
         crit = TrainableL1L2Loss(cfg.initial_alpha, data.min_constraint, data.max_constraint, cfg.box_constraint_coeff)       # TFD:680
+    elif kind in ("btfd", "btfdm"):
+        model = BayesianTransformerWithDiffusion(cfg.n_cases, data.feat_dim, cfg.nelem, cfg.hidden_units, cfg.num_transformer_layers,
+                                                 cfg.num_heads, cfg.dim_feedforward, cfg.dropout_rate, cfg.max_len, cfg.diffusion_hidden_dim,
+                                                 cfg.diffusion_T, output_scales=kind == "btfdm")                # BTFD:640-653
+        crit = TrainableL1L2Loss(cfg.initial_alpha, data.min_constraint, data.max_constraint, cfg.box_constraint_coeff)
     elif kind == "gnn":
         model = ChainGNN(data.X_train.shape[1], cfg.nelem, cfg.encoder_hidden_dim, cfg.gnn_hidden_dim, cfg.num_gnn_layers, cfg.dropout_rate)
         crit = TrainableL1L2Loss(cfg.initial_alpha, data.min_constraint, data.max_constraint, cfg.box_constraint_coeff)
@@ -647,8 +690,12 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
     reference's DataLoader shuffle, PINN:701, is unseeded; the golden-fixture tests replay the order it drew).
     `autocast_dtype=torch.float16`: the reference's AMP mode (fp16 autocast + GradScaler, PINN:706, :759-768) on the framework modules; the
     returned dict then carries `grad_scaler` = {"scale", "skipped_steps", "steps"}."""
-    cfg = cfg or {"pinn": PinnConfig, "tfd": TfdConfig, "fnn": FnnConfig, "gnn": GnnConfig, "fno": FnoConfig}[kind]()
-    alpha_term = kind in ("tfd", "fnn", "fno")          # (initial_alpha - alpha)^2 in the training loss (TFD:743, FNO:615)
+    cfg = cfg or {"pinn": PinnConfig, "tfd": TfdConfig, "fnn": FnnConfig, "gnn": GnnConfig, "fno": FnoConfig, "btfd": BtfdConfig,
+                  "btfdm": BtfdmConfig}[kind]()
+    alpha_term = kind in ("tfd", "fnn", "fno", "btfd", "btfdm")    # (initial_alpha - alpha)^2 in the training loss (TFD:743, FNO:615, BTFD:730)
+    bayes_kl = kind in ("btfd", "btfdm") and cfg.kl == "gaussian"
+    if kind in ("btfd", "btfdm") and cfg.kl not in ("none", "gaussian"):
+        raise ValueError(f"kl must be 'none' or 'gaussian', not {cfg.kl!r}")
     if kind == "fno":
         autocast_dtype = None                           # FNO:613 runs with autocast disabled
     device = torch.device(device)
@@ -665,6 +712,19 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
         _tf.disarm_gather()              # (whatever an earlier run that did not reach its end left armed)
     if init_fn is not None:
         init_fn(model)
+    bayes_hip = None
+    if kind in ("btfd", "btfdm") and device.type == "cuda":
+        # the four Bayesian layers: one sampling launch per forward, one fold launch per backward (bayes.py, csrc/bayes_mlp.hip); with
+        # the KL term on, the fold adds its gradient and the loss its (detached) value
+        from . import bayes as _bayes
+        bayes_hip = _bayes.BayesSampler(model, seed=seed * 7919 + 307 + rank, kl_scale=cfg.bnn_kl_scale if bayes_kl else 0.0)
+        model.bayes_sampler = bayes_hip
+
+    def kl_term():
+        from . import bayes as _bayes
+        kl = _bayes.bayesian_kl(model)
+        return cfg.bnn_kl_scale * (kl.detach() if bayes_hip is not None else kl)
+
     if sync_bn and dp:
         model = nn.SyncBatchNorm.convert_sync_batchnorm(model)
     net = model
@@ -853,6 +913,11 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
                 loss = crit(preds.float(), Yb)
                 if alpha_term:
                     loss = loss + (cfg.initial_alpha - crit.alpha) ** 2   # TFD:743 / FNN (constant 0: alpha never trains)
+            if bayes_kl:
+                kl = kl_term()
+                loss = loss + kl
+                if loss_acc is not None:
+                    loss_acc.add_(kl.detach())
         if physics is not None:
             term = physics_loss(preds, pin)
             # (with the running sum both launches have already added their values up: the step's scalar only roots the backward pass,
@@ -926,8 +991,10 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
         with torch.no_grad(), torch.autocast(device_type=device.type, dtype=autocast_dtype, enabled=use_ac):
             preds = model(Xb)
             if on_gpu and _FUSED_LOSS:
-                return fused_loss(crit, preds, Yb)
-            return crit(preds.float(), Yb)
+                v = fused_loss(crit, preds, Yb)
+            else:
+                v = crit(preds.float(), Yb)
+            return v + kl_term() if bayes_kl else v                       # BTFD:772
 
     # Transformer-Diffusion fast path: the validation pass as ONE forward over all validation rows (chunks of <= _VAL_CHUNK rows, whole
     # reference batches each) + the loss per reference batch on row slices of its output, every value added to `acc` by the loss launch
