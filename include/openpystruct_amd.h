@@ -100,6 +100,23 @@ int ops_beam_solve_forces_f32(int B, int Ne, const double* x, long x_bstride, co
                               const double* Fy, long Fy_bstride, const double* wy, long wy_bstride, float* V32, float* M32,
                               int32_t* status, const uint8_t* active, int tiling, void* stream);
 
+/* Vector-Jacobian product of ops_beam_solve_batched_f64 (an addition: the reference differentiates nothing through its
+ * solve).  Given the forward's solution v, theta and the cotangents gv, gt [B,N] (on v, theta) and gV, gM [B,Ne] (on V, M)
+ * of some loss L, returns
+ *   gI  [B,Ne] = dL/dI      gFy [B,N] = dL/dFy (0 on fixed u_y)      gwy [B,Ne] = dL/dwy per element
+ * by one adjoint solve K lambda = g_u with the forward's own factorisation (recomputed, not stored) and per-element
+ * contractions.  dL/dE is gI * I / E per element (linear in E I), and a shared scalar E or wy takes the sum
+ * over the beam's elements: the caller reduces.  x, fix get no gradient.  Arguments x .. wy as in ops_beam_solve_batched_f64
+ * (wy is validated only: the gradient does not depend on it); v, theta, cotangents and outputs dense.  A NULL cotangent is
+ * zero; gFy / gwy may be NULL (not computed).  status [B] (may be NULL): non-zero where the factorisation fails, and that
+ * beam's gradients are NaN.  One launch; serves every Ne the forward serves.  Returns OPS_AMD_OK or an OPS_AMD_ERR_* code.
+ * Never throws, never blocks. */
+int ops_beam_solve_vjp_f64(int B, int Ne, const double* x, long x_bstride, const double* E, long E_bstride,
+                           const double* I, long I_bstride, const uint8_t* fix, long fix_bstride,
+                           const double* wy, long wy_bstride, const double* v, const double* theta,
+                           const double* gv, const double* gt, const double* gV, const double* gM,
+                           double* gI, double* gFy, double* gwy, int32_t* status, void* stream);
+
 /* Hyper-parameters of the per-case sizing optimiser (module-level constants of the reference,
  * SingleCore.py:20-44): E, G = E / 2.6, alpha_moment = alpha_shear = 1e-2, lr = 0.01, gamma = 0.98,
  * tolerance = 5e-3, patience = 5 (MultiCore: 10, GPU script: 1e-2 / 100), max_epochs = 600,

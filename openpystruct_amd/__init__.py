@@ -3,7 +3,7 @@
 Host side in Python over a C-ABI HIP library; see DESIGN.md and INTEGRATION.md.
 """
 from . import runtime  # noqa: F401  (entry points call runtime.configure() before their first HIP call; importing sets nothing)
-from .beam import BeamSolution, beam_solve, kernel_name  # noqa: F401
-from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam_solve)
+from .beam import BeamSolution, beam_solve, beam_solve_vjp, differentiable_beam_solve, kernel_name  # noqa: F401
+from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam_solve, its VJP op and autograd formula)
 
-__all__ = ["BeamSolution", "beam_solve", "kernel_name"]
+__all__ = ["BeamSolution", "beam_solve", "beam_solve_vjp", "differentiable_beam_solve", "kernel_name"]

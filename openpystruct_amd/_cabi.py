@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpy
 EXPORTS = (
     "ops_beam_solve_batched_f64",
     "ops_beam_solve_forces_f64",
+    "ops_beam_solve_vjp_f64",
     "ops_beam_solve_forces_f32",
     "ops_beam_sizing_step_vm32_f32",
     "ops_sizing_schedule_f32",
@@ -265,6 +266,9 @@ def load():
     f = lib.ops_beam_solve_batched_f64
     f.restype = it
     f.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, vp, it, vp]
+    vj = lib.ops_beam_solve_vjp_f64
+    vj.restype = it
+    vj.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg] + [vp] * 11
     ff = lib.ops_beam_solve_forces_f64
     ff.restype = it
     ff.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, it, vp]

@@ -38,19 +38,10 @@ def _dev_f64(t, device, name):
 TILING_STREAM_OUT = 0x100     # include/openpystruct_amd.h OPS_AMD_TILING_STREAM_OUT
 
 
-def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolution] = None, stream_out: bool = False) -> BeamSolution:
-    """Solve B straight Euler-Bernoulli beams (Ne elements, N = Ne + 1 nodes) on the GPU.
-
-    x    [N] or [B,N]      node coordinates            I    [B,Ne]  element second moments of area
-    E    scalar or [B,Ne]  Young's modulus             fix  [N] or [B,N] uint8, bit0 = u_y fixed, bit1 = theta_z fixed
-    Fy   [B,N]             nodal point loads           wy   scalar or [B,Ne] transverse UDL (beamUniform Wy)
-
-    Asynchronous on the current stream of I's device; `out` lets callers reuse result buffers; `stream_out`: non-temporal
-    result stores, for callers cycling through more output than the 256 MiB Infinity Cache holds.
-    """
-    lib = _cabi.load()
+def _check_inputs(fn, x, E, I, fix, wy, Fy=None):
+    """Device, shapes and dtypes of a beam-solve argument list (include/openpystruct_amd.h): contiguous float64 / uint8 on I's GPU."""
     if not torch.is_tensor(I) or not I.is_cuda:
-        raise RuntimeError("beam_solve needs GPU tensors: openpystruct_amd has no CPU fallback (I must be a CUDA/HIP tensor)")
+        raise RuntimeError(f"{fn} needs GPU tensors: openpystruct_amd has no CPU fallback (I must be a CUDA/HIP tensor)")
     dev = I.device
     I = _dev_f64(I, dev, "I")
     if I.dim() != 2:
@@ -58,7 +49,8 @@ def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolut
     B, Ne = I.shape
     N = Ne + 1
     x = _dev_f64(x, dev, "x")
-    Fy = _dev_f64(Fy, dev, "Fy")
+    if Fy is not None:
+        Fy = _dev_f64(Fy, dev, "Fy")
     E = _dev_f64(E, dev, "E")
     wy = _dev_f64(wy, dev, "wy")
     if not torch.is_tensor(fix):
@@ -70,12 +62,28 @@ def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolut
         raise ValueError(f"x must be [{N}] or [{B},{N}], got {tuple(x.shape)}")
     if fix.shape not in ((N,), (B, N)):
         raise ValueError(f"fix must be [{N}] or [{B},{N}], got {tuple(fix.shape)}")
-    if Fy.shape != (B, N):
+    if Fy is not None and Fy.shape != (B, N):
         raise ValueError(f"Fy must be [{B},{N}], got {tuple(Fy.shape)}")
     if E.numel() != 1 and E.shape != (B, Ne):
         raise ValueError("E must be a scalar or [B, Ne]")
     if wy.numel() != 1 and wy.shape != (B, Ne):
         raise ValueError("wy must be a scalar or [B, Ne]")
+    return dev, B, Ne, x, E, I, fix, wy, Fy
+
+
+def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolution] = None, stream_out: bool = False) -> BeamSolution:
+    """Solve B straight Euler-Bernoulli beams (Ne elements, N = Ne + 1 nodes) on the GPU.
+
+    x    [N] or [B,N]      node coordinates            I    [B,Ne]  element second moments of area
+    E    scalar or [B,Ne]  Young's modulus             fix  [N] or [B,N] uint8, bit0 = u_y fixed, bit1 = theta_z fixed
+    Fy   [B,N]             nodal point loads           wy   scalar or [B,Ne] transverse UDL (beamUniform Wy)
+
+    Asynchronous on the current stream of I's device; `out` lets callers reuse result buffers; `stream_out`: non-temporal
+    result stores, for callers cycling through more output than the 256 MiB Infinity Cache holds.
+    """
+    lib = _cabi.load()
+    dev, B, Ne, x, E, I, fix, wy, Fy = _check_inputs("beam_solve", x, E, I, fix, wy, Fy)
+    N = Ne + 1
     if out is None:
         out = BeamSolution(
             torch.empty((B, N), dtype=torch.float64, device=dev),
@@ -111,3 +119,58 @@ def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolut
 
 def kernel_name(B: int, Ne: int, tiling: int = 0) -> str:
     return _cabi.load().ops_beam_solve_kernel_name(B, Ne, tiling).decode()
+
+
+def beam_solve_vjp(x, E, I, fix, wy, v, theta, gv=None, gt=None, gV=None, gM=None):
+    """Vector-Jacobian product of `beam_solve` (csrc/beam_vjp.hip, one launch): given the forward's solution (v, theta) and the
+    cotangents of a loss L on v, theta [B,N] and V, M [B,Ne] (None = zero), returns (gI, gFy, gwy, status):
+
+    gI [B,Ne] = dL/dI,  gFy [B,N] = dL/dFy (0 on fixed u_y),  gwy [B,Ne] = dL/dwy PER ELEMENT (a shared wy is their sum),
+    status [B] int32 (non-zero: factorisation failed, that beam's gradients are NaN).  dL/dE = gI * I / E per element.
+    Arguments x .. wy as in `beam_solve`; GPU float64 only, asynchronous on the current stream."""
+    lib = _cabi.load()
+    dev, B, Ne, x, E, I, fix, wy, _ = _check_inputs("beam_solve_vjp", x, E, I, fix, wy)
+    N = Ne + 1
+
+    def rows(t, name, cols, required=False):
+        if t is None:
+            if required:
+                raise ValueError(f"{name} is required")
+            return None
+        t = _dev_f64(t, dev, name)
+        if t.shape != (B, cols):
+            raise ValueError(f"{name} must be [{B},{cols}], got {tuple(t.shape)}")
+        return t
+
+    v, theta = rows(v, "v", N, True), rows(theta, "theta", N, True)
+    gv, gt, gV, gM = rows(gv, "gv", N), rows(gt, "gt", N), rows(gV, "gV", Ne), rows(gM, "gM", Ne)
+    gI = torch.empty((B, Ne), dtype=torch.float64, device=dev)
+    gFy = torch.empty((B, N), dtype=torch.float64, device=dev)
+    gwy = torch.empty((B, Ne), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.ops_beam_solve_vjp_f64(
+            B, Ne,
+            x.data_ptr(), N if x.dim() == 2 else 0,
+            E.data_ptr(), Ne if E.numel() != 1 else 0,
+            I.data_ptr(), Ne,
+            fix.data_ptr(), N if fix.dim() == 2 else 0,
+            wy.data_ptr(), Ne if wy.numel() != 1 else 0,
+            v.data_ptr(), theta.data_ptr(), ptr(gv), ptr(gt), ptr(gV), ptr(gM),
+            gI.data_ptr(), gFy.data_ptr(), gwy.data_ptr(), status.data_ptr(), stream,
+        )
+    if rc != _cabi.OK:
+        raise RuntimeError(f"ops_beam_solve_vjp_f64 failed with code {rc}: {lib.ops_amd_last_error().decode()}")
+    return gI, gFy, gwy, status
+
+
+def differentiable_beam_solve(x, E, I, fix, Fy, wy) -> BeamSolution:
+    """`beam_solve` through the registered operator `torch.ops.openpystruct_amd.beam_solve`, which has an autograd formula:
+    gradients reach I, E, Fy and wy (torch_op.py).  x and fix are not differentiable.  E and wy: tensors or
+    Python scalars (a scalar gets no gradient)."""
+    from . import torch_op  # noqa: F401  (registers the operator and its autograd formula)
+    dev = I.device
+    t = lambda a, dt=torch.float64: a if torch.is_tensor(a) else torch.as_tensor(a, dtype=dt, device=dev)   # noqa: E731
+    return BeamSolution(*torch.ops.openpystruct_amd.beam_solve(t(x), t(E), I, t(fix, torch.uint8), t(Fy), t(wy)))
