@@ -182,6 +182,21 @@ def _launch_mc(lib, a, dev):
         raise RuntimeError(f"ops_bayes_mlp_mc_f32 failed with code {rc}: {lib.ops_amd_last_error()}")
 
 
+def _check_mc_shapes(S: int, blocks) -> None:
+    """The limits of ops_bayes_mlp_mc_f32 (one lin1 tile and 32 input rows, or one lin2 tile and 32 hidden rows, in LDS; S on grid.y),
+    checked before anything is allocated or launched: the C call would only return OPS_AMD_ERR_UNSUPPORTED."""
+    if S > 65535:
+        raise NotImplementedError(f"n_samples {S} exceeds the Monte-Carlo kernels' limit of 65535 samples per call")
+    for name, mlp in blocks:
+        K, H = mlp.lin1.in_features, mlp.lin1.out_features
+        for what, v, lim in (("input width K", K, _cabi.BAYES_MC_MAX_K), ("hidden width H", H, _cabi.BAYES_MC_MAX_H),
+                             ("K + H", K + H, _cabi.BAYES_MC_MAX_KH)):
+            if v > lim:
+                raise NotImplementedError(f"{name}: {what} = {v} exceeds the Monte-Carlo kernels' limit of {lim} "
+                                          f"(K = feat_dim = {K}, H = {H}; K <= {_cabi.BAYES_MC_MAX_K}, H <= {_cabi.BAYES_MC_MAX_H}, "
+                                          f"K + H <= {_cabi.BAYES_MC_MAX_KH})")
+
+
 def mc_seeds(seed: int):
     """(diffusion block, head block) stream seeds of `predict_with_uncertainty(seed=seed)`."""
     return _mix(int(seed) * 2 + 1), _mix(int(seed) * 2 + 2)
@@ -204,9 +219,10 @@ def predict_with_uncertainty(model, X: torch.Tensor, n_samples: int = 50, seed: 
     B, Nc, d = X.shape
     if S < 1 or Nc != model.n_cases or d != model.feat_dim:
         raise ValueError(f"X {tuple(X.shape)} / n_samples {S} do not fit the model (n_cases {model.n_cases}, feat_dim {model.feat_dim})")
+    dm, head = model.diffusion.mlp, model.bnn_output
+    _check_mc_shapes(S, (("diffusion block", dm), ("output head", head)))
     dev = X.device
     X = X.float().contiguous()
-    dm, head = model.diffusion.mlp, model.bnn_output
     for p in model.parameters():
         _check_gpu(p.data)
     n_elem = head.lin2.out_features

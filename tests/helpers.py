@@ -127,3 +127,22 @@ def assert_stop_epochs_agree(ep, ref_ep, ref_loss_history, tolerance, patience, 
     marg = marginal_stop_decisions(ref_loss_history, tolerance)
     assert marg and abs(int(ep) - int(ref_ep)) <= patience, (what, int(ep), int(ref_ep), marg[-5:])
     return False
+
+
+def framework_loop(m, X, draws):
+    """The reference's get_bnn_output_stats fed the kernels' per-sample draws (`predict_with_uncertainty(..., return_draws=True)`):
+    S framework forwards of the BTFD / BTFDM model `m` in float32 -> [S, B, n_elem] float64."""
+    import torch
+
+    from openpystruct_amd import bayes
+
+    S = draws["t"].shape[0]
+    preds = []
+    with torch.no_grad():
+        for s in range(S):
+            wd = bayes.split_draws(m, draws["w_diff"][s], "diffusion")
+            wh = bayes.split_draws(m, draws["w_head"][s], "head")
+            bayes.set_frozen_draws(m.bayes_layers(), wd + wh)
+            preds.append(m(X, (draws["t"][s], draws["xeps"][s])).double())
+    bayes.set_frozen_draws(m.bayes_layers(), None)
+    return torch.stack(preds)

@@ -10,6 +10,7 @@ torch = pytest.importorskip("torch")
 
 from openpystruct_amd import bayes, dataprep, train  # noqa: E402
 from openpystruct_amd.surrogates import BayesianTransformerWithDiffusion, BayesLinear  # noqa: E402
+from tests.helpers import framework_loop  # noqa: E402
 
 
 @pytest.fixture(autouse=True)
@@ -208,27 +209,13 @@ def test_train_surrogate_end_to_end(kind):
     assert out["model"].bayes_sampler is not None and int(out["model"].bayes_sampler.counter) > 0
 
 
-def _framework_loop(m, X, draws):
-    """The reference's get_bnn_output_stats fed the kernel's per-sample draws: S framework forwards in float32."""
-    S = draws["t"].shape[0]
-    preds = []
-    with torch.no_grad():
-        for s in range(S):
-            wd = bayes.split_draws(m, draws["w_diff"][s], "diffusion")
-            wh = bayes.split_draws(m, draws["w_head"][s], "head")
-            bayes.set_frozen_draws(m.bayes_layers(), wd + wh)
-            preds.append(m(X, (draws["t"][s], draws["xeps"][s])).double())
-    bayes.set_frozen_draws(m.bayes_layers(), None)
-    return torch.stack(preds)
-
-
 @pytest.mark.parametrize("B,n_cases", [(1, 6), (7, 8), (512, 6), (1, 8), (512, 8)])
 def test_predict_with_uncertainty_equals_the_replayed_loop(B, n_cases):
     S = 50
     m = _model(n_cases, output_scales=n_cases == 8, seed=B).eval()
     X = torch.randn(B, n_cases, 120, device="cuda")
     mean, std, draws = bayes.predict_with_uncertainty(m, X, n_samples=S, seed=4, return_draws=True)
-    P = _framework_loop(m, X, draws)
+    P = framework_loop(m, X, draws)
     rm, rs = P.mean(0), P.std(0, unbiased=False)
     scale_m, scale_s = float(rm.abs().max()), float(rs.max())
     em = float((mean.double() - rm).abs().max()) / scale_m
