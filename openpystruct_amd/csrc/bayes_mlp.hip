@@ -17,10 +17,10 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "dropout_stream.hpp"
+#include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
-
-void set_last_error(const char* msg);
 
 __device__ __forceinline__ DropKey bayes_key(uint64_t seed, uint64_t counter, int layer) {
   return drop_key(seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(layer + 1)), counter);
@@ -28,12 +28,6 @@ __device__ __forceinline__ DropKey bayes_key(uint64_t seed, uint64_t counter, in
 __device__ __forceinline__ float bayes_normal(DropKey k, uint64_t e) {
   const float u1 = 1.0f - drop_uniform(k, 2 * e), u2 = drop_uniform(k, 2 * e + 1);      // (0, 1], [0, 1)
   return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
-}
-__device__ __forceinline__ uint16_t bayes_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
 }
 
 struct BayesLayers { ops_bayes_layer l[OPS_BAYES_MAX_LAYERS]; };
@@ -55,7 +49,7 @@ __global__ __launch_bounds__(256) void bayes_sample_kernel(BayesLayers L, unsign
     const float v = mu + expf(ls) * ep;
     if (w) {
       p.w[j] = v;
-      if (p.w16) ((uint16_t*)p.w16)[j] = bayes_f2bf(v);
+      if (p.w16) ((uint16_t*)p.w16)[j] = f32_to_bf16(v);
     } else {
       p.b[j] = v;
     }
@@ -96,12 +90,6 @@ constexpr int MC_RT = 32;
 constexpr int MC_THREADS = 256;
 constexpr int MC_JT = 64;        // lin1: hidden columns per workgroup
 constexpr int MC_NT = 16;        // lin2: output columns per workgroup
-
-__device__ __forceinline__ float mc_wsum(float v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 __device__ __forceinline__ size_t mc_eps_stride(const ops_bayes_mc_args& a) {
   return (size_t)a.H * a.K + a.H + (size_t)a.N * a.H + a.N;
@@ -254,10 +242,10 @@ __global__ __launch_bounds__(MC_THREADS) void bayes_mc_lin2_kernel(ops_bayes_mc_
       float* h = hs + r * H;
       float sm = 0.0f;
       for (int j = lane; j < H; j += 64) sm += h[j];
-      const float mean = mc_wsum(sm) / (float)H;
+      const float mean = wave_sum(sm) / (float)H;
       float sq = 0.0f;
       for (int j = lane; j < H; j += 64) { const float dv = h[j] - mean; sq = fmaf(dv, dv, sq); }
-      const float rstd = 1.0f / sqrtf(mc_wsum(sq) / (float)H + a.ln_eps);
+      const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)H + a.ln_eps);
       for (int j = lane; j < H; j += 64) {
         const float v = (h[j] - mean) * rstd * a.ln_g[j] + a.ln_b[j];
         h[j] = v > 0.0f ? v : v * a.slope;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "beam_math.hpp"
+#include "lane_common.hpp"
 #include "sizing_math.hpp"
 
 namespace opsamd {
@@ -44,14 +45,6 @@ hipError_t launch_fat_sizing(const BeamParams& p, const SizingArgs& sz, int P, i
 // v_mov_b32 with a row_shr / row_shl modifier (bound_ctrl writes 0 for lanes shifted in from outside
 // the row); no LDS crossbar, no wait.  P = 8 shares its row with a second beam and masks the lanes
 // that would read across the group edge.  P >= 32: ds_bpermute (__shfl).
-template <int CTRL>
-__device__ __forceinline__ double dpp_mov(double x) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
 template <int P>
 struct Xch {
   template <int S>

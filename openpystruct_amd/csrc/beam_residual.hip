@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "../../include/openpystruct_amd.h"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
@@ -173,8 +174,10 @@ __device__ __forceinline__ PhEl ph_el(const PhysArgs& a, int e) {
   return k;
 }
 
+// thread 0 gets the totals.  Not block_sum of lane_common.hpp (no barrier before s_red is written), and the butterfly is open-coded:
+// written with wave_sum, the kernels compile to different instructions
 template <int NV>
-__device__ __forceinline__ void ph_block_sum(double (&v)[NV], double* s_red) {      // thread 0 gets the totals
+__device__ __forceinline__ void ph_block_sum(double (&v)[NV], double* s_red) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < NV; ++k)
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(256) void phys_loss_bwd_kernel(const PhysArgs a, in
   auto put = [&](int c, double g) {
     if (a.bf16) {
       uint32_t u = __float_as_uint((float)g);
-      if ((u & 0x7fffffffu) > 0x7f800000u) u |= 0x400000u; else u += 0x7fffu + ((u >> 16) & 1u);
+      if ((u & 0x7fffffffu) > 0x7f800000u) u |= 0x400000u; else u = bf16_rne_bits(u);
       ((uint16_t*)a.dpreds)[b * a.ldp + c] = (uint16_t)(u >> 16);
     } else ((float*)a.dpreds)[b * a.ldp + c] = (float)g;
   };

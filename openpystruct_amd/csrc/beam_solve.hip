@@ -23,6 +23,7 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "beam_io.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -535,15 +536,6 @@ static bool results_cache_resident(const void* out, unsigned long long call_byte
   return resident;
 }
 
-static thread_local char g_last_error[256] = {0};
-
-// shared by every translation unit of the library (ops_amd_last_error reports it)
-void set_last_error(const char* msg) {
-  int k = 0;
-  for (; msg && msg[k] && k < 255; ++k) g_last_error[k] = msg[k];
-  g_last_error[k] = 0;
-}
-
 template <int P, int M>
 static hipError_t launch(const BeamParams& p, bool shared, hipStream_t stream) {
   constexpr int BPW = 64 / P;
@@ -580,9 +572,7 @@ using namespace opsamd;
 
 extern "C" {
 
-int ops_amd_abi_version(void) { return OPS_AMD_ABI_VERSION; }
 int ops_amd_max_elements(void) { return 64 * 16 - 1; }
-const char* ops_amd_last_error(void) { return g_last_error; }
 
 const char* ops_beam_solve_kernel_name(int B, int Ne, int tiling) {
   tiling &= ~OPS_AMD_TILING_STREAM_OUT;

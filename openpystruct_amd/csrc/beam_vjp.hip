@@ -14,10 +14,9 @@
 #include "../../include/openpystruct_amd.h"
 #include "beam_adjoint.hpp"
 #include "beam_io.hpp"
+#include "library.hpp"
 
 namespace opsamd {
-
-void set_last_error(const char* msg);   // beam_solve.hip
 
 struct VjpParams {
   int B, Ne;

@@ -17,6 +17,7 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "repack_tiles.hpp"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
@@ -93,11 +94,7 @@ __global__ __launch_bounds__(FA_THREADS) void flat_adam_kernel(long n, float* __
     vi = __builtin_fmaf(beta2, vi, (1.0f - beta2) * gi * gi);
     return pi - step_size * (mi / (sqrtf(vi) / bc2s + eps));
   };
-  auto to_bf16 = [](float f) -> uint16_t {                 // round to nearest even (parameters are finite)
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-  };
+  auto to_bf16 = [](float f) -> uint16_t { return (uint16_t)(bf16_rne_bits(__float_as_uint(f)) >> 16); };   // (parameters are finite)
   // 16-byte groups (the four flat buffers are framework allocations: 16-byte aligned; otherwise everything takes the scalar loop)
   const bool al = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) && (!shadow || ((uintptr_t)shadow & 7) == 0);
   const long n4 = al ? n >> 2 : 0;

@@ -1,5 +1,5 @@
 // Batched 2-D frame solve, third generation (r06): SEVERAL FRAMES PER WAVEFRONT for the narrow bands the reference actually draws.
-// (included by frame_solve.hip after frame_wave.hpp: FrameParams, frcp, write_results, FwPlan, fw_dpp, fw_fence come from there)
+// (included by frame_solve.hip after frame_wave.hpp: FrameParams, frcp, write_results, FwPlan, fw_fence come from there)
 //
 // /root/reference/OpenPyStruct_FrameOpt_Discrete_Beta.py:17-18, :50-52 draws bays, stories ~ U{1..10}; along the short side of the grid
 // (FrameTopology(numbering="auto")) the half bandwidth is kd = 3 m + 2, m = min(stories, bays + 1): 97 of the 100 draws have kd < 32 and
@@ -196,9 +196,9 @@ __device__ __forceinline__ void fp_backward(const double* __restrict__ Lc, doubl
       if (m & 1) acc1 = __builtin_fma(l, x, acc1); else acc0 = __builtin_fma(l, x, acc0);
     }
     double s_ = acc0 + acc1;
-    s_ += fw_dpp<0xB1>(s_);                               // quad_perm [1,0,3,2]
-    s_ += fw_dpp<0x4E>(s_);                               // quad_perm [2,3,0,1]
-    s_ += fw_dpp<0x141>(s_);                              // row_half_mirror: the eight lanes of a column hold its sum
+    s_ += dpp_mov<0xB1>(s_);                               // quad_perm [1,0,3,2]
+    s_ += dpp_mov<0x4E>(s_);                               // quad_perm [2,3,0,1]
+    s_ += dpp_mov<0x141>(s_);                              // row_half_mirror: the eight lanes of a column hold its sum
     if (k == 0) tb[u] = xs[jc] - s_;
     fp_order();
     double x[U], tr[NT];

@@ -30,12 +30,9 @@
 #include <stdlib.h>
 
 #include <atomic>
-#include <string_view>
 
 #include "../../include/openpystruct_amd.h"
-
-namespace opsamd { void set_last_error(const char* msg); }   // beam_solve.hip: what ops_amd_last_error() reports
-static inline void set_frame_error(const char* msg) { opsamd::set_last_error(msg); }
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -586,40 +583,6 @@ using namespace opsamd;
 
 static const size_t LDS_MAX = 160 * 1024 - 64;
 
-// ---- library options (ops_amd_set_option: the one place a caller -- tests, A/B scripts -- steers the dispatch; no environment variable is read) ----
-static std::atomic<long> g_frame_latency_batch{-1};      // "frame_latency_batch": -1 = the model below; 0 = tuned kernels for every batch
-static std::atomic<long> g_frame_coop{1};                // "frame_coop": 0 = never four waves per frame; 1 = where measured faster (default); 2 = for every small batch (A/B, tests)
-static std::atomic<long> g_frame_pack{1};                // "frame_pack": 0 = one wave per frame for every half bandwidth (A/B)
-static std::atomic<int> g_deterministic{0};              // "deterministic": 1 = fixed-order reductions in the Transformer-Diffusion step's gradient launches
-namespace opsamd {
-int deterministic_mode() { return g_deterministic.load(std::memory_order_relaxed); }
-void reset_head_ticket();              // seq_layer.hip
-}
-
-extern "C" int ops_amd_set_option(const char* name, long value) {
-  if (!name) return OPS_AMD_ERR_INVALID_ARG;
-  const std::string_view n(name);
-  if (n == "frame_latency_batch") { g_frame_latency_batch.store(value < 0 ? -1 : value); return OPS_AMD_OK; }
-  if (n == "frame_pack") { g_frame_pack.store(value != 0); return OPS_AMD_OK; }
-  if (n == "frame_coop") { if (value < 0 || value > 2) return OPS_AMD_ERR_INVALID_ARG; g_frame_coop.store(value); return OPS_AMD_OK; }
-  if (n == "deterministic") {
-    g_deterministic.store(value != 0);
-    int ndev = 0;
-    if (value != 0 && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) opsamd::reset_head_ticket();      // (current device; no GPU: nothing to re-arm)
-    return OPS_AMD_OK;
-  }
-  return OPS_AMD_ERR_INVALID_ARG;
-}
-extern "C" long ops_amd_get_option(const char* name) {
-  if (!name) return -2;
-  const std::string_view n(name);
-  if (n == "frame_latency_batch") return g_frame_latency_batch.load();
-  if (n == "frame_pack") return g_frame_pack.load();
-  if (n == "frame_coop") return g_frame_coop.load();
-  if (n == "deterministic") return g_deterministic.load();
-  return -2;
-}
-
 static size_t frame_lds_resident_bytes(int n_eq, int kd) {
   return ((size_t)frame_n3(n_eq) * frame_ld(kd) + frame_n3(n_eq)) * sizeof(double);
 }
@@ -648,11 +611,11 @@ static int eff_kd(int half_bandwidth) { return half_bandwidth < 3 ? 3 : half_ban
 // what one launch of the tuned kernels never takes less than (one wave's chain): fit of r06, see latency_batch
 static double tuned_floor_seconds(int n_eq, int kd) {
   int P, G, W;
-  const bool pack = g_frame_pack.load() && fp_config(kd, &P, &G, &W);
+  const bool pack = frame_pack_option() && fp_config(kd, &P, &G, &W);
   return pack ? 10e-6 + 0.5e-6 * n_eq : (0.275e-6 + 0.0075e-6 * kd) * n_eq;
 }
 static int latency_batch(int n_eq, int kd) {
-  const long o = g_frame_latency_batch.load();
+  const long o = frame_latency_batch_option();
   if (o >= 0) return (int)(o > 0x7fffffff ? 0x7fffffff : o);
   // r06 fit (scripts/frame_dispatch_sweep.py on the packed kernel, profiles/r06_frame_dispatch_sweep.txt): a launch of the tuned kernels never
   // takes less than one wave's chain -- packed (kd <= 29): ~10 us + 0.5 us per equation (2 x 2: 17 us, 5 x 5: 47, 8 x 8: 123); a wave per frame:
@@ -691,9 +654,9 @@ static FrameFamily frame_family(int B, int n_eq, int kd) {
   // once per CU and needs a second round (10 x 10, 384-768 frames: 140-162 us against 204-306 and 189; 12 x 12, 512: 226 / 290 / 312); its cost
   // ~0.37 us per equation, +15 % per further frame per CU, is held against the tuned kernels' floor.  An explicit "frame_latency_batch" option keeps
   // its meaning: that many frames or fewer never take the tuned kernels.
-  const bool lat_forced = g_frame_latency_batch.load() >= 0;
+  const bool lat_forced = frame_latency_batch_option() >= 0;
   const int lat = latency_batch(n_eq, kd);
-  const bool coop_ok = g_frame_coop.load() && fc_lds_doubles(n_eq, fc_width(kd)) * sizeof(double) <= LDS_MAX;
+  const bool coop_ok = frame_coop_option() && fc_lds_doubles(n_eq, fc_width(kd)) * sizeof(double) <= LDS_MAX;
   const bool legacy_ok = legacy_kernels_serve(n_eq, kd);
   const size_t band = frame_lds_resident_bytes(n_eq, kd);
   if (coop_ok && !lat_forced) {
@@ -703,13 +666,13 @@ static FrameFamily frame_family(int B, int n_eq, int kd) {
     if (band > LDS_MAX / 2 && B > 256 && B <= coop_max && coop_s < tuned_floor_seconds(n_eq, kd)) return FAM_COOP;
   }
   if (B <= lat) {
-    if (coop_ok && g_frame_coop.load() == 2) return FAM_COOP;
+    if (coop_ok && frame_coop_option() == 2) return FAM_COOP;
     if (legacy_ok && (band <= LDS_MAX || !coop_ok)) return FAM_LEGACY;
     if (coop_ok) return FAM_COOP;
   }
   int P, G, W;
   // the packed kernel's 8 or 16 frames per workgroup keep x (n_eq) and their parking areas in LDS (+ the inertias if those fit too: launch_pack)
-  if (g_frame_pack.load() && fp_config(kd, &P, &G, &W) && 4 * (size_t)(64 / P) * fp_lds_doubles(n_eq, 0, P, G, W) * sizeof(double) <= LDS_MAX)
+  if (frame_pack_option() && fp_config(kd, &P, &G, &W) && 4 * (size_t)(64 / P) * fp_lds_doubles(n_eq, 0, P, G, W) * sizeof(double) <= LDS_MAX)
     return FAM_PACK;
   // the wave kernel (window width 36 serves every narrower band): its four waves' LDS must fit one CU; frames beyond that (tall and narrow:
   // thousands of equations) take the workgroup-per-frame kernels, whose band streams through an LDS ring
@@ -735,87 +698,92 @@ static hipError_t resident_workgroups(const void* fn, size_t lds, int devid, std
   return hipSuccess;
 }
 
+// the assembly plan at the start of the workspace (built here unless the caller reuses it); returns the factor storage behind it
+static double* frame_plan(const FrameParams& p, void* ws, hipStream_t s, bool reuse_plan, int W, int G, int EPG, FwPlan* pl) {
+  *pl = fw_plan_at(ws, p.n_eq, p.Ne, G, EPG);
+  if (!reuse_plan)
+    hipLaunchKernelGGL(frame_plan_kernel, dim3(1), dim3(1024), (size_t)3 * (fw_groups(p.n_eq, G) + 2) * sizeof(int), s, p, W, ws, G, EPG);
+  return (double*)((char*)ws + plan_region_bytes(p.n_eq, G, EPG));
+}
+
 template <int W, int P, int G>
-static hipError_t launch_pack(const FrameParams& p, double* ws, hipStream_t s, bool reuse_plan) {
-  static std::atomic<unsigned long long> done{0};
+static hipError_t launch_pack(const FrameParams& p, void* ws, hipStream_t s, bool reuse_plan, int devid) {
   static std::atomic<long long> cap_key[64];
   static std::atomic<int> cap_val[64];
-  int devid = 0;
-  hipError_t e = hipGetDevice(&devid);
+  hipError_t e = set_lds_limit_once<frame_pack_kernel<W, P, G>>(devid, (int)LDS_MAX);
   if (e != hipSuccess) return e;
   constexpr int F = 64 / P;
   const bool stage_I = 4 * (size_t)F * fp_lds_doubles(p.n_eq, p.Ne, P, G, W) * sizeof(double) <= LDS_MAX / 2;     // (at least two workgroups per CU)
   const int ne_lds = stage_I ? p.Ne : 0;
   const size_t lds = 4 * (size_t)F * fp_lds_doubles(p.n_eq, ne_lds, P, G, W) * sizeof(double);
-  const unsigned long long bit = 1ull << (devid & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    e = hipFuncSetAttribute((const void*)frame_pack_kernel<W, P, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-  }
   int cap = 0;
   e = resident_workgroups((const void*)frame_pack_kernel<W, P, G>, lds, devid, cap_key, cap_val, &cap);
   if (e != hipSuccess) return e;
   const long need = ((long)p.B + 4 * F - 1) / (4 * F);
   const unsigned grid = (unsigned)(need < cap ? need : cap);
-  void* plan_base = ws;
-  double* factor = (double*)((char*)ws + plan_region_bytes(p.n_eq, G, fp_epg(G)));
-  const FwPlan pl = fw_plan_at(plan_base, p.n_eq, p.Ne, G, fp_epg(G));
-  if (!reuse_plan)
-    hipLaunchKernelGGL(frame_plan_kernel, dim3(1), dim3(1024), (size_t)3 * (fw_groups(p.n_eq, G) + 2) * sizeof(int), s, p, W, plan_base, G, fp_epg(G));
+  FwPlan pl;
+  double* factor = frame_plan(p, ws, s, reuse_plan, W, G, fp_epg(G), &pl);
   hipLaunchKernelGGL((frame_pack_kernel<W, P, G>), dim3(grid), dim3(256), lds, s, p, factor, pl, ne_lds);
   return hipGetLastError();
 }
 
 template <int W>
-static hipError_t launch_wave(const FrameParams& p, double* ws_all, hipStream_t s, bool reuse_plan) {
-  static std::atomic<unsigned long long> done{0};
-  int devid = 0;
-  hipError_t e = hipGetDevice(&devid);
+static hipError_t launch_wave(const FrameParams& p, void* ws, hipStream_t s, bool reuse_plan, int devid) {
+  const hipError_t e = set_lds_limit_once<frame_wave_kernel<W>>(devid, (int)LDS_MAX);
   if (e != hipSuccess) return e;
   const size_t lds = 4 * fw_lds_doubles(p.n_eq, W) * sizeof(double);      // size limits: frame_family (checked by the caller)
-  const unsigned long long bit = 1ull << (devid & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    e = hipFuncSetAttribute((const void*)frame_wave_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-  }
-  void* plan_base = ws_all;
-  double* ws = (double*)((char*)ws_all + plan_region_bytes(p.n_eq, FW_G, FW_EPG));
-  const FwPlan pl = fw_plan_at(plan_base, p.n_eq, p.Ne);
-  if (!reuse_plan)
-    hipLaunchKernelGGL(frame_plan_kernel, dim3(1), dim3(1024), (size_t)3 * (fw_groups(p.n_eq) + 2) * sizeof(int), s, p, W, plan_base, FW_G, FW_EPG);
-  hipLaunchKernelGGL((frame_wave_kernel<W>), dim3((unsigned)((p.B + 3) / 4)), dim3(256), lds, s, p, ws, pl);
+  FwPlan pl;
+  double* factor = frame_plan(p, ws, s, reuse_plan, W, FW_G, FW_EPG, &pl);
+  hipLaunchKernelGGL((frame_wave_kernel<W>), dim3((unsigned)((p.B + 3) / 4)), dim3(256), lds, s, p, factor, pl);
   return hipGetLastError();
 }
 
 template <int W>
-static hipError_t launch_coop(const FrameParams& p, double* ws_all, hipStream_t s, bool reuse_plan) {
-  static std::atomic<unsigned long long> done{0};
-  int devid = 0;
-  hipError_t e = hipGetDevice(&devid);
+static hipError_t launch_coop(const FrameParams& p, void* ws, hipStream_t s, bool reuse_plan, int devid) {
+  const hipError_t e = set_lds_limit_once<frame_coop_kernel<W>>(devid, (int)LDS_MAX);
   if (e != hipSuccess) return e;
   const size_t lds = fc_lds_doubles(p.n_eq, W) * sizeof(double);          // size limit: frame_family (checked by the caller)
-  const unsigned long long bit = 1ull << (devid & 63);
-  if (!(done.load(std::memory_order_acquire) & bit)) {
-    e = hipFuncSetAttribute((const void*)frame_coop_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-    if (e != hipSuccess) return e;
-    done.fetch_or(bit, std::memory_order_release);
-  }
-  void* plan_base = ws_all;
-  double* ws = (double*)((char*)ws_all + plan_region_bytes(p.n_eq, FW_G, FW_EPG));
-  const FwPlan pl = fw_plan_at(plan_base, p.n_eq, p.Ne);
-  if (!reuse_plan)
-    hipLaunchKernelGGL(frame_plan_kernel, dim3(1), dim3(1024), (size_t)3 * (fw_groups(p.n_eq) + 2) * sizeof(int), s, p, W, plan_base, FW_G, FW_EPG);
-  hipLaunchKernelGGL((frame_coop_kernel<W>), dim3((unsigned)p.B), dim3(64 * FC_NW), lds, s, p, ws, pl);
+  FwPlan pl;
+  double* factor = frame_plan(p, ws, s, reuse_plan, W, FW_G, FW_EPG, &pl);
+  hipLaunchKernelGGL((frame_coop_kernel<W>), dim3((unsigned)p.B), dim3(64 * FC_NW), lds, s, p, factor, pl);
   return hipGetLastError();
 }
 
-extern "C" size_t ops_frame_workspace_bytes(int B, int n_eq, int half_bandwidth) {
-  if (B <= 0 || n_eq < 1 || half_bandwidth < 0) return 0;
-  const int kd = eff_kd(half_bandwidth);
-  switch (frame_family(B, n_eq, kd)) {
-    case FAM_WIDE: return (size_t)B * frame_lds_resident_bytes(n_eq, kd);      // frame_wide_kernel: the band always lives in HBM
+// the tuned kernels (packed, wave, four waves per frame): the compiled window width that serves kd
+static hipError_t launch_tuned(FrameFamily fam, int kd, const FrameParams& p, void* ws, hipStream_t s, bool reuse_plan, int devid) {
+  if (fam == FAM_PACK) {
+    int P, G, W;
+    fp_config(kd, &P, &G, &W);
+    switch (W) {
+      case 6: return launch_pack<6, 16, 4>(p, ws, s, reuse_plan, devid);
+      case 10: return launch_pack<10, 16, 4>(p, ws, s, reuse_plan, devid);
+      case 12: return launch_pack<12, 16, 4>(p, ws, s, reuse_plan, devid);
+      case 16: return launch_pack<16, 32, 8>(p, ws, s, reuse_plan, devid);
+      case 18: return launch_pack<18, 32, 8>(p, ws, s, reuse_plan, devid);
+      case 22: return launch_pack<22, 32, 8>(p, ws, s, reuse_plan, devid);
+      case 24: return launch_pack<24, 32, 8>(p, ws, s, reuse_plan, devid);
+      case 28: return launch_pack<28, 32, 4>(p, ws, s, reuse_plan, devid);
+      default: return launch_pack<30, 32, 2>(p, ws, s, reuse_plan, devid);
+    }
+  }
+  if (fam == FAM_COOP) {
+    switch (fc_width(kd)) {
+      case 20: return launch_coop<20>(p, ws, s, reuse_plan, devid);
+      case 36: return launch_coop<36>(p, ws, s, reuse_plan, devid);
+      case 52: return launch_coop<52>(p, ws, s, reuse_plan, devid);
+      default: return launch_coop<56>(p, ws, s, reuse_plan, devid);
+    }
+  }
+  switch (fw_width(kd)) {
+    case 36: return launch_wave<36>(p, ws, s, reuse_plan, devid);
+    case 52: return launch_wave<52>(p, ws, s, reuse_plan, devid);
+    default: return launch_wave<56>(p, ws, s, reuse_plan, devid);
+  }
+}
+
+// the workspace a call of family `fam` needs (0: none): what ops_frame_workspace_bytes reports and what the solve checks
+static size_t frame_workspace_need(FrameFamily fam, int B, int n_eq, int kd) {
+  switch (fam) {
     case FAM_PACK: {                               // per frame: the columns of L (the kernel uses one slot per resident wave); once: the plan
       int P, G, W;
       fp_config(kd, &P, &G, &W);
@@ -823,10 +791,17 @@ extern "C" size_t ops_frame_workspace_bytes(int B, int n_eq, int half_bandwidth)
     }
     case FAM_WAVE: return (size_t)B * fw_frame_doubles(n_eq, kd) * sizeof(double) + plan_region_bytes(n_eq, FW_G, FW_EPG);
     case FAM_COOP: return (size_t)B * fc_frame_doubles(n_eq, kd) * sizeof(double) + plan_region_bytes(n_eq, FW_G, FW_EPG);
+    case FAM_WIDE: return (size_t)B * frame_lds_resident_bytes(n_eq, kd);      // frame_wide_kernel: the band always lives in HBM
     default: break;
   }
   if (frame_lds_resident_bytes(n_eq, kd) <= LDS_MAX) return 0;   // the band lives in LDS
   return (size_t)B * frame_lds_resident_bytes(n_eq, kd);
+}
+
+extern "C" size_t ops_frame_workspace_bytes(int B, int n_eq, int half_bandwidth) {
+  if (B <= 0 || n_eq < 1 || half_bandwidth < 0) return 0;
+  const int kd = eff_kd(half_bandwidth);
+  return frame_workspace_need(frame_family(B, n_eq, kd), B, n_eq, kd);
 }
 
 // which plan (if any) a call of this shape builds at the start of its workspace: 0 = none; equal values = interchangeable plans
@@ -866,30 +841,24 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
   if (half_bandwidth > FRAME_WIDE_MAX_KD) return OPS_AMD_ERR_UNSUPPORTED;
   const int kd = eff_kd(half_bandwidth);
   const size_t lds_bytes = frame_lds_resident_bytes(n_eq, kd);
+  int devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
   {
-    // the dynamic-LDS limit is a per-DEVICE function attribute: set once per device this thread-safe way (a process may
-    // drive several GPUs: ops.set_device / FrameTopology(device=...))
-    static std::atomic<unsigned long long> attr_done{0};
-    int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
-    const unsigned long long bit = 1ull << devid;
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-      hipError_t e = hipFuncSetAttribute((const void*)frame_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)frame_assemble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)frame_factor_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)frame_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX);
-      if (e != hipSuccess) { set_frame_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-      attr_done.fetch_or(bit, std::memory_order_release);      // idempotent: two threads racing here both set the same value
-    }
+    hipError_t e = set_lds_limit_once<frame_solve_kernel>(devid, (int)LDS_MAX);
+    if (e == hipSuccess) e = set_lds_limit_once<frame_assemble_kernel>(devid, (int)LDS_MAX);
+    if (e == hipSuccess) e = set_lds_limit_once<frame_factor_big_kernel>(devid, (int)LDS_MAX);
+    if (e == hipSuccess) e = set_lds_limit_once<frame_wide_kernel>(devid, (int)LDS_MAX);
+    if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
   }
   FrameParams p{B, n_nodes, n_elems, n_eq, kd, elem_geo, elem_EA, elem_E, elem_w, elem_eq, node_eq,
                 I, loads, loads_bstride, disp, forces, V, M, status};
   hipStream_t s = (hipStream_t)stream;
   const FrameFamily fam = frame_family(B, n_eq, kd);
+  const size_t need = frame_workspace_need(fam, B, n_eq, kd);
   if (fam == FAM_WIDE) {
     // the window rows of a block step are one 64-lane wave: beyond that, the plain column-by-column fallback on the band in HBM
     const int ld = frame_ld(kd), n3 = frame_n3(n_eq);
-    const size_t need = (size_t)B * lds_bytes, lds_wide = ((size_t)n3 + ld) * sizeof(double);
+    const size_t lds_wide = ((size_t)n3 + ld) * sizeof(double);
     if (lds_wide > LDS_MAX) return OPS_AMD_ERR_UNSUPPORTED;
     long slab = ((long)(LDS_MAX / sizeof(double)) - n3) / ld;          // columns per LDS slab of the assembly
     if (slab > FRAME_SLAB_MAX) slab = FRAME_SLAB_MAX;
@@ -899,51 +868,10 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
     hipLaunchKernelGGL(frame_wide_kernel, dim3((unsigned)B), dim3(1024), lds_wide, s, p, (double*)workspace);
     return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
   }
-  if (fam == FAM_PACK) {
-    int P, G, W;
-    fp_config(kd, &P, &G, &W);
-    const size_t need = pack_slots(B, P) * fp_frame_doubles(n_eq, W) * sizeof(double) + plan_region_bytes(n_eq, G, fp_epg(G));
+  if (fam == FAM_PACK || fam == FAM_COOP || fam == FAM_WAVE) {
     if (!workspace || workspace_bytes < need || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
-    hipError_t e = hipSuccess;
-    switch (W) {
-      case 6: e = launch_pack<6, 16, 4>(p, (double*)workspace, s, reuse_plan); break;
-      case 10: e = launch_pack<10, 16, 4>(p, (double*)workspace, s, reuse_plan); break;
-      case 12: e = launch_pack<12, 16, 4>(p, (double*)workspace, s, reuse_plan); break;
-      case 16: e = launch_pack<16, 32, 8>(p, (double*)workspace, s, reuse_plan); break;
-      case 18: e = launch_pack<18, 32, 8>(p, (double*)workspace, s, reuse_plan); break;
-      case 22: e = launch_pack<22, 32, 8>(p, (double*)workspace, s, reuse_plan); break;
-      case 24: e = launch_pack<24, 32, 8>(p, (double*)workspace, s, reuse_plan); break;
-      case 28: e = launch_pack<28, 32, 4>(p, (double*)workspace, s, reuse_plan); break;
-      default: e = launch_pack<30, 32, 2>(p, (double*)workspace, s, reuse_plan); break;
-    }
-    if (e != hipSuccess) { set_frame_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-    return OPS_AMD_OK;
-  }
-  if (fam == FAM_COOP) {
-    const int W = fc_width(kd);
-    const size_t need = (size_t)B * fc_frame_doubles(n_eq, kd) * sizeof(double) + plan_region_bytes(n_eq, FW_G, FW_EPG);
-    if (!workspace || workspace_bytes < need || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
-    hipError_t e = hipSuccess;
-    switch (W) {
-      case 20: e = launch_coop<20>(p, (double*)workspace, s, reuse_plan); break;
-      case 36: e = launch_coop<36>(p, (double*)workspace, s, reuse_plan); break;
-      case 52: e = launch_coop<52>(p, (double*)workspace, s, reuse_plan); break;
-      default: e = launch_coop<56>(p, (double*)workspace, s, reuse_plan); break;
-    }
-    if (e != hipSuccess) { set_frame_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-    return OPS_AMD_OK;
-  }
-  if (fam == FAM_WAVE) {
-    const int W = fw_width(kd);
-    const size_t need = (size_t)B * fw_frame_doubles(n_eq, kd) * sizeof(double) + plan_region_bytes(n_eq, FW_G, FW_EPG);
-    if (!workspace || workspace_bytes < need || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
-    hipError_t e = hipSuccess;
-    switch (W) {
-      case 36: e = launch_wave<36>(p, (double*)workspace, s, reuse_plan); break;
-      case 52: e = launch_wave<52>(p, (double*)workspace, s, reuse_plan); break;
-      default: e = launch_wave<56>(p, (double*)workspace, s, reuse_plan); break;
-    }
-    if (e != hipSuccess) { set_frame_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
+    const hipError_t e = launch_tuned(fam, kd, p, workspace, s, reuse_plan, devid);
+    if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
     return OPS_AMD_OK;
   }
   const bool resident = lds_bytes <= LDS_MAX;
@@ -952,7 +880,6 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
   if (!resident) {
     // band in the HBM workspace, sliding LDS ring
     const int ld = frame_ld(kd), n3 = frame_n3(n_eq);
-    const size_t need = (size_t)B * lds_bytes;
     const size_t lds2 = ((size_t)(kd + 6) * ld + (size_t)n3 + 2 * (size_t)FRAME_CH * ld) * sizeof(double);
     if (lds2 > LDS_MAX) return OPS_AMD_ERR_UNSUPPORTED;
     if (!workspace || workspace_bytes < need) return OPS_AMD_ERR_INVALID_ARG;

@@ -34,6 +34,7 @@
 // the whole band of the reference's frames (kd = 3 (bays + 1) + 2 <= 35) and its panel factorisation is the serial part
 // (and the FP64 matrix rate of the MI355X equals its vector rate).
 #pragma once
+#include "lane_common.hpp"
 
 namespace opsamd {
 
@@ -50,14 +51,6 @@ __host__ __device__ inline size_t fw_lds_doubles(int n, int W) { return ((2 * FW
 __device__ __forceinline__ double fw_readlane(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
-}
-// DPP move of a double (quad_perm, row_half_mirror, ...: no LDS)
-template <int CTRL>
-__device__ __forceinline__ double fw_dpp(double x) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 // LDS operations of one wave execute in order; this pins the compiler and lands earlier reads
 __device__ __forceinline__ void fw_fence() {
@@ -308,9 +301,9 @@ __device__ __forceinline__ void fw_backward(const double* __restrict__ rows, dou
       if (m & 1) acc1 = __builtin_fma(l, x, acc1); else acc0 = __builtin_fma(l, x, acc0);
     }
     double s_ = acc0 + acc1;
-    s_ += fw_dpp<0xB1>(s_);                               // quad_perm [1,0,3,2]
-    s_ += fw_dpp<0x4E>(s_);                               // quad_perm [2,3,0,1]
-    s_ += fw_dpp<0x141>(s_);                              // row_half_mirror: the eight lanes of a group hold its sum
+    s_ += dpp_mov<0xB1>(s_);                               // quad_perm [1,0,3,2]
+    s_ += dpp_mov<0x4E>(s_);                               // quad_perm [2,3,0,1]
+    s_ += dpp_mov<0x141>(s_);                              // row_half_mirror: the eight lanes of a group hold its sum
     double t = xs[jc] - s_;
 #pragma unroll
     for (int v = 0; v < 7; ++v) {                         // x of column j_v is final when its turn comes

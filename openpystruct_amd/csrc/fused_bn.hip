@@ -27,6 +27,7 @@
 #include "../../include/openpystruct_amd.h"
 #include "dropout_stream.hpp"
 #include "call_counter.hpp"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
@@ -35,20 +36,12 @@ constexpr int FB_RG = 16;        // row groups per workgroup (256 threads)
 constexpr int FB_RPT = 8;        // rows a thread keeps in registers: batches up to FB_RG * FB_RPT = 128 rows take ONE pass over memory
 
 __device__ __forceinline__ float fb_ld(const void* p, long i, int bf16) {
-  return bf16 ? __uint_as_float((uint32_t)((const uint16_t*)p)[i] << 16) : ((const float*)p)[i];
-}
-__device__ __forceinline__ uint16_t fb_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
+  return bf16 ? bf16_to_f32(((const uint16_t*)p)[i]) : ((const float*)p)[i];
 }
 __device__ __forceinline__ void fb_st(void* p, long i, int bf16, float v) {
-  if (bf16) ((uint16_t*)p)[i] = fb_f2bf(v);
+  if (bf16) ((uint16_t*)p)[i] = f32_to_bf16(v);
   else ((float*)p)[i] = v;
 }
-// splitmix64 finaliser: a counter-based uniform in [0, 1)
-__device__ __forceinline__ float fb_uniform(uint64_t seed, uint64_t call, uint64_t idx) { return drop_uniform(seed, call, idx); }   // csrc/dropout_stream.hpp
 // sum over the FB_RG row groups of a column (threads t, t + 32, ...): every thread of the column gets the total
 __device__ __forceinline__ float fb_colsum(float v, float* s_red, int col, int rg) {
   __syncthreads();
@@ -90,7 +83,7 @@ __global__ __launch_bounds__(256) void fused_bn_fwd_kernel(const FbArgs a) {
     if (a.x3) z += fb_ld(a.x3, i, bf);
     // bfloat16 activations: normalise the value that is SAVED for the backward pass (the sum rounded to bfloat16), so that the
     // LeakyReLU sees the same pre-activation sign in both directions (and the framework's bf16 sum is what it would see too)
-    if (bf && (a.x2 || a.x3)) z = __uint_as_float((uint32_t)fb_f2bf(z) << 16);
+    if (bf && (a.x2 || a.x3)) z = bf16_round(z);
     return z;
   };
   // rows of this thread: rg, rg + FB_RG, ...; the first FB_RPT of them live in registers
@@ -160,7 +153,7 @@ __global__ __launch_bounds__(256) void fused_bn_fwd_kernel(const FbArgs a) {
       float y = a.gamma ? __builtin_fmaf((z - mean) * rstd, g, be) : z;
       if (a.use_act) y = y > 0.0f ? y : y * a.slope;
       if (drop) {
-        const bool keep = fb_uniform(a.seed, call, (unsigned long long)i) >= a.p_drop;
+        const bool keep = drop_uniform(a.seed, call, (unsigned long long)i) >= a.p_drop;
         a.mask[i] = keep ? 1 : 0;
         y = keep ? y * keep_scale : 0.0f;
       }

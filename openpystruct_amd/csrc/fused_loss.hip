@@ -12,18 +12,12 @@
 #include <stdint.h>
 
 #include "../../include/openpystruct_amd.h"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
 constexpr int FL_THREADS = 256;
 constexpr int FL_MAXG = 128;
-
-__device__ __forceinline__ uint16_t fl_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 __global__ __launch_bounds__(FL_THREADS) void fused_loss_kernel(int B, int C, int nI, int nD, const void* __restrict__ preds, int bf16,
                                                                  const float* __restrict__ targets, const float* __restrict__ alpha_p,
@@ -40,7 +34,7 @@ __global__ __launch_bounds__(FL_THREADS) void fused_loss_kernel(int B, int C, in
   const long n = (long)B * C;
   for (long e = (long)blockIdx.x * FL_THREADS + threadIdx.x; e < n; e += (long)gridDim.x * FL_THREADS) {
     const int col = (int)(e % C);
-    const float p = bf16 ? __uint_as_float((uint32_t)((const uint16_t*)preds)[e] << 16) : ((const float*)preds)[e];
+    const float p = bf16 ? bf16_to_f32(((const uint16_t*)preds)[e]) : ((const float*)preds)[e];
     const float t = targets[e], d = p - t, sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
     float g;
     if (col < nI) {
@@ -54,14 +48,14 @@ __global__ __launch_bounds__(FL_THREADS) void fused_loss_kernel(int B, int C, in
       if (col < nI + nD) { acc[3] += rel; g = penalty * sg / den * inv_nD; }
       else { acc[4] += rel; g = penalty * sg / den * inv_nR; }
     }
-    if (bf16) ((uint16_t*)grad)[e] = fl_f2bf(g);
+    if (bf16) ((uint16_t*)grad)[e] = f32_to_bf16(g);
     else ((float*)grad)[e] = g;
   }
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     double v = acc[k];
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);      // (open-coded: wave_sum compiles to different instructions here)
     if (lane == 0) s_red[wave][k] = v;
   }
   __syncthreads();

@@ -9,15 +9,9 @@
 #include "../../include/openpystruct_amd.h"
 #include "call_counter.hpp"
 #include "input_noise.hpp"
+#include "lane_common.hpp"
 
 namespace opsamd {
-
-__device__ __forceinline__ uint16_t ip_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 // VEC4: F % 4 == 0 and 16-byte aligned rows -- four consecutive features per thread and trip (one index load, one 16-byte row load,
 // one 8- or 16-byte store); the grid is at most 128 workgroups (call_counter.hpp), so the trips must be wide
@@ -38,8 +32,8 @@ __global__ __launch_bounds__(256) void gather_noise_kernel(int B, long F, const 
       const float v2 = ip_noisy(x.z, sg, seed, call, i + 2), v3 = ip_noisy(x.w, sg, seed, call, i + 3);
       if (out_bf16) {
         uint2 o;
-        o.x = (uint32_t)ip_f2bf(v0) | ((uint32_t)ip_f2bf(v1) << 16);
-        o.y = (uint32_t)ip_f2bf(v2) | ((uint32_t)ip_f2bf(v3) << 16);
+        o.x = (uint32_t)f32_to_bf16(v0) | ((uint32_t)f32_to_bf16(v1) << 16);
+        o.y = (uint32_t)f32_to_bf16(v2) | ((uint32_t)f32_to_bf16(v3) << 16);
         *(uint2*)((uint16_t*)out + i) = o;
       } else {
         *(float4*)((float*)out + i) = make_float4(v0, v1, v2, v3);
@@ -49,7 +43,7 @@ __global__ __launch_bounds__(256) void gather_noise_kernel(int B, long F, const 
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
       const long b = i / F, f = i - b * F;
       const float v = ip_noisy(X[idx[b] * F + f], sg, seed, call, i);
-      if (out_bf16) ((uint16_t*)out)[i] = ip_f2bf(v);
+      if (out_bf16) ((uint16_t*)out)[i] = f32_to_bf16(v);
       else ((float*)out)[i] = v;
     }
   }

@@ -39,13 +39,13 @@
 #include "dropout_stream.hpp"
 #include "call_counter.hpp"
 #include "repack_tiles.hpp"
+#include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
-#ifdef MB_EXP          // stand-alone experiment builds (scripts/mlp_launch_bench.py: 1 = no product, 2 = one reduction step)
+#ifdef MB_EXP          // stand-alone experiment builds (scripts/mlp_launch_bench.py: 1 = no product, 2 = one reduction step; no library.hip)
 inline void set_last_error(const char*) {}
-#else
-void set_last_error(const char* msg);   // beam_solve.hip: what ops_amd_last_error() reports
 #endif
 
 typedef __bf16 mb_bf16x8 __attribute__((ext_vector_type(8)));
@@ -56,14 +56,6 @@ constexpr int MB_COLS = 16;                 // output columns per workgroup
 constexpr int MB_THREADS = 512;             // 8 waves, one 16 x 16 MFMA tile each
 constexpr int MB_NSUM = 12;                 // backward stencil sums per workgroup
 
-__device__ __forceinline__ float mb_bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t mb_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float mb_round(float f) { return mb_bf2f(mb_f2bf(f)); }
 // Fragment-tiled storage of a [rows, K] bf16 matrix (rows padded to 16, K to 32; KS = K / 32): tile (rows >> 4, k >> 5) is 1 KB,
 // stored in MFMA lane order -- lane = ((k >> 3) & 3) << 4 | (row & 15) holds 8 consecutive k -- so one wave-wide 16-byte load IS
 // the A / B fragment of `v_mfma_f32_16x16x32_bf16` and touches 8 whole cache lines (row-major storage: 16 half lines per load,
@@ -72,20 +64,7 @@ __device__ __forceinline__ long mb_toff(int row, int k, int KS) {
   return ((long)(row >> 4) * KS + (k >> 5)) * 512 + ((k >> 3) & 3) * 128 + (row & 15) * 8 + (k & 7);
 }
 // element (row r, column c) of a matrix whose TRANSPOSED copy [cols, 128] is stored tiled (rows = c, k = r, KS = 4)
-__device__ __forceinline__ float mb_ldt(const void* p, int c, int r) { return mb_bf2f(((const uint16_t*)p)[mb_toff(c, r, MB_ROWS / 32)]); }
-// sum over the 32 lanes that share a column (a half wave)
-__device__ __forceinline__ float mb_hsum(float v) {
-#pragma unroll
-  for (int s = 16; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-__device__ __forceinline__ double mb_wsum_d(double v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-// splitmix64 finaliser: a counter-based uniform in [0, 1) (the stream of csrc/fused_bn.hip)
-__device__ __forceinline__ float mb_uniform(uint64_t seed, uint64_t call, uint64_t idx) { return drop_uniform(seed, call, idx); }   // csrc/dropout_stream.hpp
+__device__ __forceinline__ float mb_ldt(const void* p, int c, int r) { return bf16_to_f32(((const uint16_t*)p)[mb_toff(c, r, MB_ROWS / 32)]); }
 
 // ---- the product: one 16 x 16 tile per wave, reduction in steps of 32, fragments straight from global memory ----
 // lane l holds A[row l&15][k = 8 (l>>4) + j] and B[k][col l&15] (j = 0..7): 16 contiguous bytes of a row of either operand, and
@@ -131,6 +110,7 @@ __device__ __forceinline__ float mb_conv_at(const void* Ot, int No, int q, int r
 }
 
 // sums NV floats over the workgroup -- float inside a wave (64 terms), double across the waves; thread 0 gets the totals in `out`
+// (not block_sum of lane_common.hpp: float wave sums; written with wave_sum, the kernels compile to different instructions)
 template <int NV>
 __device__ __forceinline__ void mb_block_sum_f(const float (&v)[NV], double (&out)[NV], double* s_red /*[8][NV]*/) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -152,25 +132,6 @@ __device__ __forceinline__ void mb_block_sum_f(const float (&v)[NV], double (&ou
       double t = 0.0;
       for (int wv = 0; wv < MB_THREADS / 64; ++wv) t += s_red[wv * NV + k];
       out[k] = t;
-    }
-}
-// sums NV doubles over the workgroup; thread 0 gets the totals
-template <int NV>
-__device__ __forceinline__ void mb_block_sum(double (&v)[NV], double* s_red /*[8][NV]*/) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = mb_wsum_d(v[k]);
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s_red[wave * NV + k] = v[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      double t = 0.0;
-      for (int w = 0; w < MB_THREADS / 64; ++w) t += s_red[w * NV + k];
-      v[k] = t;
     }
 }
 
@@ -355,7 +316,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
     for (int i = 0; i < 4; ++i) s_t[wave * 16 + (lane >> 4) * 4 + i][lane & 15] = acc[i];
   }
   if (a_add_mode != OPS_MLP_ADD_NONE) {
-    pp0 = mb_wsum_d(pp0); pp1 = mb_wsum_d(pp1);
+    pp0 = wave_sum(pp0); pp1 = wave_sum(pp1);
     if (lane == 0) { s_tot[wave] = pp0; s_tot[wave + 8] = pp1; }
   }
 #pragma unroll
@@ -363,7 +324,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
     if (chv[rep]) *(uint4*)&s_stage[(tid + MB_THREADS * rep) >> 4][8 * (tid & 15)] = ch[rep];
   if (fin) {
 #pragma unroll
-    for (int k = 0; k < 5; ++k) lp[k] = mb_wsum_d(lp[k]);
+    for (int k = 0; k < 5; ++k) lp[k] = wave_sum(lp[k]);
     if (lane == 0) {
       const double al = fmin(fmax((double)a.alpha[0], 1e-6), 1.0);
       const int nI = a.nI, nD = a.nD, nR = a.loss_C - nI - nD;
@@ -387,9 +348,9 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
   float lacc[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // TAIL_LOSS: sum |d|_I, sum d^2_I, sum box penalty, sum rel_d, sum rel_r
 
   if (fwd) {
-    const float bias_b = mb_round(bias);
+    const float bias_b = bf16_round(bias);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = rl[i] ? mb_round(v[i] + bias_b) : 0.0f;       // the Linear's bf16 output
+    for (int i = 0; i < 4; ++i) v[i] = rl[i] ? bf16_round(v[i] + bias_b) : 0.0f;       // the Linear's bf16 output
     if (a_add_mode == OPS_MLP_ADD_FWD_BLOCK) {
       // whole-tensor statistics of conv1(O) from the previous launch's partial sums
       const double n = (double)B * (double)No, m = s_tot[0] / n, var = fmax(s_tot[1] / n - m * m, 0.0);
@@ -406,21 +367,21 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
       for (int i = 0; i < 4; ++i)
         if (rl[i]) {
           const int r = q + 32 * i;
-          const float o = mb_bf2f(s_stage[cl + 2][r]);
-          const float conv = __builtin_fmaf(sc_w0, mb_bf2f(s_stage[cl + 1][r]), __builtin_fmaf(sc_w1, o, __builtin_fmaf(sc_w2, mb_bf2f(s_stage[cl + 3][r]), sc_b)));
-          const float s = mb_round(__builtin_fmaf(conv, scale, shift));
-          v[i] = mb_round(v[i] + s + o);
+          const float o = bf16_to_f32(s_stage[cl + 2][r]);
+          const float conv = __builtin_fmaf(sc_w0, bf16_to_f32(s_stage[cl + 1][r]), __builtin_fmaf(sc_w1, o, __builtin_fmaf(sc_w2, bf16_to_f32(s_stage[cl + 3][r]), sc_b)));
+          const float s = bf16_round(__builtin_fmaf(conv, scale, shift));
+          v[i] = bf16_round(v[i] + s + o);
         }
     }
     if (has_bn) {
       float sm = 0.0f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) sm += v[i];                 // dead rows hold 0
-      float mean = mb_hsum(sm) * invB;
+      float mean = wave_sum<32>(sm) * invB;
       float sq = 0.0f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) { const float d = v[i] - mean; sq += rl[i] ? d * d : 0.0f; }
-      float var = mb_hsum(sq) * invB;                         // biased: what normalises
+      float var = wave_sum<32>(sq) * invB;                         // biased: what normalises
       float rstd = rsqrtf(var + a.eps);
       if (a_eval_stats) {                                     // model.eval(): the running statistics, read only
         mean = clive ? a.running_mean[c] : 0.0f;
@@ -437,7 +398,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
       if (blockIdx.x == 0 && tid == 0 && a.num_batches_tracked && !a_eval_stats) a.num_batches_tracked[0] += 1;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        s_z[q + 32 * i][cl] = mb_f2bf(v[i]);                 // exact: v is a bf16 value; leaves with the results below
+        s_z[q + 32 * i][cl] = f32_to_bf16(v[i]);                 // exact: v is a bf16 value; leaves with the results below
         v[i] = rl[i] ? __builtin_fmaf((v[i] - mean) * rstd, g, be) : 0.0f;
       }
     }
@@ -448,7 +409,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
         float y = v[i] > 0.0f ? v[i] : v[i] * a.slope;
         if (drop) {
           const uint64_t e = (uint64_t)(q + 32 * i) * (uint64_t)N + (uint64_t)c;
-          y = mb_uniform(a.seed, call, e) >= a.p_drop ? y * keep_scale : 0.0f;
+          y = drop_uniform(a.seed, call, e) >= a.p_drop ? y * keep_scale : 0.0f;
         }
         v[i] = y;
       }
@@ -457,7 +418,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
       // the predictions leave through LDS first, then v becomes d loss / d predictions
       if (sP) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) s_y[q + 32 * i][cl] = mb_f2bf(v[i]);
+        for (int i = 0; i < 4; ++i) s_y[q + 32 * i][cl] = f32_to_bf16(v[i]);
         __syncthreads();
         if (tid < 2 * MB_ROWS) {
           const int r = tid >> 1, h = tid & 1;
@@ -493,13 +454,13 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
       }
       float sb = 0.0f;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) sb += mb_round(v[i]);
-      sb = mb_hsum(sb);
+      for (int i = 0; i < 4; ++i) sb += bf16_round(v[i]);
+      sb = wave_sum<32>(sb);
       if (clive && q == 0 && a.dbias) a.dbias[c] = sb;
     }
   } else {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = rl[i] ? mb_round(v[i]) : 0.0f;              // the input gradient's bf16 value
+    for (int i = 0; i < 4; ++i) v[i] = rl[i] ? bf16_round(v[i]) : 0.0f;              // the input gradient's bf16 value
     if (a_add_mode == OPS_MLP_ADD_BWD_BLOCK) {
       // + dZ (identity path) + conv1^T( bn1 backward (dZ) ) (stencil path); the whole-tensor means from the partial sums
       const double n = (double)B * (double)No;
@@ -519,9 +480,9 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
           const int r = q + 32 * i;
           float dy[3], po[5], pg[3];
 #pragma unroll
-          for (int d = 0; d < 5; ++d) po[d] = mb_bf2f(s_stage[cl + d][r]);
+          for (int d = 0; d < 5; ++d) po[d] = bf16_to_f32(s_stage[cl + d][r]);
 #pragma unroll
-          for (int d = 0; d < 3; ++d) pg[d] = mb_bf2f(s_stage[20 + cl + d][r]);
+          for (int d = 0; d < 3; ++d) pg[d] = bf16_to_f32(s_stage[20 + cl + d][r]);
 #pragma unroll
           for (int d = 0; d < 3; ++d) {
             const int qq = c + d - 1;
@@ -535,7 +496,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
             }
           }
           const float sdx = __builtin_fmaf(sc_w0, dy[2], __builtin_fmaf(sc_w1, dy[1], sc_w2 * dy[0]));
-          v[i] = mb_round(v[i] + pg[1] + sdx);
+          v[i] = bf16_round(v[i] + pg[1] + sdx);
         }
     }
     if (act_bwd) {
@@ -543,7 +504,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
 #pragma unroll
       for (int i = 0; i < 4; ++i)
         if (rl[i]) {
-          const float y = mb_bf2f(s_stage[54 + cl][q + 32 * i]);
+          const float y = bf16_to_f32(s_stage[54 + cl][q + 32 * i]);
           v[i] *= y == 0.0f ? 0.0f : (y > 0.0f ? keep_scale : a.slope * keep_scale);
         }
     }
@@ -551,11 +512,11 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
       float xh[4], sg = 0.0f, sgx = 0.0f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        xh[i] = rl[i] ? (mb_bf2f(s_stage[38 + cl][q + 32 * i]) - mean_c) * rstd_c : 0.0f;
+        xh[i] = rl[i] ? (bf16_to_f32(s_stage[38 + cl][q + 32 * i]) - mean_c) * rstd_c : 0.0f;
         sg += v[i];
         sgx = __builtin_fmaf(v[i], xh[i], sgx);
       }
-      sg = mb_hsum(sg); sgx = mb_hsum(sgx);
+      sg = wave_sum<32>(sg); sgx = wave_sum<32>(sgx);
       if (clive && q == 0) { a.dgamma[c] = sgx; a.dbeta[c] = sg; }
       const float k2 = g * rstd_c;
 #pragma unroll
@@ -564,8 +525,8 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
     if (a.dbias) {
       float sb = 0.0f;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) sb += mb_round(v[i]);
-      sb = mb_hsum(sb);
+      for (int i = 0; i < 4; ++i) sb += bf16_round(v[i]);
+      sb = wave_sum<32>(sb);
       if (clive && q == 0) a.dbias[c] = sb;
     }
   }
@@ -573,7 +534,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
   // ---- results through LDS, 16-byte chunks in the tiled layout: threads 0..255 the row-major copy (row, 8 columns), threads
   // 256..511 the transposed copy (column, 8 rows); the saved pre-normalisation values likewise (transposed only) ----
 #pragma unroll
-  for (int i = 0; i < 4; ++i) s_y[q + 32 * i][cl] = rl[i] ? mb_f2bf(v[i]) : (uint16_t)0;
+  for (int i = 0; i < 4; ++i) s_y[q + 32 * i][cl] = rl[i] ? f32_to_bf16(v[i]) : (uint16_t)0;
   __syncthreads();
   if (tid < 2 * MB_ROWS) {
     const int r = tid >> 1, h = tid & 1;
@@ -602,7 +563,7 @@ __global__ __launch_bounds__(MB_THREADS) void mlp_strip_kernel(const ops_mlp_str
     double accd[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) accd[k] = (double)lacc[k];
-    mb_block_sum<5>(accd, s_red);
+    block_sum<MB_THREADS / 64, false>(accd, s_red);
     if (tid == 0)
 #pragma unroll
       for (int k = 0; k < 5; ++k) ((double*)s_loss_ws)[blockIdx.x * 5 + k] = accd[k];
@@ -625,11 +586,6 @@ struct WgradNorm {
   const float* rptr[OPS_MLP_MAX_NORM_RANGES];
   int rlen[OPS_MLP_MAX_NORM_RANGES];
 };
-__device__ __forceinline__ float mb_wsum_f(float v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 template <bool NORM>
 __global__ __launch_bounds__(64) void mlp_wgrad_kernel(const WgradTable tb, const WgradNorm nm) {
@@ -651,7 +607,7 @@ __global__ __launch_bounds__(64) void mlp_wgrad_kernel(const WgradTable tb, cons
         const float x = g[i] * nm.scale, y = i + 64 < len ? g[i + 64] * nm.scale : 0.0f;
         a0 = __builtin_fmaf(x, x, a0); a1 = __builtin_fmaf(y, y, a1);
       }
-      const double d = mb_wsum_d((double)a0 + (double)a1);
+      const double d = wave_sum((double)a0 + (double)a1);
       if (threadIdx.x == 0) nm.part[blockIdx.x] = d;
       return;
     }
@@ -699,7 +655,7 @@ __global__ __launch_bounds__(64) void mlp_wgrad_kernel(const WgradTable tb, cons
       }
     }
   if constexpr (NORM) {                     // 16 values per lane in float, the 64 lanes and everything after in double
-    const double d = mb_wsum_d((double)sq);
+    const double d = wave_sum((double)sq);
     if (lane == 0) nm.part[blockIdx.x] = d;
   }
 }
@@ -719,7 +675,7 @@ __global__ __launch_bounds__(256) void mlp_repack_kernel(const RepackTable tb) {
     const ops_mlp_repack_entry m = tb.m[mi];
     const long le = e - tb.e0[mi];
     const int n = (int)(le / m.K), k = (int)(le - (long)n * m.K);
-    const uint16_t h = mb_f2bf(m.W[le]);
+    const uint16_t h = f32_to_bf16(m.W[le]);
     ((uint16_t*)m.Wp)[mb_toff(n, k, m.ldw >> 5)] = h;
     ((uint16_t*)m.Wtp)[mb_toff(k, n, m.ldwt >> 5)] = h;
   }
@@ -794,7 +750,7 @@ __global__ __launch_bounds__(256) void mlp_gather_noise_kernel(int B, int F, con
         const float u2 = (float)((hh >> 16) & 0xFFFFFFull) * (1.0f / 16777216.0f);   // [0, 1)
         v += sg * sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530717958647692f * u2);
       }
-      h = mb_f2bf(v);
+      h = f32_to_bf16(v);
     }
     s_tile[fl][bl] = h;
   }

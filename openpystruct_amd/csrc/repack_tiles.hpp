@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/openpystruct_amd.h"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
@@ -50,11 +51,7 @@ __device__ __forceinline__ void repack_tile_job(const float* __restrict__ p, con
     const int r = tr ? b : a, c = tr ? a : b;
     v[j] = (r < N && c < K) ? W[(long)r * K + c] : 0.0f;
   }
-  auto to_bf16 = [](float f) -> uint32_t {
-    uint32_t u = __float_as_uint(f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-  };
+  auto to_bf16 = [](float f) -> uint32_t { return bf16_rne_bits(__float_as_uint(f)) >> 16; };
   uint4 o;
   o.x = to_bf16(v[0]) | (to_bf16(v[1]) << 16); o.y = to_bf16(v[2]) | (to_bf16(v[3]) << 16);
   o.z = to_bf16(v[4]) | (to_bf16(v[5]) << 16); o.w = to_bf16(v[6]) | (to_bf16(v[7]) << 16);

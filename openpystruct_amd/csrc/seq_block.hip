@@ -20,22 +20,10 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "dropout_stream.hpp"
+#include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
-
-__device__ __forceinline__ float sq_bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t sq_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float sq_uniform(uint64_t seed, uint64_t call, uint64_t idx) { return drop_uniform(seed, call, idx); }   // csrc/dropout_stream.hpp
-__device__ __forceinline__ float sq_wsum(float v) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 // ================================================================================================================================
 // attention over short sequences: a workgroup stages the q|k|v rows of NB samples in LDS (coalesced 16-byte loads), one thread per
@@ -127,7 +115,7 @@ __device__ __forceinline__ void sa_row(const float (&q)[DHP], const uint16_t* __
 #pragma unroll
   for (int j = 0; j < SA_MAXS; ++j) {
     p[j] *= inv;
-    const bool keep = !(p_drop > 0.0f) || sq_uniform(seed, call, eidx0 + j) >= p_drop;
+    const bool keep = !(p_drop > 0.0f) || drop_uniform(seed, call, eidx0 + j) >= p_drop;
     pk[j] = (j < S && keep) ? p[j] * ks : 0.0f;
   }
 }
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attention_fwd_kernel(const SaA
     uint16_t* out = a.ctx + ((long)(b0 + bl) * S + i) * d + h * dh;
 #pragma unroll
     for (int t = 0; t < DHP; ++t)
-      if (t < dh) out[t] = sq_f2bf(o[t]);
+      if (t < dh) out[t] = f32_to_bf16(o[t]);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && a.used_call) *a.used_call = call;
 }
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attention_bwd_kernel(const SaA
     uint16_t* dqo = a.dqkv + ((long)(b0 + bl) * S + i) * 3 * d + h * dh;
 #pragma unroll
     for (int t = 0; t < DHP; ++t)
-      if (t < dh) dqo[t] = sq_f2bf(dq[t]);
+      if (t < dh) dqo[t] = f32_to_bf16(dq[t]);
   }
   __syncthreads();
   if (bl < nb) {
@@ -248,7 +236,7 @@ __global__ __launch_bounds__(SA_THREADS) void seq_attention_bwd_kernel(const SaA
     uint16_t* dvo = dko + d;
 #pragma unroll
     for (int t = 0; t < DHP; ++t)
-      if (t < dh) { dko[t] = sq_f2bf(dk[t]); dvo[t] = sq_f2bf(dv[t]); }
+      if (t < dh) { dko[t] = f32_to_bf16(dk[t]); dvo[t] = f32_to_bf16(dv[t]); }
   }
 }
 
@@ -294,18 +282,18 @@ __global__ __launch_bounds__(LN_THREADS) void dropout_add_ln_fwd_kernel(const Ln
       z[k] = 0.0f;
       if (c < d) {
         const long e = (long)r * d + c;
-        float xv = sq_bf2f(a.x[e]);
-        if (a.p_drop > 0.0f) xv = sq_uniform(a.seed, call, (uint64_t)e) >= a.p_drop ? xv * ks : 0.0f;
-        const float rv = a.res_bf16 ? sq_bf2f(((const uint16_t*)a.res)[e]) : ((const float*)a.res)[e];
+        float xv = bf16_to_f32(a.x[e]);
+        if (a.p_drop > 0.0f) xv = drop_uniform(a.seed, call, (uint64_t)e) >= a.p_drop ? xv * ks : 0.0f;
+        const float rv = a.res_bf16 ? bf16_to_f32(((const uint16_t*)a.res)[e]) : ((const float*)a.res)[e];
         z[k] = rv + xv;
         sum += z[k];
       }
     }
-    const float mean = sq_wsum(sum) / (float)d;
+    const float mean = wave_sum(sum) / (float)d;
     float sq = 0.0f;
 #pragma unroll
     for (int k = 0; k < LN_MAXC; ++k) { const float dv = z[k] - mean; sq += (lane + 64 * k < d) ? dv * dv : 0.0f; }
-    const float rstd = rsqrtf(sq_wsum(sq) / (float)d + a.eps);
+    const float rstd = rsqrtf(wave_sum(sq) / (float)d + a.eps);
     if (lane == 0) { a.mean[r] = mean; a.rstd[r] = rstd; }
 #pragma unroll
     for (int k = 0; k < LN_MAXC; ++k) {
@@ -315,7 +303,7 @@ __global__ __launch_bounds__(LN_THREADS) void dropout_add_ln_fwd_kernel(const Ln
         const float y = __builtin_fmaf((z[k] - mean) * rstd, g[k], be[k]);
         a.z[e] = z[k];
         a.y32[e] = y;
-        a.y16[e] = sq_f2bf(y);
+        a.y16[e] = f32_to_bf16(y);
       }
     }
   }
@@ -345,7 +333,7 @@ __global__ __launch_bounds__(LN_BWD_THREADS) void dropout_add_ln_bwd_kernel(cons
         if (c < d) {
           const long e = (long)r * d + c;
           gv[k] = a.dy32 ? a.dy32[e] : 0.0f;
-          if (a.dy16) gv[k] += sq_bf2f(a.dy16[e]);
+          if (a.dy16) gv[k] += bf16_to_f32(a.dy16[e]);
           zv[k] = a.z[e];
         }
       }
@@ -369,7 +357,7 @@ __global__ __launch_bounds__(LN_BWD_THREADS) void dropout_add_ln_bwd_kernel(cons
       s1 += gy[k];
       s2 = __builtin_fmaf(gy[k], xh[k], s2);
     }
-    s1 = sq_wsum(s1) / (float)d; s2 = sq_wsum(s2) / (float)d;
+    s1 = wave_sum(s1) / (float)d; s2 = wave_sum(s2) / (float)d;
 #pragma unroll
     for (int k = 0; k < LN_MAXC; ++k) {
       const int c = lane + 64 * k;
@@ -377,8 +365,8 @@ __global__ __launch_bounds__(LN_BWD_THREADS) void dropout_add_ln_bwd_kernel(cons
         const long e = (long)r * d + c;
         const float dz = rstd * (gy[k] - s1 - xh[k] * s2);
         a.dres[e] = dz;
-        const bool keep = !(a.p_drop > 0.0f) || sq_uniform(a.seed, call, (uint64_t)e) >= a.p_drop;
-        a.dx[e] = sq_f2bf(keep ? dz * ks : 0.0f);
+        const bool keep = !(a.p_drop > 0.0f) || drop_uniform(a.seed, call, (uint64_t)e) >= a.p_drop;
+        a.dx[e] = f32_to_bf16(keep ? dz * ks : 0.0f);
       }
     }
 #pragma unroll
@@ -410,10 +398,10 @@ __global__ __launch_bounds__(256) void act_dropout_fwd_kernel(long n, const uint
   const unsigned long long call = p_drop > 0.0f ? *counter : 0ull;
   const float ks = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-    float v = sq_bf2f(x[e]);
+    float v = bf16_to_f32(x[e]);
     v = v > 0.0f ? v : v * slope;
-    if (p_drop > 0.0f) v = sq_uniform(seed, call, (uint64_t)e) >= p_drop ? v * ks : 0.0f;
-    y[e] = sq_f2bf(v);
+    if (p_drop > 0.0f) v = drop_uniform(seed, call, (uint64_t)e) >= p_drop ? v * ks : 0.0f;
+    y[e] = f32_to_bf16(v);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && used_call) *used_call = call;
 }
@@ -423,15 +411,12 @@ __global__ __launch_bounds__(256) void act_dropout_bwd_kernel(long n, const uint
   const unsigned long long call = p_drop > 0.0f ? *used_call : 0ull;
   const float ks = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-    float g = sq_bf2f(dy[e]);
-    if (p_drop > 0.0f) g = sq_uniform(seed, call, (uint64_t)e) >= p_drop ? g * ks : 0.0f;
-    g = sq_bf2f(x[e]) > 0.0f ? g : g * slope;
-    dx[e] = sq_f2bf(g);
+    float g = bf16_to_f32(dy[e]);
+    if (p_drop > 0.0f) g = drop_uniform(seed, call, (uint64_t)e) >= p_drop ? g * ks : 0.0f;
+    g = bf16_to_f32(x[e]) > 0.0f ? g : g * slope;
+    dx[e] = f32_to_bf16(g);
   }
 }
-
-void set_last_error(const char* msg);
-int deterministic_mode();              // frame_solve.hip: library option "deterministic" (ops_amd_set_option)
 
 }  // namespace opsamd
 
@@ -649,7 +634,7 @@ __device__ __forceinline__ void wgrad_tn_body(int T, int N, int K, const uint16_
       if (bias_job) {
         const uint16_t* pv = (const uint16_t*)&ra[i];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) csum[j] += sq_bf2f(pv[j]);
+        for (int j = 0; j < 8; ++j) csum[j] += bf16_to_f32(pv[j]);
       }
     }
   };
@@ -887,7 +872,7 @@ __global__ __launch_bounds__(256) void diffusion_noise_kernel(long rows, int d, 
     const float a = acp[t[r]], s_a = sqrtf(a), s_b = sqrtf(1.0f - a);
     const float v = s_a * x[e] + s_b * eps[e];
     xn32[e] = v;
-    xn16[e] = sq_f2bf(v);
+    xn16[e] = f32_to_bf16(v);
     if (e - r * d == 0) { sa[r] = s_a; sb[r] = s_b; }
   }
 }
@@ -912,7 +897,7 @@ __global__ __launch_bounds__(256) void diffusion_noise_draw_kernel(long rows, in
     const float ep = sqrtf(-2.0f * __logf(u1)) * __cosf(6.28318530717958647692f * u2);
     const float v = s_a * x[e] + s_b * ep;
     xn32[e] = v;
-    xn16[e] = sq_f2bf(v);
+    xn16[e] = f32_to_bf16(v);
     if (eps_out) eps_out[e] = ep;
     if (e - r * d == 0) { sa[r] = s_a; sb[r] = s_b; if (t_out) t_out[r] = t; }
   }
@@ -934,11 +919,11 @@ __global__ __launch_bounds__(256) void diffusion_combine_fwd_kernel(int B, int N
       v = cls[c];
     } else {
       const long r = b * Nc + (s - 1), q = r * d + c;
-      v = (xn32[q] - sb[r] * sq_bf2f(m[q])) / sa[r];
+      v = (xn32[q] - sb[r] * bf16_to_f32(m[q])) / sa[r];
     }
     v += pe[(long)s * d + c];
     z[e] = v;
-    if (z16) z16[e] = sq_f2bf(v);                           // the first in-projection's operand: no cast node
+    if (z16) z16[e] = f32_to_bf16(v);                           // the first in-projection's operand: no cast node
   }
 }
 
@@ -955,7 +940,7 @@ __global__ __launch_bounds__(256) void diffusion_combine_bwd_kernel(int B, int N
     const long r = q / d, b = r / Nc;
     const int s = (int)(r - b * Nc) + 1;
     const long gi = (b * S + s) * d + c;
-    dm[q] = sq_f2bf(-(sb[r] / sa[r]) * ((g ? g[gi] : 0.0f) + (g16 ? sq_bf2f(g16[gi]) : 0.0f)));
+    dm[q] = f32_to_bf16(-(sb[r] / sa[r]) * ((g ? g[gi] : 0.0f) + (g16 ? bf16_to_f32(g16[gi]) : 0.0f)));
   }
   if (dcls && (int)blockIdx.x < 64) {                      // 64 workgroups share the [CLS] rows, eight independent loads per trip
     for (int c = threadIdx.x; c < d; c += 256) {
@@ -965,7 +950,7 @@ __global__ __launch_bounds__(256) void diffusion_combine_bwd_kernel(int B, int N
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const long b = b0 + 64 * k, gi = (b * S) * d + c;
-          v[k] = b < B ? (g ? g[gi] : 0.0f) + (g16 ? sq_bf2f(g16[gi]) : 0.0f) : 0.0f;
+          v[k] = b < B ? (g ? g[gi] : 0.0f) + (g16 ? bf16_to_f32(g16[gi]) : 0.0f) : 0.0f;
         }
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc += v[k];

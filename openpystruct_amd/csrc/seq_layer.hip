@@ -28,11 +28,11 @@
 #include "dropout_stream.hpp"
 #include "call_counter.hpp"
 #include "input_noise.hpp"
+#include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
-void set_last_error(const char* msg);   // beam_solve.hip
-int deterministic_mode();                // frame_solve.hip: library option "deterministic"
 // deterministic mode: the workgroups of the head's backward launch add their LayerNorm gamma / beta column sums IN WORKGROUP ORDER (a ticket:
 // workgroup i waits for i - 1, which the dispatcher started before it); the last one re-arms the ticket for the next launch
 __device__ unsigned int g_head_ticket = 0u;
@@ -41,36 +41,23 @@ typedef __bf16 sl_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float sl_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned sl_u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float sl_bf2f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
-__device__ __forceinline__ uint16_t sl_f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ float sl_round(float f) { return sl_bf2f(sl_f2bf(f)); }
-__device__ __forceinline__ float sl_uniform(uint64_t seed, uint64_t call, uint64_t idx) { return drop_uniform(seed, call, idx); }   // csrc/dropout_stream.hpp
-// lane exchange inside a 16-lane row by DPP (a `__shfl_xor` is a ds_bpermute: an LDS-pipe round trip of ~100 cycles per step; the
-// first version's two LayerNorms spent 2.6 us each in their 32 dependent ones)
-template <int CTRL>
-__device__ __forceinline__ float sl_dpp(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
+// lane exchange inside a 16-lane row by DPP (dpp_mov; a `__shfl_xor` is a ds_bpermute: an LDS-pipe round trip of ~100 cycles per step;
+// the first version's two LayerNorms spent 2.6 us each in their 32 dependent ones)
 __device__ __forceinline__ unsigned sl_dpp_or_quad(unsigned v) {
   v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
   v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
   return v;
 }
 __device__ __forceinline__ float sl_quadsum(float v) {       // all four lanes of a quad get the quad's sum
-  v += sl_dpp<0xB1>(v);                                        // quad_perm [1, 0, 3, 2]
-  v += sl_dpp<0x4E>(v);                                        // quad_perm [2, 3, 0, 1]
+  v += dpp_mov<0xB1>(v);                                        // quad_perm [1, 0, 3, 2]
+  v += dpp_mov<0x4E>(v);                                        // quad_perm [2, 3, 0, 1]
   return v;
 }
 // sum over the 16 lanes that hold one row group of an MFMA accumulator (lanes 16 g .. 16 g + 15): every lane gets the total
 __device__ __forceinline__ float sl_rowsum(float v) {
   v = sl_quadsum(v);
-  v += sl_dpp<0x124>(v);                                       // row_ror:4
-  v += sl_dpp<0x128>(v);                                       // row_ror:8
+  v += dpp_mov<0x124>(v);                                       // row_ror:4
+  v += dpp_mov<0x128>(v);                                       // row_ror:8
   return v;
 }
 
@@ -84,16 +71,9 @@ __device__ __forceinline__ void sl_lds_barrier() {
   __asm__ volatile("" ::: "memory");
 }
 
-// The launch's argument block read AT THE POINT OF USE.  The 45-field struct held in scalar registers for the whole kernel is ~90 of the
-// 102 SGPRs: the first builds spilled scalars into VGPR lanes -- 1 600 v_writelane / v_readlane of the kernel's 7 900 instructions.
-// The kernarg segment is constant memory (scalar loads); the empty asm makes the pointer opaque so that the field loads stay behind it.
-typedef const __attribute__((opencl_constant)) ops_tfd_layer_args* sl_args_ptr;
-template <int ARGOFF = 0>                  // byte offset of the argument block in the kernarg segment (the pair kernel carries two)
-__device__ __forceinline__ sl_args_ptr sl_late_args() {
-  auto p = __builtin_amdgcn_kernarg_segment_ptr();
-  __asm__ volatile("" : "+s"(p));
-  return (sl_args_ptr)((const __attribute__((opencl_constant)) char*)p + ARGOFF);
-}
+// The launch's argument block is read AT THE POINT OF USE (late_args, lane_common.hpp).  The 45-field struct held in scalar registers for
+// the whole kernel is ~90 of the 102 SGPRs: the first builds spilled scalars into VGPR lanes -- 1 600 v_writelane / v_readlane of the
+// kernel's 7 900 instructions.  ARGOFF: the pair kernel carries two argument blocks.
 
 // Four floats that THIS launch has written (the pair kernels: a workgroup re-reads the rows it stored a moment ago): device-scope loads,
 // which do not look into the CU's vector L1.  A plain load is not enough although only the workgroup's own bytes are consumed: rows are
@@ -247,7 +227,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
   // bias read issued in a product's epilogue would wait for every weight fragment requested ahead of it.
   float bq[3], b1v[2];
 #pragma unroll
-  for (int j = 0; j < 3; ++j) { const int m = 16 * (wave + SL_NW * j) + c; bq[j] = sl_bf2f(((const uint16_t*)a.b_in)[m < 3 * d ? m : 3 * d - 1]); }
+  for (int j = 0; j < 3; ++j) { const int m = 16 * (wave + SL_NW * j) + c; bq[j] = bf16_to_f32(((const uint16_t*)a.b_in)[m < 3 * d ? m : 3 * d - 1]); }
   WTile<4> wq[3], wo, w1[2];
   WTile<8> w2;
   // (no branches around the loads: tiles beyond a product's last are clamped to it, so that the compiler can COUNT the outstanding
@@ -260,8 +240,8 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
   {
     const int r = tid >> 5, q4 = tid & 31;
     uint2 o;
-    o.x = (uint32_t)sl_f2bf(xin.x) | ((uint32_t)sl_f2bf(xin.y) << 16);
-    o.y = (uint32_t)sl_f2bf(xin.z) | ((uint32_t)sl_f2bf(xin.w) << 16);
+    o.x = (uint32_t)f32_to_bf16(xin.x) | ((uint32_t)f32_to_bf16(xin.y) << 16);
+    o.y = (uint32_t)f32_to_bf16(xin.z) | ((uint32_t)f32_to_bf16(xin.w) << 16);
     *(uint2*)(s_x + r * XS + 4 * q4) = o;
   }
   SL_STAMP(8);
@@ -275,9 +255,9 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
 #pragma unroll
   for (int i = 0; i < 4; ++i) { const int r = 4 * g + i; xres[i] = a.x32[(row0 + (r < nrows ? r : 0)) * d + (colok ? n : 0)]; }
 #pragma unroll
-  for (int j = 0; j < 2; ++j) { const int m = 16 * (wave + SL_NW * j) + c; b1v[j] = sl_bf2f(((const uint16_t*)a.b_1)[m < ff ? m : ff - 1]); }
+  for (int j = 0; j < 2; ++j) { const int m = 16 * (wave + SL_NW * j) + c; b1v[j] = bf16_to_f32(((const uint16_t*)a.b_1)[m < ff ? m : ff - 1]); }
   const int nc = colok ? n : d - 1;
-  const float bo = sl_bf2f(((const uint16_t*)a.b_out)[nc]), b2v = sl_bf2f(((const uint16_t*)a.b_2)[nc]);
+  const float bo = bf16_to_f32(((const uint16_t*)a.b_out)[nc]), b2v = bf16_to_f32(((const uint16_t*)a.b_2)[nc]);
   const float gm1 = a.gamma1[nc], be1 = a.beta1[nc], gm2 = a.gamma2[nc], be2 = a.beta2[nc];
   sl_load_tile<4>(wo, (const uint16_t*)a.W_out, KSD, wave < NTD ? wave : NTD - 1, lane);
 #pragma unroll
@@ -302,7 +282,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int r = 4 * g + i;
-            const uint16_t v = sl_f2bf(acc[i] + b);
+            const uint16_t v = f32_to_bf16(acc[i] + b);
             s_big[((r * 3 + which) * H + hh) * SL_DHP + tt] = v;
             s_st[r * QS + m] = v;
           }
@@ -315,7 +295,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
 
   // ---- attention: four lanes per (sample, head, query), four head dimensions each ----
   {
-    const sl_args_ptr la = sl_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
     const DropKey key_attn = drop_key(la->seed_attn, call);   // scalar-unit work (csrc/dropout_stream.hpp)
     const float p_attn = la->p_attn;
     const float scale = rsqrtf((float)dh), ks = la->p_attn > 0.0f ? 1.0f / (1.0f - la->p_attn) : 1.0f;
@@ -371,7 +351,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
       const int r = bl * S + i;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        if (4 * qd + t < dh) s_ctx[r * XS + hh * dh + 4 * qd + t] = sl_f2bf(o[t]);
+        if (4 * qd + t < dh) s_ctx[r * XS + hh * dh + 4 * qd + t] = f32_to_bf16(o[t]);
     }
     // columns d .. 127 of the attention rows and the rows beyond the samples: zero (they multiply clamped weight reads)
     sl_zero_cols(s_ctx, XS, d, 128, tid);
@@ -383,7 +363,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
   // order and the store loops below have trip counts the compiler cannot count through).
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   SL_STAMP(3);
-  { const sl_args_ptr la = sl_late_args<ARGOFF>();
+  { const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
   sl_store_rows<2>(la->qkv, s_st, QS, 3 * d, row0, nrows, tid);
   sl_store_rows<2>(la->ctx, s_ctx, XS, d, row0, nrows, tid); }
   SL_STAMP(9);
@@ -393,7 +373,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
   {
     float z[4];
     const sl_f32x4 acc = sl_mma_tile<4>(wo, s_ctx, XS, c, g);
-    const sl_args_ptr la = sl_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
     const DropKey key_1 = drop_key(la->seed_1, call);
     const float p_1 = la->p_1;
     const float ks = la->p_1 > 0.0f ? 1.0f / (1.0f - la->p_1) : 1.0f;
@@ -402,7 +382,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
       const int r = 4 * g + i;
       float zz = 0.0f;
       if (colok && r < nrows) {
-        float xv = sl_round(acc[i] + bo);
+        float xv = bf16_round(acc[i] + bo);
         if (p_1 > 0.0f) xv = drop_uniform(key_1, (uint64_t)(row0 * d) + (uint32_t)(r * d + n)) >= p_1 ? xv * ks : 0.0f;
         zz = xres[i] + xv;
       }
@@ -420,18 +400,18 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
       const int r = 4 * g + i;
       y1[i] = __builtin_fmaf((z[i] - mean[i]) * rstd[i], gm1, be1);
       if (wave == 0 && c == 0 && r < nrows) { ((__attribute__((address_space(1))) float*)la->mean1)[row0 + r] = mean[i]; ((__attribute__((address_space(1))) float*)la->rstd1)[row0 + r] = rstd[i]; }
-      s_x[r * XS + n] = (colok && r < nrows) ? sl_f2bf(y1[i]) : (uint16_t)0;     // (x as an operand is dead since the in-projection)
+      s_x[r * XS + n] = (colok && r < nrows) ? f32_to_bf16(y1[i]) : (uint16_t)0;     // (x as an operand is dead since the in-projection)
     }
   }
   sl_lds_barrier();
   SL_STAMP(4);
-  { const sl_args_ptr la = sl_late_args<ARGOFF>();
+  { const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
   sl_store_rows<4>(la->z1, s_f32, FS, d, row0, nrows, tid);
   sl_store_rows<2>(la->y1_16, s_x, XS, d, row0, nrows, tid); }
 
   // ---- feed-forward 1: u = y1 W_1^T + b_1 (saved), h = dropout(ReLU(u)) -> LDS operand rows ----
   {
-    const sl_args_ptr la = sl_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
     const DropKey key_act = drop_key(la->seed_act, call);
     const float p_act = la->p_act;
     const float ks = la->p_act > 0.0f ? 1.0f / (1.0f - la->p_act) : 1.0f;
@@ -446,11 +426,11 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int r = 4 * g + i;
-            const uint16_t ub = sl_f2bf(acc[i] + b);
-            float hv = sl_bf2f(ub);
+            const uint16_t ub = f32_to_bf16(acc[i] + b);
+            float hv = bf16_to_f32(ub);
             hv = (hv > 0.0f || la->identity_act) ? hv : 0.0f;
             if (p_act > 0.0f && r < nrows) hv = drop_uniform(key_act, (uint64_t)(row0 * ff) + (uint32_t)(r * ff + m)) >= p_act ? hv * ks : 0.0f;
-            s_big[r * HS + m] = r < nrows ? sl_f2bf(hv) : (uint16_t)0;
+            s_big[r * HS + m] = r < nrows ? f32_to_bf16(hv) : (uint16_t)0;
             s_st[r * QS + m] = ub;                     // (the q|k|v rows went out two barriers ago)
           }
         }
@@ -459,7 +439,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
   }
   sl_lds_barrier();
   SL_STAMP(5);
-  { const sl_args_ptr la = sl_late_args<ARGOFF>();
+  { const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
   sl_store_rows<2>(la->u, s_st, QS, ff, row0, nrows, tid);
   sl_store_rows<2>(la->h, s_big, HS, ff, row0, nrows, tid); }
   SL_STAMP(12);
@@ -468,7 +448,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
   {
     float z[4];
     const sl_f32x4 acc = sl_mma_tile<8>(w2, s_big, HS, c, g);
-    const sl_args_ptr la = sl_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_args, ARGOFF>();
     const DropKey key_2 = drop_key(la->seed_2, call);
     const float p_2 = la->p_2;
     const float ks = la->p_2 > 0.0f ? 1.0f / (1.0f - la->p_2) : 1.0f;
@@ -479,7 +459,7 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
       const int r = 4 * g + i;
       float zz = 0.0f;
       if (colok && r < nrows) {
-        float xv = sl_round(acc[i] + b2v);
+        float xv = bf16_round(acc[i] + b2v);
         if (p_2 > 0.0f) xv = drop_uniform(key_2, (uint64_t)(row0 * d) + (uint32_t)(r * d + n)) >= p_2 ? xv * ks : 0.0f;
         zz = y1[i] + xv;
       }
@@ -498,14 +478,14 @@ __device__ __forceinline__ void tfd_layer_fwd_body(const ops_tfd_layer_args& a) 
       if (wave == 0 && c == 0 && r < nrows) { ((__attribute__((address_space(1))) float*)la->mean2)[row0 + r] = mean[i]; ((__attribute__((address_space(1))) float*)la->rstd2)[row0 + r] = rstd[i]; }
       const float y2 = __builtin_fmaf((z[i] - mean[i]) * rstd[i], gm2, be2);
       s_y2[r * FS + n] = y2;
-      s_x[r * XS + n] = sl_f2bf(y2);                   // (y1 as an operand is dead since feed-forward 1, its store is two barriers old)
+      s_x[r * XS + n] = f32_to_bf16(y2);                   // (y1 as an operand is dead since feed-forward 1, its store is two barriers old)
     }
     sl_lds_barrier();
     SL_STAMP(15);
     sl_store_rows<4>(la->y32, s_y2, FS, d, row0, nrows, tid);
     sl_store_rows<2>(la->y16, s_x, XS, d, row0, nrows, tid);
   }
-  { const sl_args_ptr la = sl_late_args<ARGOFF>(); if (blockIdx.x == 0 && tid == 0 && la->used_call) *(__attribute__((address_space(1))) unsigned long long*)la->used_call = call; }
+  { const auto la = late_args<ops_tfd_layer_args, ARGOFF>(); if (blockIdx.x == 0 && tid == 0 && la->used_call) *(__attribute__((address_space(1))) unsigned long long*)la->used_call = call; }
   if (a.trace && tid == 0) {
     SL_STAMP(6);
     for (int k = 0; k < 16; ++k) a.trace[16 * (unsigned long long)blockIdx.x + k] = stamp[k];
@@ -525,20 +505,12 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_layer_pair_fwd_kernel(const op
   tfd_layer_fwd_body<(int)sizeof(ops_tfd_layer_args), true>(b);
 }
 
-
 // ================================================================================================================================
 // The layer's backward pass as one launch: the same decomposition (16 rows per workgroup, 8 waves split the column tiles, all weight
 // fragments -- here the TRANSPOSES' tiles -- requested at entry).  Arithmetic contract = the eight launches it replaces
 // (dropout_add_ln_bwd, act_dropout_bwd, seq_attention_bwd of csrc/seq_block.hip and four bf16 library products): bf16 operands, fp32
 // accumulation, every product rounded to bf16 before use, the residual stream's gradient in fp32.
 // ================================================================================================================================
-typedef const __attribute__((opencl_constant)) ops_tfd_layer_bwd_args* slb_args_ptr;
-template <int ARGOFF = 0>
-__device__ __forceinline__ slb_args_ptr slb_late_args() {
-  auto p = __builtin_amdgcn_kernarg_segment_ptr();
-  __asm__ volatile("" : "+s"(p));
-  return (slb_args_ptr)((const __attribute__((opencl_constant)) char*)p + ARGOFF);
-}
 #define SL_GLOBAL(T, p) ((__attribute__((address_space(1))) T*)(p))
 
 // LayerNorm backward for the accumulator layout (lane (c, g) of wave w: rows 4 g + i, column n = 16 w + c).  dy, xhat in registers;
@@ -703,7 +675,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
   // ---- LayerNorm2 backward -> dres2 (registers), d_f (bf16 operand rows) ----
   float dres2[4], pg2, pb2;
   {
-    const slb_args_ptr la = slb_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>();
     const DropKey key_2 = drop_key(la->seed_2, call);
     const float p_2 = la->p_2, ks = p_2 > 0.0f ? 1.0f / (1.0f - p_2) : 1.0f;
     float dy[4], xh[4], rstd[4];
@@ -724,7 +696,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
       if (!live) dres2[i] = 0.0f;
       float v = dres2[i];
       if (p_2 > 0.0f) v = drop_uniform(key_2, (uint64_t)(row0 * d) + (uint32_t)(r * d + n)) >= p_2 ? v * ks : 0.0f;
-      s_a[r * XS + n] = live ? sl_f2bf(v) : (uint16_t)0;
+      s_a[r * XS + n] = live ? f32_to_bf16(v) : (uint16_t)0;
     }
   }
   sl_lds_barrier();
@@ -732,7 +704,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
 
   // ---- d_h = d_f W_2 (bf16), ReLU + dropout backward -> d_u ----
   {
-    const slb_args_ptr la = slb_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>();
     const DropKey key_act = drop_key(la->seed_act, call);
     const float p_act = la->p_act, ks = p_act > 0.0f ? 1.0f / (1.0f - p_act) : 1.0f;
 #pragma unroll
@@ -745,10 +717,10 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const int r = 4 * g + i;
-            float gv = sl_round(acc[i]);
+            float gv = bf16_round(acc[i]);
             if (p_act > 0.0f) gv = drop_uniform(key_act, (uint64_t)(row0 * ff) + (uint32_t)(r * ff + m)) >= p_act ? gv * ks : 0.0f;
-            gv = (sl_bf2f(s_u[r * HS + m]) > 0.0f || la->identity_act) ? gv : 0.0f;
-            s_du[r * HS + m] = r < nrows ? sl_f2bf(gv) : (uint16_t)0;
+            gv = (bf16_to_f32(s_u[r * HS + m]) > 0.0f || la->identity_act) ? gv : 0.0f;
+            s_du[r * HS + m] = r < nrows ? f32_to_bf16(gv) : (uint16_t)0;
           }
         }
       }
@@ -758,7 +730,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
   // every weight fragment has arrived by now (see the forward kernel): one full wait BEFORE the first store is issued
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
   SLB_STAMP(4);
-  { const slb_args_ptr la = slb_late_args<ARGOFF>();
+  { const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>();
     if (g == 0) {
       if (la->ln_part) { SL_GLOBAL(float, la->ln_part)[((long)blockIdx.x * 4 + 0) * 128 + n] = colok ? pg2 : 0.0f; SL_GLOBAL(float, la->ln_part)[((long)blockIdx.x * 4 + 1) * 128 + n] = colok ? pb2 : 0.0f; }
       else if (colok) { unsafeAtomicAdd(la->dgamma2 + n, pg2); unsafeAtomicAdd(la->dbeta2 + n, pb2); }
@@ -769,7 +741,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
   // ---- d_y1 = d_u W_1 (bf16) + dres2, LayerNorm1 backward -> dres1 (registers), d_a ----
   float dres1[4];
   {
-    const slb_args_ptr la = slb_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>();
     const DropKey key_1 = drop_key(la->seed_1, call);
     const float p_1 = la->p_1, ks = p_1 > 0.0f ? 1.0f / (1.0f - p_1) : 1.0f;
     const sl_f32x4 acc = sl_mma_tile<8>(wt1, s_du, HS, c, g);
@@ -778,7 +750,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
     for (int i = 0; i < 4; ++i) {
       const int r = 4 * g + i;
       const bool live = colok && r < nrows;
-      dy[i] = live ? dres2[i] + sl_round(acc[i]) : 0.0f;
+      dy[i] = live ? dres2[i] + bf16_round(acc[i]) : 0.0f;
       rstd[i] = s_stat[3][r];
       xh[i] = live ? (s_z1[r * FS + n] - s_stat[2][r]) * rstd[i] : 0.0f;
     }
@@ -796,12 +768,12 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
       if (!live) dres1[i] = 0.0f;
       float v = dres1[i];
       if (p_1 > 0.0f) v = drop_uniform(key_1, (uint64_t)(row0 * d) + (uint32_t)(r * d + n)) >= p_1 ? v * ks : 0.0f;
-      s_a[r * XS + n] = live ? sl_f2bf(v) : (uint16_t)0;
+      s_a[r * XS + n] = live ? f32_to_bf16(v) : (uint16_t)0;
     }
   }
   sl_lds_barrier();
   SLB_STAMP(5);
-  { const slb_args_ptr la = slb_late_args<ARGOFF>(); sl_store_rows<2>(la->d_a, s_a, XS, d, row0, nrows, tid); }
+  { const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>(); sl_store_rows<2>(la->d_a, s_a, XS, d, row0, nrows, tid); }
 
   // ---- d_ctx = d_a W_out (bf16) -> padded head vectors ----
   {
@@ -810,7 +782,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
       const float inv_dh = 1.0f / (float)dh;
       const int hh = (int)(((float)n + 0.5f) * inv_dh), tt = n - hh * dh;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { const int r = 4 * g + i; if (r < nrows) s_do[(r * H + hh) * SL_DHP + tt] = sl_f2bf(acc[i]); }
+      for (int i = 0; i < 4; ++i) { const int r = 4 * g + i; if (r < nrows) s_do[(r * H + hh) * SL_DHP + tt] = f32_to_bf16(acc[i]); }
     }
   }
   sl_lds_barrier();
@@ -818,7 +790,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
 
   // ---- attention backward: four lanes per (sample, head, token), four head dimensions each ----
   {
-    const slb_args_ptr la = slb_late_args<ARGOFF>();
+    const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>();
     const DropKey key_attn = drop_key(la->seed_attn, call);
     const float p_attn = la->p_attn, ks = p_attn > 0.0f ? 1.0f / (1.0f - p_attn) : 1.0f;
     const float scale = rsqrtf((float)dh);
@@ -889,7 +861,7 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
       const int r = bl * S + i;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        if (4 * qd + t < dh) s_dq[r * QS + hh * dh + 4 * qd + t] = sl_f2bf(dq[t]);
+        if (4 * qd + t < dh) s_dq[r * QS + hh * dh + 4 * qd + t] = f32_to_bf16(dq[t]);
     }
     sl_lds_barrier();
     // token as KEY / VALUE j: dk_j = sum_i dS_ij q_i, dv_j = sum_i P~_ij dO_i
@@ -909,21 +881,21 @@ __device__ __forceinline__ void tfd_layer_bwd_body(const ops_tfd_layer_bwd_args&
       const int r = bl * S + j;
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        if (4 * qd + t < dh) { s_dq[r * QS + d + hh * dh + 4 * qd + t] = sl_f2bf(dk[t]); s_dq[r * QS + 2 * d + hh * dh + 4 * qd + t] = sl_f2bf(dv[t]); }
+        if (4 * qd + t < dh) { s_dq[r * QS + d + hh * dh + 4 * qd + t] = f32_to_bf16(dk[t]); s_dq[r * QS + 2 * d + hh * dh + 4 * qd + t] = f32_to_bf16(dv[t]); }
     }
   }
   sl_lds_barrier();
   SLB_STAMP(7);
-  { const slb_args_ptr la = slb_late_args<ARGOFF>(); sl_store_rows<2>(la->dqkv, s_dq, QS, 3 * d, row0, nrows, tid); }
+  { const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>(); sl_store_rows<2>(la->dqkv, s_dq, QS, 3 * d, row0, nrows, tid); }
 
   // ---- dx = dres1 + bf16(dqkv W_in) ----
   {
     const sl_f32x4 acc = sl_mma_tile<12>(wti, s_dq, QS, c, g);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { const int r = 4 * g + i; s_g[r * FS + n] = dres1[i] + sl_round(acc[i]); }
+    for (int i = 0; i < 4; ++i) { const int r = 4 * g + i; s_g[r * FS + n] = dres1[i] + bf16_round(acc[i]); }
   }
   sl_lds_barrier();
-  { const slb_args_ptr la = slb_late_args<ARGOFF>(); sl_store_rows<4>(la->dx32, s_g, FS, d, row0, nrows, tid); }
+  { const auto la = late_args<ops_tfd_layer_bwd_args, ARGOFF>(); sl_store_rows<4>(la->dx32, s_g, FS, d, row0, nrows, tid); }
   if (a.trace && tid == 0) {
     SLB_STAMP(8);
     for (int k = 0; k < 16; ++k) a.trace[16 * (unsigned long long)blockIdx.x + k] = stamp[k];
@@ -943,7 +915,6 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_layer_pair_bwd_kernel(const op
   __syncthreads();
   tfd_layer_bwd_body<true, false, (int)sizeof(ops_tfd_layer_bwd_args), true>(b);
 }
-
 
 // ================================================================================================================================
 // The model's head around the encoder (TFD:568-575): fc1 -> LayerNorm -> ReLU -> dropout -> fc2 on the B [CLS] rows, one launch per
@@ -969,13 +940,6 @@ __device__ __forceinline__ void sl_store_rows_ld(void* __restrict__ dst, long ld
   }
 }
 
-typedef const __attribute__((opencl_constant)) ops_tfd_head_args* slh_args_ptr;
-__device__ __forceinline__ slh_args_ptr slh_late_args() {
-  auto p = __builtin_amdgcn_kernarg_segment_ptr();
-  __asm__ volatile("" : "+s"(p));
-  return (slh_args_ptr)p;
-}
-
 __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_head_args a) {
   constexpr int XS = 128 + 8, HS = 256 + 8, FS2 = 256 + 4;
   __shared__ __attribute__((aligned(16))) uint16_t s_x[16 * XS];      // [CLS] rows (bf16 operand), at the end the output rows
@@ -997,10 +961,10 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int m = 16 * (wave + SL_NW * j) + c, mc = m < hid ? m : hid - 1;
-    b1v[j] = sl_bf2f(((const uint16_t*)a.b1)[mc]); gmv[j] = a.gamma[mc]; bev[j] = a.beta[mc];
+    b1v[j] = bf16_to_f32(((const uint16_t*)a.b1)[mc]); gmv[j] = a.gamma[mc]; bev[j] = a.beta[mc];
   }
   const int oc = 16 * wave + c;
-  const float b2v = sl_bf2f(((const uint16_t*)a.b2)[oc < C ? oc : C - 1]);
+  const float b2v = bf16_to_f32(((const uint16_t*)a.b2)[oc < C ? oc : C - 1]);
   const bool with_loss = a.targets != nullptr;                         // (kernel-uniform)
   float tgv[4] = {0.0f, 0.0f, 0.0f, 0.0f};                             // this lane's four targets (rows 4 g + i, column oc): requested up front
   if (with_loss) {
@@ -1031,9 +995,9 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * g + i;
-          const uint16_t ab = sl_f2bf(acc[i] + b1v[j]);
+          const uint16_t ab = f32_to_bf16(acc[i] + b1v[j]);
           s_a16[r * HS + m] = ab;
-          s_f32[r * FS2 + m] = r < nrows ? sl_bf2f(ab) : 0.0f;
+          s_f32[r * FS2 + m] = r < nrows ? bf16_to_f32(ab) : 0.0f;
         }
       }
     }
@@ -1042,7 +1006,7 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
 
   // ---- LayerNorm statistics (two passes over the published rows, every wave for its own rows), ReLU, dropout -> h ----
   {
-    const slh_args_ptr la = slh_late_args();
+    const auto la = late_args<ops_tfd_head_args>();
     const DropKey key = drop_key(la->seed, call);
     const float p = la->p_drop, ks = p > 0.0f ? 1.0f / (1.0f - p) : 1.0f, eps = la->eps;
     float mean[4], rstd[4];
@@ -1069,17 +1033,17 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * g + i;
-          float y = sl_round(__builtin_fmaf((s_f32[r * FS2 + m] - mean[i]) * rstd[i], gmv[j], bev[j]));     // the LayerNorm's bf16 output
+          float y = bf16_round(__builtin_fmaf((s_f32[r * FS2 + m] - mean[i]) * rstd[i], gmv[j], bev[j]));     // the LayerNorm's bf16 output
           y = (y > 0.0f || la->identity_act) ? y : 0.0f;
           if (p > 0.0f) y = drop_uniform(key, (uint64_t)((long)(b0 + r) * hid + m)) >= p ? y * ks : 0.0f;
-          s_h[r * HS + m] = r < nrows ? sl_f2bf(y) : (uint16_t)0;
+          s_h[r * HS + m] = r < nrows ? f32_to_bf16(y) : (uint16_t)0;
         }
       }
     }
   }
   sl_lds_barrier();
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every weight fragment is in; stores from here on
-  { const slh_args_ptr la = slh_late_args();
+  { const auto la = late_args<ops_tfd_head_args>();
     sl_store_rows<2>(la->a16, s_a16, HS, hid, b0, nrows, tid);
     sl_store_rows<2>(la->h, s_h, HS, hid, b0, nrows, tid); }
 
@@ -1087,7 +1051,7 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
   float ls0 = 0.0f, ls1 = 0.0f, ls2 = 0.0f;
   if (wave < NT2) {
     const sl_f32x4 acc = sl_mma_tile<8>(w2, s_h, HS, c, g);
-    const slh_args_ptr la = slh_late_args();
+    const auto la = late_args<ops_tfd_head_args>();
     float alpha = 0.0f, lo = 0.0f, hi = 0.0f, inv_n = 0.0f, bw = 0.0f;
     bool has_min = false, has_max = false;
     if (with_loss) {
@@ -1101,17 +1065,17 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = 4 * g + i;
-      const uint16_t pb = sl_f2bf(acc[i] + b2v);
+      const uint16_t pb = f32_to_bf16(acc[i] + b2v);
       s_x[r * XS + oc] = pb;                                           // (the [CLS] rows as an operand are dead)
       if (with_loss) {
         const bool live = r < nrows && oc < C;
-        const float p = sl_bf2f(pb), dd = p - tgv[i], sg = dd > 0.0f ? 1.0f : (dd < 0.0f ? -1.0f : 0.0f);
+        const float p = bf16_to_f32(pb), dd = p - tgv[i], sg = dd > 0.0f ? 1.0f : (dd < 0.0f ? -1.0f : 0.0f);
         float gv = (alpha * sg + (1.0f - alpha) * 2.0f * dd) * inv_n;
         float pen = 0.0f;
         if (has_min && p < lo) { pen += lo - p; gv -= bw; }
         if (has_max && p > hi) { pen += p - hi; gv += bw; }
         if (live) { ls0 += fabsf(dd); ls1 = __builtin_fmaf(dd, dd, ls1); ls2 += pen; }
-        s_gr[r * XS + oc] = live ? sl_f2bf(gv) : (uint16_t)0;
+        s_gr[r * XS + oc] = live ? f32_to_bf16(gv) : (uint16_t)0;
       }
     }
   }
@@ -1120,7 +1084,7 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
     if (lane == 0) { s_ls[wave][0] = ls0; s_ls[wave][1] = ls1; s_ls[wave][2] = ls2; }
   }
   sl_lds_barrier();
-  { const slh_args_ptr la = slh_late_args();
+  { const auto la = late_args<ops_tfd_head_args>();
     sl_store_rows_ld<2, 8>(la->out, C, s_x, XS, C, b0, nrows, tid);
     if (with_loss) {
       sl_store_rows_ld<2, 8>(la->grad, C, s_gr, XS, C, b0, nrows, tid);
@@ -1132,13 +1096,6 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
       }
     }
     if (blockIdx.x == 0 && tid == 0 && la->used_call) *SL_GLOBAL(unsigned long long, la->used_call) = call; }
-}
-
-typedef const __attribute__((opencl_constant)) ops_tfd_head_bwd_args* slhb_args_ptr;
-__device__ __forceinline__ slhb_args_ptr slhb_late_args() {
-  auto p = __builtin_amdgcn_kernarg_segment_ptr();
-  __asm__ volatile("" : "+s"(p));
-  return (slhb_args_ptr)p;
 }
 
 __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_head_bwd_args a, const int det) {
@@ -1177,10 +1134,10 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_
   uint2 gin = *(const uint2*)((const uint16_t*)a.g + (long)(b0 + (gok ? gr : 0)) * C + 4 * (gok ? gq : 0));
   if (a.g2) {                                              // a second gradient on the predictions: g + g2 as a bfloat16 addition rounds it
     const uint2 g2 = *(const uint2*)((const uint16_t*)a.g2 + (long)(b0 + (gok ? gr : 0)) * C + 4 * (gok ? gq : 0));
-    const uint32_t s0 = sl_f2bf(__uint_as_float(gin.x << 16) + __uint_as_float(g2.x << 16));
-    const uint32_t s1 = sl_f2bf(__uint_as_float(gin.x & 0xffff0000u) + __uint_as_float(g2.x & 0xffff0000u));
-    const uint32_t s2 = sl_f2bf(__uint_as_float(gin.y << 16) + __uint_as_float(g2.y << 16));
-    const uint32_t s3 = sl_f2bf(__uint_as_float(gin.y & 0xffff0000u) + __uint_as_float(g2.y & 0xffff0000u));
+    const uint32_t s0 = f32_to_bf16(__uint_as_float(gin.x << 16) + __uint_as_float(g2.x << 16));
+    const uint32_t s1 = f32_to_bf16(__uint_as_float(gin.x & 0xffff0000u) + __uint_as_float(g2.x & 0xffff0000u));
+    const uint32_t s2 = f32_to_bf16(__uint_as_float(gin.y << 16) + __uint_as_float(g2.y << 16));
+    const uint32_t s3 = f32_to_bf16(__uint_as_float(gin.y & 0xffff0000u) + __uint_as_float(g2.y & 0xffff0000u));
     gin = uint2{s0 | (s1 << 16), s2 | (s3 << 16)};
     if (a.g_sum && gok) *(uint2*)((uint16_t*)a.g_sum + (long)(b0 + gr) * C + 4 * gq) = gin;      // (may be `g` itself: own elements only)
   }
@@ -1209,7 +1166,7 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_
 
   // ---- d_h = g W_2 (bf16), ReLU / dropout backward (h's zeros), LayerNorm backward ----
   {
-    const slhb_args_ptr la = slhb_late_args();
+    const auto la = late_args<ops_tfd_head_bwd_args>();
     const float p = la->p_drop, ks = p > 0.0f ? 1.0f / (1.0f - p) : 1.0f;
     float dy[2][4], xh[2][4], rstd[4];
 #pragma unroll
@@ -1223,10 +1180,10 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_
       for (int i = 0; i < 4; ++i) {
         const int r = 4 * g + i;
         const bool live = t < NT1 && m < hid && r < nrows;
-        float gv = sl_round(acc[i]);
-        gv = (live && s_h[r * HS + (live ? m : 0)] != 0) ? sl_round(gv * ks) : 0.0f;
+        float gv = bf16_round(acc[i]);
+        gv = (live && s_h[r * HS + (live ? m : 0)] != 0) ? bf16_round(gv * ks) : 0.0f;
         dy[j][i] = gv;
-        xh[j][i] = live ? (sl_bf2f(s_a[r * HS + m]) - s_stat[0][r]) * rstd[i] : 0.0f;
+        xh[j][i] = live ? (bf16_to_f32(s_a[r * HS + m]) - s_stat[0][r]) * rstd[i] : 0.0f;
       }
     }
     // row means of gamma dy and gamma dy xhat over the hid columns: per-wave partial sums -> LDS -> one barrier
@@ -1268,37 +1225,30 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int m = 16 * (wave + SL_NW * j) + c;
-        if (m < hid) s_da[r * HS + m] = r < nrows ? sl_f2bf(rstd[i] * (gy[j][i] - s1 - xh[j][i] * s2)) : (uint16_t)0;
+        if (m < hid) s_da[r * HS + m] = r < nrows ? f32_to_bf16(rstd[i] * (gy[j][i] - s1 - xh[j][i] * s2)) : (uint16_t)0;
       }
     }
   }
   sl_lds_barrier();
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-  { const slhb_args_ptr la = slhb_late_args(); sl_store_rows<2>(la->d_a, s_da, HS, hid, b0, nrows, tid); }
+  { const auto la = late_args<ops_tfd_head_bwd_args>(); sl_store_rows<2>(la->d_a, s_da, HS, hid, b0, nrows, tid); }
 
   // ---- gradient of the [CLS] rows: d_a W_1 (bf16) into row b S of the caller's [B S, d] tensor ----
   {
     const sl_f32x4 acc = sl_mma_tile<8>(wt1, s_da, HS, c, g);
     const int n = 16 * wave + c;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) s_g[(4 * g + i) * XS + n] = sl_f2bf(acc[i]);       // (the incoming rows as an operand are dead)
+    for (int i = 0; i < 4; ++i) s_g[(4 * g + i) * XS + n] = f32_to_bf16(acc[i]);       // (the incoming rows as an operand are dead)
   }
   sl_lds_barrier();
-  { const slhb_args_ptr la = slhb_late_args(); sl_store_rows_ld<2, 16>(la->dcls_rows, (long)S * d, s_g, XS, d, (long)b0, nrows, tid); }
+  { const auto la = late_args<ops_tfd_head_bwd_args>(); sl_store_rows_ld<2, 16>(la->dcls_rows, (long)S * d, s_g, XS, d, (long)b0, nrows, tid); }
 }
-
 
 // ================================================================================================================================
 // The diffusion front end (TFD:443-478, :563-567): draw -> x_noisy -> MLP -> combine as one launch per direction (was: draw, product,
 // ReLU, product, combine forward; combine, product, ReLU backward).  16 input rows per workgroup; the [CLS] row of a sample is written
 // by the workgroup that owns the sample's first row.
 // ================================================================================================================================
-typedef const __attribute__((opencl_constant)) ops_tfd_front_args* slf_args_ptr;
-__device__ __forceinline__ slf_args_ptr slf_late_args() {
-  auto p = __builtin_amdgcn_kernarg_segment_ptr();
-  __asm__ volatile("" : "+s"(p));
-  return (slf_args_ptr)p;
-}
 
 __global__ __launch_bounds__(64 * SL_NW) void tfd_front_fwd_kernel(const ops_tfd_front_args a) {
   constexpr int XS = 128 + 8, HS = 256 + 8, FS = 128 + 4;
@@ -1336,8 +1286,8 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_fwd_kernel(const ops_tfd
   const int nc = colok ? n : d - 1;
   float b0v[2], pev[4];
 #pragma unroll
-  for (int j = 0; j < 2; ++j) { const int m = 16 * (wave + SL_NW * j) + c; b0v[j] = sl_bf2f(((const uint16_t*)a.b0)[m < hid ? m : hid - 1]); }
-  const float b2v = sl_bf2f(((const uint16_t*)a.b2)[nc]);
+  for (int j = 0; j < 2; ++j) { const int m = 16 * (wave + SL_NW * j) + c; b0v[j] = bf16_to_f32(((const uint16_t*)a.b0)[m < hid ? m : hid - 1]); }
+  const float b2v = bf16_to_f32(((const uint16_t*)a.b2)[nc]);
   const float inv_Nc = 1.0f / (float)Nc;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -1379,8 +1329,8 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_fwd_kernel(const ops_tfd
     if (pq == 0) { s_ab[0][pr] = s_a; s_ab[1][pr] = s_b; }
     *(float4*)(s_f32 + pr * FS + 4 * pq) = make_float4(v[0], v[1], v[2], v[3]);
     uint2 o;
-    o.x = (uint32_t)sl_f2bf(v[0]) | ((uint32_t)sl_f2bf(v[1]) << 16);
-    o.y = (uint32_t)sl_f2bf(v[2]) | ((uint32_t)sl_f2bf(v[3]) << 16);
+    o.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
+    o.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
     *(uint2*)(s_x + pr * XS + 4 * pq) = o;
   }
   sl_zero_cols(s_h, HS, hid, 256, tid);
@@ -1397,15 +1347,15 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_fwd_kernel(const ops_tfd
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * g + i;
-          const float hv = sl_round(acc[i] + b0v[j]);
-          s_h[r * HS + m] = (r < nrows && (hv > 0.0f || a.identity_act)) ? sl_f2bf(hv) : (uint16_t)0;
+          const float hv = bf16_round(acc[i] + b0v[j]);
+          s_h[r * HS + m] = (r < nrows && (hv > 0.0f || a.identity_act)) ? f32_to_bf16(hv) : (uint16_t)0;
         }
       }
     }
   }
   sl_lds_barrier();
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
-  { const slf_args_ptr la = slf_late_args();
+  { const auto la = late_args<ops_tfd_front_args>();
     sl_store_rows<2>(la->xn16, s_x, XS, d, r0, nrows, tid);
     sl_store_rows<2>(la->h, s_h, HS, hid, r0, nrows, tid); }
 
@@ -1416,16 +1366,16 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_fwd_kernel(const ops_tfd
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = 4 * g + i;
-      const float m = sl_round(acc[i] + b2v);
+      const float m = bf16_round(acc[i] + b2v);
       const float z = (s_f32[r * FS + n] - s_ab[1][r] * m) / s_ab[0][r] + pev[i];
       s_f32[r * FS + n] = z;
-      s_x[r * XS + n] = sl_f2bf(z);
+      s_x[r * XS + n] = f32_to_bf16(z);
     }
   }
   sl_lds_barrier();
   {
     // z rows: input row r of sample b = r / Nc sits at z row r + b + 1; the sample's [CLS] row (cls + pe[0]) goes out with its first row
-    const slf_args_ptr la = slf_late_args();
+    const auto la = late_args<ops_tfd_front_args>();
     __attribute__((address_space(1))) float* z = SL_GLOBAL(float, la->z);
     __attribute__((address_space(1))) uint16_t* z16 = SL_GLOBAL(uint16_t, la->z16);
     const int ppr = d / 4;
@@ -1442,8 +1392,8 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_fwd_kernel(const ops_tfd
         const sl_f32x4 w = {cv.x + pv.x, cv.y + pv.y, cv.z + pv.z, cv.w + pv.w};
         *(__attribute__((address_space(1))) sl_f32x4*)(z + (zr - 1) * d + 4 * q) = w;
         sl_u32x2 o;
-        o.x = (uint32_t)sl_f2bf(w.x) | ((uint32_t)sl_f2bf(w.y) << 16);
-        o.y = (uint32_t)sl_f2bf(w.z) | ((uint32_t)sl_f2bf(w.w) << 16);
+        o.x = (uint32_t)f32_to_bf16(w.x) | ((uint32_t)f32_to_bf16(w.y) << 16);
+        o.y = (uint32_t)f32_to_bf16(w.z) | ((uint32_t)f32_to_bf16(w.w) << 16);
         *(__attribute__((address_space(1))) sl_u32x2*)(z16 + (zr - 1) * d + 4 * q) = o;
       }
     }
@@ -1488,15 +1438,15 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_bwd_kernel(const ops_tfd
     if (cc < d)
       for (long bb = (long)blockIdx.x + (long)ncw * part; bb < a.B; bb += (long)ncw * 4) {
         const long ci = bb * S * d + cc;
-        acc += (a.g32 ? a.g32[ci] : 0.0f) + (a.g16 ? sl_bf2f(((const uint16_t*)a.g16)[ci]) : 0.0f);
+        acc += (a.g32 ? a.g32[ci] : 0.0f) + (a.g16 ? bf16_to_f32(((const uint16_t*)a.g16)[ci]) : 0.0f);
       }
     s_cls[part][cc] = acc;
   }
   {
     uint2 o = uint2{0u, 0u};
     if (pok) {
-      o.x = (uint32_t)sl_f2bf(ratio * gv.x) | ((uint32_t)sl_f2bf(ratio * gv.y) << 16);
-      o.y = (uint32_t)sl_f2bf(ratio * gv.z) | ((uint32_t)sl_f2bf(ratio * gv.w) << 16);
+      o.x = (uint32_t)f32_to_bf16(ratio * gv.x) | ((uint32_t)f32_to_bf16(ratio * gv.y) << 16);
+      o.y = (uint32_t)f32_to_bf16(ratio * gv.z) | ((uint32_t)f32_to_bf16(ratio * gv.w) << 16);
     }
     *(uint2*)(s_dm + pr * XS + 4 * pq) = o;
     *(uint4*)(s_h + pr * HS + 8 * pq) = hok ? hin : uint4{0u, 0u, 0u, 0u};
@@ -1515,7 +1465,7 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_front_bwd_kernel(const ops_tfd
     for (int i = 0; i < 4; ++i) {
       const int r = 4 * g + i;
       const bool live = t < NT1 && m < hid && r < nrows;
-      res[j][i] = (live && s_h[r * HS + (live ? m : 0)] != 0) ? sl_f2bf(acc[i]) : (uint16_t)0;
+      res[j][i] = (live && s_h[r * HS + (live ? m : 0)] != 0) ? f32_to_bf16(acc[i]) : (uint16_t)0;
     }
   }
   sl_lds_barrier();                                         // every lane has read its h values: s_h becomes d_h

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/openpystruct_amd.h"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
@@ -18,12 +19,6 @@ struct SizingArgs {
   ops_sizing_params hp;
   const float* schedule;             // optional [max_epochs, 2]: step size, sqrt(1 - beta2^(t+1)) (ops_sizing_schedule_f32)
 };
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
-  return x;
-}
 
 // state of one case as one wavefront holds it between the loads and the arithmetic (K = elements per lane)
 template <int K>

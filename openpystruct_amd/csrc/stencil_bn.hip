@@ -16,34 +16,13 @@
 #include <stdint.h>
 
 #include "../../include/openpystruct_amd.h"
+#include "lane_common.hpp"
 
 namespace opsamd {
 
 constexpr int SB_THREADS = 256;     // 4 waves: lane -> column, wave -> row
 constexpr int SB_MAXG = 64;         // workgroups per launch (partial sums per workgroup, no atomics, no zeroing)
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-// sums NV values over the workgroup; every thread gets the totals
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double* s_red /*[4][NV]*/) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum_d(v[k]);
-  __syncthreads();
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s_red[wave * NV + k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double t = 0.0;
-    for (int w = 0; w < SB_THREADS / 64; ++w) t += s_red[w * NV + k];
-    v[k] = t;
-  }
-}
 // totals of the per-workgroup partial sums part[G][NV] (every thread reads them: G <= 64)
 template <int NV>
 __device__ __forceinline__ void sum_partials(const double* __restrict__ part, int G, double (&v)[NV]) {
@@ -54,15 +33,8 @@ __device__ __forceinline__ void sum_partials(const double* __restrict__ part, in
     for (int k = 0; k < NV; ++k) v[k] += part[g * NV + k];
 }
 
-// bfloat16 <-> float (round to nearest even), for the autocast dtype of z / grad_z
-__device__ __forceinline__ uint16_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 __device__ __forceinline__ float ld_grad(const void* g, long i, int bf16) {
-  return bf16 ? __uint_as_float((uint32_t)((const uint16_t*)g)[i] << 16) : ((const float*)g)[i];
+  return bf16 ? bf16_to_f32(((const uint16_t*)g)[i]) : ((const float*)g)[i];
 }
 
 __device__ __forceinline__ float stencil_at(const float* __restrict__ row, int i, int F, float w0, float w1, float w2, float b) {
@@ -87,7 +59,7 @@ __global__ __launch_bounds__(SB_THREADS) void stencil_bn_fwd_stats_kernel(int B,
     }
   }
   double acc[2] = {(double)p0, (double)p1};
-  block_sum<2>(acc, s_red);
+  block_sum<SB_THREADS / 64, true>(acc, s_red);
   if (threadIdx.x == 0) { part[blockIdx.x * 2] = acc[0]; part[blockIdx.x * 2 + 1] = acc[1]; }
 }
 
@@ -123,7 +95,7 @@ __global__ __launch_bounds__(SB_THREADS) void stencil_bn_fwd_apply_kernel(int B,
     const float* row = x + (long)r * F;
     for (int i = tx; i < F; i += 64) {
       const float v = __builtin_fmaf(stencil_at(row, i, F, w0, w1, w2, b), scale, shift);
-      if (z_bf16) ((uint16_t*)z)[(long)r * F + i] = f2bf(v);
+      if (z_bf16) ((uint16_t*)z)[(long)r * F + i] = f32_to_bf16(v);
       else ((float*)z)[(long)r * F + i] = v;
     }
   }
@@ -146,7 +118,7 @@ __global__ __launch_bounds__(SB_THREADS) void stencil_bn_bwd_stats_kernel(int B,
     }
   }
   double acc[2] = {(double)q0, (double)q1};
-  block_sum<2>(acc, s_red);
+  block_sum<SB_THREADS / 64, true>(acc, s_red);
   if (threadIdx.x == 0) { part[blockIdx.x * 2] = acc[0]; part[blockIdx.x * 2 + 1] = acc[1]; }
 }
 
@@ -190,7 +162,7 @@ __global__ __launch_bounds__(SB_THREADS) void stencil_bn_bwd_apply_kernel(int B,
     }
   }
   double acc4[4] = {(double)a0, (double)a1, (double)a2, (double)a3};
-  block_sum<4>(acc4, s_red);
+  block_sum<SB_THREADS / 64, true>(acc4, s_red);
   if (threadIdx.x == 0)
 #pragma unroll
     for (int q = 0; q < 4; ++q) part4[blockIdx.x * 4 + q] = acc4[q];
