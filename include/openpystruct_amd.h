@@ -205,7 +205,7 @@ int ops_beam_residual_vjp_f64(int B, int Ne, const double* x, long x_bstride, co
 
 /* The surrogates' FE-residual TERM (r04, ABI 10) in three launches -- what physics.py fe_residual_loss built from ~60 framework nodes around
  * the two entry points above:
- *   I_e = max(preds[b, e] * I_scale[e] + I_mean[e], I_min);   u = (v_rec, t_rec)[rows[b]]  (I-only models; rows NULL: row b)   or
+ *   I_e = clamp_min(preds[b, e] * I_scale[e] + I_mean[e], I_min) (NaN stays NaN);   u = (v_rec, t_rec)[rows[b]]  (I-only models; rows NULL: row b)   or
  *   v_n = preds[b, Ne + n] * v_scale[n] + v_mean[n], theta_n = preds[b, Ne + N + n] * t_scale[n] + t_mean[n]   (v_rec == NULL: the PINN);
  *   r = D (K(I) u - f) with Fy [.., N] gathered by rows, shared x [N] / fix [N] / E / wy;   e = r / diag K(I)  (no gradient through the diagonal);
  *   value[0] = weight * (mean e_v^2 / (mean v^2 + 1e-30) + mean e_t^2 / (mean theta^2 + 1e-30)),  value_sum[0] += it (optional).

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void beam_dI_kernel(const ResParams p, const d
 // step around ops_beam_residual_f64 / _vjp_f64 -- inverse scalers, clamp, casts, three row gathers, the stiffness diagonal's
 // concatenations, four mean reductions of 11-13 us each and everything's backward: 250 of the 390 us of a TFD + physics step):
 //
-//     I_e  = max(p[b, e] * sI_e + mI_e, I_min)                       inertias from the model's standardised predictions
+//     I_e  = clamp_min(p[b, e] * sI_e + mI_e, I_min)                 inertias from the model's standardised predictions (NaN stays NaN)
 //     u    = recorded (v, theta)[rows[b]]   or   p[b, Ne + n] * s_n + m_n            (I-only models / the PINN's own displacement outputs)
 //     r    = D (K(I) u - f),  e_v = r_v / K_vv,  e_t = r_t / K_tt                     (Jacobi-scaled residual; K_ii from I, no gradient)
 //     term = weight * ( mean(e_v^2) / (mean(v^2) + 1e-30) + mean(e_t^2) / (mean(theta^2) + 1e-30) )     (means over all B N entries)
@@ -155,8 +155,9 @@ __device__ __forceinline__ float ph_pred(const PhysArgs& a, long b, int c) {
 }
 __device__ __forceinline__ double ph_I(const PhysArgs& a, long b, int e, bool* clamped = nullptr) {      // 0 <= e < Ne
   const float v = ph_pred(a, b, e) * a.I_scale[e] + a.I_mean[e];          // float32, as the scaler's inverse transform computes it
-  if (clamped) *clamped = !(v > a.I_min);
-  return (double)(v > a.I_min ? v : a.I_min);
+  // clamp_min's semantics: a NaN prediction stays NaN (the term shows a diverged model), only v < I_min is clamped
+  if (clamped) *clamped = v < a.I_min;
+  return (double)(v < a.I_min ? a.I_min : v);
 }
 __device__ __forceinline__ void ph_u(const PhysArgs& a, long b, long row, int n, double& v, double& t) {   // 0 <= n <= Ne
   const int N = a.Ne + 1;

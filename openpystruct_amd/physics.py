@@ -16,6 +16,7 @@ from __future__ import annotations
 import torch
 
 from . import _cabi
+from .beam import _check_inputs
 
 
 def _f64(t, dev):
@@ -73,10 +74,13 @@ class _FEResidual(torch.autograd.Function):
 
 
 def fe_residual(I, v, theta, x, E, fix, Fy, wy):
-    """r_v, r_theta [B,N] = D (K(I) [v; theta] - f); differentiable w.r.t. I, v, theta (float64 inside)."""
+    """r_v, r_theta [B,N] = D (K(I) [v; theta] - f); differentiable w.r.t. I, v, theta (float64 inside).  Shapes as `beam_solve`:
+    x, fix [N] or [B,N], E, wy scalar or [B,Ne] (the kernels read them with those strides: anything else is refused here)."""
     dev = I.device
-    return _FEResidual.apply(I, v, theta, _f64(x, dev), _f64(E, dev), torch.as_tensor(fix, dtype=torch.uint8, device=dev).contiguous(),
-                             _f64(Fy, dev), _f64(wy, dev))
+    x, E, fix, Fy, wy = (_f64(x, dev), _f64(E, dev), torch.as_tensor(fix, dtype=torch.uint8, device=dev).contiguous(), _f64(Fy, dev),
+                         _f64(wy, dev))
+    _check_inputs("fe_residual", x, E, I.detach().to(torch.float64), fix, wy, Fy)
+    return _FEResidual.apply(I, v, theta, x, E, fix, Fy, wy)
 
 
 def stiffness_diagonal(I, x, E):
@@ -115,6 +119,9 @@ class _FusedResidualTerm(torch.autograd.Function):
         if preds.dtype not in (torch.float32, torch.bfloat16) or preds.dim() != 2 or preds.stride(1) != 1:
             raise ValueError("predictions must be a [B, C] float32 or bfloat16 matrix with unit column stride")
         B, N = preds.shape[0], nel + 1
+        ncols = nel if torch.is_tensor(disp[0]) else nel + 2 * N
+        if preds.shape[1] < ncols:
+            raise ValueError(f"predictions must have at least {ncols} columns, got {preds.shape[1]}")
         f64 = dict(dtype=torch.float64, device=dev)
         ev, et = torch.empty((B, N), **f64), torch.empty((B, N), **f64)
         part = torch.empty(int(lib.ops_physics_loss_part_doubles(B, nel)), **f64)
@@ -148,7 +155,7 @@ class _FusedResidualTerm(torch.autograd.Function):
         if rc != _cabi.OK:
             raise RuntimeError(f"ops_physics_loss_fwd failed with code {rc}")
         ctx.args, ctx.keep = a, keep
-        ctx.ncols = nel if torch.is_tensor(disp[0]) else nel + 2 * N
+        ctx.ncols = ncols
         return value
 
     @staticmethod
@@ -179,6 +186,10 @@ def fused_residual_term(preds, nel, sI, disp, rows, Fy, x, E, fix, wy, weight, a
     if not preds.is_cuda:
         raise RuntimeError("fused_residual_term needs GPU tensors: openpystruct_amd has no CPU fallback")
     dev = preds.device
-    spec = (int(nel), sI, disp, rows, _f64(Fy, dev), _f64(x, dev), float(E), torch.as_tensor(fix, dtype=torch.uint8, device=dev).contiguous(),
-            float(wy), float(weight), acc)
+    nel = int(nel)
+    x, fix = _f64(x, dev), torch.as_tensor(fix, dtype=torch.uint8, device=dev).contiguous()
+    for name, t in (("x", x), ("fix", fix)):          # the kernels read both as one shared [N] array
+        if tuple(t.shape) != (nel + 1,):
+            raise ValueError(f"{name} must be [{nel + 1}] (shared by the batch), got {tuple(t.shape)}")
+    spec = (nel, sI, disp, rows, _f64(Fy, dev), x, float(E), fix, float(wy), float(weight), acc)
     return _FusedResidualTerm.apply(preds, spec)

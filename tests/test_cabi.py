@@ -169,3 +169,64 @@ def test_frame_dispatch_table_on_the_host():
     finally:
         lib.ops_amd_set_option(b"frame_latency_batch", -1); lib.ops_amd_set_option(b"frame_pack", 1)
     assert lib.ops_amd_get_option(b"deterministic") == 0
+
+
+def _arg_buffer():
+    """Pointer for the 'valid' arguments of the refusal checks below: 4 KiB of zeros on the GPU when one is visible, so that a C
+    entry that stopped refusing and launched would still read and write memory this test owns (in bounds for every shape used)."""
+    import numpy as np
+    import torch
+    if torch.cuda.is_available():
+        t = torch.zeros(512, dtype=torch.float64, device="cuda")
+        return t, t.data_ptr()
+    a = np.zeros(512)
+    return a, a.ctypes.data
+
+
+def test_residual_vjp_entry_refuses_bad_arguments(lib):
+    keep, p = _arg_buffer()
+    B, Ne = 2, 3
+
+    def call(B=B, Ne=Ne, null=None):
+        ptrs = [None if k == null else p for k in range(13)]      # x, E, I, fix, v, theta, gv, gt, sv, st, dv, dt, dI
+        x, E, I, fix, v, th, gv, gt, sv, st, dv, dt, dI = ptrs
+        return lib.ops_beam_residual_vjp_f64(B, Ne, x, 0, E, 0, I, fix, 0, v, th, gv, gt, sv, st, dv, dt, dI, None)
+    for k in range(13):
+        assert call(null=k) == _cabi.ERR_INVALID_ARG, k
+    assert call(Ne=0) == _cabi.ERR_INVALID_ARG and call(Ne=-1) == _cabi.ERR_INVALID_ARG and call(B=-1) == _cabi.ERR_INVALID_ARG
+    assert call(B=0) == _cabi.OK and call(B=0, null=0) == _cabi.OK        # an empty batch is a no-op, checked before the pointers
+    del keep
+
+
+def test_physics_loss_entries_refuse_bad_arguments(lib):
+    keep, p = _arg_buffer()
+    B, Ne = 2, 3
+    N = Ne + 1
+    assert lib.ops_physics_loss_part_doubles(B, Ne) == 8
+
+    def args(rec=True, **kw):
+        a = _cabi.PhysicsLossArgs(B=B, Ne=Ne, preds=p, preds_bf16=0, ldp=Ne if rec else Ne + 2 * N, I_scale=p, I_mean=p, I_min=1e-8,
+                                  Fy=p, x=p, fix=p, E=2e11, wy=-1e3, weight=1.0, ev=p, et=p, part=p, value=p, dpreds=p)
+        if rec:
+            a.v_rec, a.t_rec = p, p
+        else:
+            a.v_scale, a.v_mean, a.t_scale, a.t_mean = p, p, p, p
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return a
+
+    def refused(a):
+        return (lib.ops_physics_loss_fwd(ctypes.byref(a), None) == _cabi.ERR_INVALID_ARG
+                and lib.ops_physics_loss_bwd(ctypes.byref(a), None) == _cabi.ERR_INVALID_ARG)
+    assert lib.ops_physics_loss_fwd(None, None) == _cabi.ERR_INVALID_ARG and lib.ops_physics_loss_bwd(None, None) == _cabi.ERR_INVALID_ARG
+    for rec in (True, False):
+        for name in ("preds", "I_scale", "I_mean", "Fy", "x", "fix", "ev", "et", "part"):
+            assert refused(args(rec, **{name: None})), (rec, name)
+        assert refused(args(rec, B=0)) and refused(args(rec, Ne=0)) and refused(args(rec, B=-1))
+        assert refused(args(rec, ldp=Ne - 1 if rec else Ne + 2 * N - 1)), rec           # fewer columns than the term reads
+        assert lib.ops_physics_loss_fwd(ctypes.byref(args(rec, value=None)), None) == _cabi.ERR_INVALID_ARG      # its output missing
+        assert lib.ops_physics_loss_bwd(ctypes.byref(args(rec, dpreds=None)), None) == _cabi.ERR_INVALID_ARG
+    assert refused(args(True, t_rec=None)) and refused(args(True, v_rec=None))     # one recorded field without the other
+    for name in ("v_scale", "v_mean", "t_scale", "t_mean"):                        # predicted fields without their scalers
+        assert refused(args(False, **{name: None})), name
+    del keep

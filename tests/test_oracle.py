@@ -264,3 +264,72 @@ def test_kat_frame_oracle_l_shaped_cantilever():
     assert tip[0] == pytest.approx(top[0], rel=1e-9, abs=1e-15)           # the arm carries no axial force
     # base reactions through the element end forces of the first column element: global (Fx, Fy, Mz) at node 0
     assert f[0, 1] == pytest.approx(-P, rel=1e-9) and f[0, 2] == pytest.approx(-P * a, rel=1e-9) and abs(f[0, 0]) < 1e-6 * abs(P)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the float64 references of the FE-residual kernels (tests/beam_dense.py), pinned to the oracle's assembled K and to differences
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("Ne,B,per_beam,per_elem", [(1, 2, True, True), (5, 3, True, True), (13, 4, False, True), (30, 3, True, False)])
+def test_residual_ref_equals_the_masked_assembled_residual(Ne, B, per_beam, per_elem):
+    import torch
+
+    from tests.beam_dense import random_case, residual_ref
+    rng = np.random.default_rng(100 + Ne)
+    N = Ne + 1
+    x, fix, I, Fy = random_case(rng, B, Ne, per_beam=per_beam, rz=True)
+    Ev = rng.uniform(1.5e11, 2.5e11, size=(B, Ne)) if per_elem else np.float64(2e11)
+    wy = rng.uniform(-2e3, 0, size=(B, Ne)) if per_elem else np.float64(-750.0)
+    v, th = rng.standard_normal((B, N)) * 1e-2, rng.standard_normal((B, N)) * 1e-3
+    t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))   # noqa: E731
+    rv, rt, sv, st = (a.numpy() for a in residual_ref(x, t(Ev), t(I), fix, t(Fy), t(wy), t(v), t(th)))
+    assert any(((fix if fix.ndim == 1 else fix[b]) & 2).any() for b in range(B))      # a clamped rotation occurs
+    for b in range(B):
+        pick = lambda a: a if np.ndim(a) < 2 else a[b]     # noqa: E731
+        K, f = bo.assemble_beam(pick(x), pick(Ev), I[b], Fy[b], pick(wy))
+        u = np.empty(2 * N); u[0::2] = v[b]; u[1::2] = th[b]
+        r = K @ u - f
+        fb = pick(fix).astype(np.int64)
+        r[0::2][(fb & 1) != 0] = 0.0
+        r[1::2][(fb & 2) != 0] = 0.0
+        assert (rv[b][(fb & 1) != 0] == 0).all() and (rt[b][(fb & 2) != 0] == 0).all()
+        assert (np.abs(rv[b] - r[0::2]) <= 4e-15 * sv[b]).all() and (np.abs(rt[b] - r[1::2]) <= 4e-15 * st[b]).all()
+        assert (np.abs(r[0::2]) <= sv[b] * (1 + 1e-12)).all() and (np.abs(r[1::2]) <= st[b] * (1 + 1e-12)).all()
+
+
+@pytest.mark.parametrize("mode", ["recorded", "predicted"])
+def test_residual_term_ref_gradient_matches_central_differences(mode):
+    """d term / d preds of the fused term's reference against float64 central differences of the same function, with the
+    Jacobi diagonal and the mean-square scales held (they are detached in the term), a clamped inertia included."""
+    import types
+
+    import torch
+
+    from tests.beam_dense import random_case, residual_term_ref
+    rng = np.random.default_rng(7 if mode == "recorded" else 8)
+    B, Ne, G = 3, 6, 5
+    N = Ne + 1
+    x, fix, I, Fy = random_case(rng, G, Ne, rz=True)
+    t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64))   # noqa: E731
+    sc = lambda m, s: types.SimpleNamespace(mean_=t(m), scale_=t(s))   # noqa: E731
+    sI = sc(I.mean(0), I.std(0) + 1e-3)
+    rows = torch.tensor([4, 1, 4])
+    if mode == "recorded":
+        disp = (t(rng.standard_normal((G, N)) * 1e-2), t(rng.standard_normal((G, N)) * 1e-3))
+        C = Ne
+    else:
+        disp = (sc(rng.standard_normal(N) * 1e-2, np.full(N, 1e-2)), sc(rng.standard_normal(N) * 1e-3, np.full(N, 1e-3)))
+        C = Ne + 2 * N
+    p = t(rng.standard_normal((B, C)))
+    p[1, 2] = -1e3                                                    # clamped: no gradient
+    args = (Ne, sI, disp, rows, t(Fy), x, 2e11, fix, -750.0, 0.25)
+    val, g, consts = residual_term_ref(p, *args)
+    assert g.shape == (B, C) and float(g[1, 2]) == 0.0 and float(g.abs().max()) > 0
+    fd = torch.zeros_like(g)
+    for b in range(B):
+        for c in range(C):
+            h = 1e-6 * max(1.0, abs(float(p[b, c])))
+            pp, pm = p.clone(), p.clone()
+            pp[b, c] += h
+            pm[b, c] -= h
+            fd[b, c] = (residual_term_ref(pp, *args, consts=consts)[0] - residual_term_ref(pm, *args, consts=consts)[0]) / (2 * h)
+    assert float((fd - g).abs().max()) <= 1e-9 * float(g.abs().max()), float((fd - g).abs().max() / g.abs().max())
