@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define OPS_AMD_ABI_VERSION 13
+#define OPS_AMD_ABI_VERSION 14
 
 /* return codes of the launch functions (per-beam results are in `status`) */
 #define OPS_AMD_OK 0
@@ -343,9 +343,10 @@ const char* ops_amd_last_error(void);
  *                          per CU: e.g. 10 x 10 at 257 .. 768 frames); 0: never; 2: for every small batch (A/B, tests)
  *   "deterministic"        0 (default); 1: the Transformer-Diffusion step's gradient launches reduce in a fixed order -- one row split per weight-
  *                          gradient product and one workgroup per column-sum strip (ops_linear_wgrad_accumulate*), one workgroup for the [CLS]
- *                          sums (ops_tfd_front_bwd), the head's LayerNorm sums in workgroup order (ops_tfd_head_bwd) -- so that two runs of one
- *                          seed give the same bits (float atomics otherwise land in arrival order); slower.  Takes effect at launch: a captured
- *                          graph keeps the mode it was captured in.  (The PINN step and the FE kernels have no float atomics.) */
+ *                          sums (ops_tfd_front_bwd), the head's LayerNorm sums as per-workgroup partials reduced by the caller in fixed order
+ *                          (ops_tfd_head_bwd refuses a NULL ln_part) -- so that two runs of one seed give the same bits (float atomics otherwise
+ *                          land in arrival order); slower.  Takes effect at launch: a captured graph keeps the mode it was captured in.  (The
+ *                          PINN step and the FE kernels have no float atomics.)  Setting it makes no HIP call. */
 int ops_amd_set_option(const char* name, long value);
 long ops_amd_get_option(const char* name);
 
@@ -648,7 +649,8 @@ int ops_tfd_encoder_layer_pair_bwd(const ops_tfd_layer_bwd_args* later, const op
  * ReLU, dropout, out = fc2 + b2 (bf16 [B, C]).  d <= 128, hid <= 256 (multiples of 8), C <= 128 (a multiple of 4); weights: fragment-tiled
  * copies as for the layer launches (forward Wp, backward Wtp).  Saved for the backward launch and the weight-gradient products: a16,
  * mean, rstd, h.  Backward: g [B, C] bf16 = d loss / d out -> d_a [B, hid] bf16 (gradient at fc1's output), dcls = d_a W_1 written into the
- * [CLS] rows (row stride S d elements) of `dcls_rows` (a [B S, d] bf16 tensor whose other rows the caller keeps zero), dgamma / dbeta ADDED. */
+ * [CLS] rows (row stride S d elements) of `dcls_rows` (a [B S, d] bf16 tensor whose other rows the caller keeps zero), dgamma / dbeta ADDED
+ * (or, with ln_part, stored as per-workgroup partials). */
 typedef struct ops_tfd_head_args {
   int32_t B, S, d, hid, C;
   const void* y16;
@@ -678,6 +680,10 @@ typedef struct ops_tfd_head_bwd_args {
    * launch's own loss gradient plus what another term (the FE-residual one) put on the predictions; g_sum (may be NULL, may be g)
    * receives the sum -- the weight-gradient product of the output layer reads it. */
   const void* g2; void* g_sum;
+  float* ln_part;                                     /* ABI 14: NULL, or [workgroups = ceil(B / 16)][2][hid] float32: the launch stores every
+                                                         workgroup's column sums (dgamma | dbeta) there INSTEAD of adding them into dgamma /
+                                                         dbeta; the caller sums the rows in a fixed order.  Required in deterministic mode
+                                                         (NULL: ERR_INVALID_ARG) */
 } ops_tfd_head_bwd_args;
 int ops_tfd_head_bwd(const ops_tfd_head_bwd_args* args, void* stream);
 

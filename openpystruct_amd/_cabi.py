@@ -10,7 +10,7 @@ import os
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 FRAME_REUSE_PLAN = 1     # include/openpystruct_amd.h OPS_FRAME_REUSE_PLAN
-ABI_VERSION = 13     # include/openpystruct_amd.h OPS_AMD_ABI_VERSION
+ABI_VERSION = 14     # include/openpystruct_amd.h OPS_AMD_ABI_VERSION
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
 
@@ -207,7 +207,8 @@ class TfdHeadBwdArgs(ctypes.Structure):
     _vp, _i, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
     _fields_ = [("B", _i), ("S", _i), ("d", _i), ("hid", _i), ("C", _i), ("g", _vp), ("Wt2", _vp), ("Wt1", _vp), ("gamma", _vp), ("p_drop", _f),
                 ("a16", _vp), ("mean", _vp), ("rstd", _vp), ("h", _vp), ("d_a", _vp), ("dcls_rows", _vp), ("dgamma", _vp), ("dbeta", _vp),
-                ("loss_part", _vp), ("alpha", _vp), ("alpha0", _f), ("box_weight", _f), ("loss", _vp), ("loss_sum", _vp), ("g2", _vp), ("g_sum", _vp)]
+                ("loss_part", _vp), ("alpha", _vp), ("alpha0", _f), ("box_weight", _f), ("loss", _vp), ("loss_sum", _vp), ("g2", _vp), ("g_sum", _vp),
+                ("ln_part", _vp)]
 
 
 class PhysicsLossArgs(ctypes.Structure):

@@ -39,12 +39,7 @@ extern "C" int ops_amd_set_option(const char* name, long value) {
   if (n == "frame_latency_batch") { g_frame_latency_batch.store(value < 0 ? -1 : value); return OPS_AMD_OK; }
   if (n == "frame_pack") { g_frame_pack.store(value != 0); return OPS_AMD_OK; }
   if (n == "frame_coop") { if (value < 0 || value > 2) return OPS_AMD_ERR_INVALID_ARG; g_frame_coop.store(value); return OPS_AMD_OK; }
-  if (n == "deterministic") {
-    g_deterministic.store(value != 0);
-    int ndev = 0;
-    if (value != 0 && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) opsamd::reset_head_ticket();      // (current device; no GPU: nothing to re-arm)
-    return OPS_AMD_OK;
-  }
+  if (n == "deterministic") { g_deterministic.store(value != 0); return OPS_AMD_OK; }
   return OPS_AMD_ERR_INVALID_ARG;
 }
 extern "C" long ops_amd_get_option(const char* name) {

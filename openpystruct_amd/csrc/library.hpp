@@ -14,8 +14,6 @@ long frame_latency_batch_option();      // "frame_latency_batch": -1 = the dispa
 long frame_coop_option();               // "frame_coop": 0 = never four waves per frame; 1 = where measured faster; 2 = for every small batch
 long frame_pack_option();               // "frame_pack": 0 = one wave per frame for every half bandwidth
 
-void reset_head_ticket();               // seq_layer.hip: re-arms the deterministic head backward's ticket
-
 // Raises kernel `Fn`'s dynamic-LDS limit to `bytes` on device `devid` (0 .. 63), once per device: the limit is a per-DEVICE function attribute
 // and a process may drive several GPUs (ops.set_device / FrameTopology(device=...)).  Two threads racing here both set the same value.
 template <auto Fn>

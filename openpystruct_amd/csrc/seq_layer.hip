@@ -21,6 +21,10 @@
 // bf16 before it is used, LayerNorm statistics and the residual stream in fp32.  Dropout masks: the counter-based stream of
 // csrc/dropout_stream.hpp, one seed per site; the backward launches regenerate them from (seed, the call counter value the forward
 // launch used, element index) -- no mask is stored.
+//
+// LayerNorm gamma / beta gradients (layer and head backward): float atomics, or -- with the argument block's `ln_part` -- each workgroup's
+// column sums stored as its own row of partials, which the caller adds up in a fixed order (library option "deterministic").  No launch
+// waits for another workgroup.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -32,10 +36,6 @@
 #include "library.hpp"
 
 namespace opsamd {
-
-// deterministic mode: the workgroups of the head's backward launch add their LayerNorm gamma / beta column sums IN WORKGROUP ORDER (a ticket:
-// workgroup i waits for i - 1, which the dispatcher started before it); the last one re-arms the ticket for the next launch
-__device__ unsigned int g_head_ticket = 0u;
 
 typedef __bf16 sl_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float sl_f32x4 __attribute__((ext_vector_type(4)));
@@ -1098,7 +1098,7 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_fwd_kernel(const ops_tfd_
     if (blockIdx.x == 0 && tid == 0 && la->used_call) *SL_GLOBAL(unsigned long long, la->used_call) = call; }
 }
 
-__global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_head_bwd_args a, const int det) {
+__global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_head_bwd_args a) {
   constexpr int XS = 128 + 8, HS = 256 + 8;
   __shared__ __attribute__((aligned(16))) uint16_t s_g[16 * XS];      // d loss / d out rows (operand), at the end the [CLS] gradient rows
   __shared__ __attribute__((aligned(16))) uint16_t s_h[16 * HS];      // h (its zeros are the ReLU / dropout mask)
@@ -1194,11 +1194,8 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_
       const float p1 = sl_rowsum(gy[0][i] + gy[1][i]), p2 = sl_rowsum(gy[0][i] * xh[0][i] + gy[1][i] * xh[1][i]);
       if (c == 0) { s_red[(4 * g + i) * SL_NW + wave] = p1; s_red[(16 + 4 * g + i) * SL_NW + wave] = p2; }
     }
-    // gamma / beta gradients: column sums over the workgroup's rows
-    if (det) {                                            // (workgroup-uniform) wait for this workgroup's turn
-      if (tid == 0) while (__hip_atomic_load(&g_head_ticket, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != blockIdx.x) __builtin_amdgcn_s_sleep(2);
-      __syncthreads();
-    }
+    // gamma / beta gradients: column sums over the workgroup's rows, added into dgamma / dbeta -- or, with ln_part, stored as this
+    // workgroup's row of partials (the caller sums the rows in a fixed order: deterministic mode)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int m = 16 * (wave + SL_NW * j) + c;
@@ -1207,12 +1204,10 @@ __global__ __launch_bounds__(64 * SL_NW) void tfd_head_bwd_kernel(const ops_tfd_
       for (int i = 0; i < 4; ++i) { pg = __builtin_fmaf(dy[j][i], xh[j][i], pg); pb += dy[j][i]; }
       pg += __shfl_xor(pg, 16, 64); pb += __shfl_xor(pb, 16, 64);
       pg += __shfl_xor(pg, 32, 64); pb += __shfl_xor(pb, 32, 64);
-      if (g == 0 && m < hid) { unsafeAtomicAdd(la->dgamma + m, pg); unsafeAtomicAdd(la->dbeta + m, pb); }
-    }
-    if (det) {                                            // every add of this workgroup has landed before the next one starts
-      __threadfence();
-      __syncthreads();
-      if (tid == 0) __hip_atomic_store(&g_head_ticket, blockIdx.x + 1 == gridDim.x ? 0u : blockIdx.x + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      if (g == 0 && m < hid) {
+        if (la->ln_part) { SL_GLOBAL(float, la->ln_part)[((long)blockIdx.x * 2 + 0) * hid + m] = pg; SL_GLOBAL(float, la->ln_part)[((long)blockIdx.x * 2 + 1) * hid + m] = pb; }
+        else { unsafeAtomicAdd(la->dgamma + m, pg); unsafeAtomicAdd(la->dbeta + m, pb); }
+      }
     }
     sl_lds_barrier();
 #pragma unroll
@@ -1594,7 +1589,8 @@ extern "C" int ops_tfd_head_bwd(const ops_tfd_head_bwd_args* a, void* stream) {
   if ((((uintptr_t)a->Wt2 | (uintptr_t)a->Wt1 | (uintptr_t)a->a16 | (uintptr_t)a->h | (uintptr_t)a->d_a | (uintptr_t)a->dcls_rows) & 15) != 0 || ((uintptr_t)a->g & 7) != 0)
     return OPS_AMD_ERR_UNSUPPORTED;
   if (a->loss_part && (!a->alpha || !a->loss)) return OPS_AMD_ERR_INVALID_ARG;
-  hipLaunchKernelGGL(opsamd::tfd_head_bwd_kernel, dim3((unsigned)((a->B + 15) / 16)), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a, opsamd::deterministic_mode());
+  if (opsamd::deterministic_mode() && !a->ln_part) return OPS_AMD_ERR_INVALID_ARG;      // (atomics would add the workgroups in arrival order)
+  hipLaunchKernelGGL(opsamd::tfd_head_bwd_kernel, dim3((unsigned)((a->B + 15) / 16)), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
   return OPS_AMD_OK;
@@ -1626,12 +1622,3 @@ extern "C" int ops_tfd_front_bwd(const ops_tfd_front_bwd_args* a, void* stream) 
   if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
   return OPS_AMD_OK;
 }
-
-// re-arms the ticket of the head's deterministic gradient sums (a launch that faulted half way must not leave later launches waiting): called
-// when the library option "deterministic" is set
-namespace opsamd {
-void reset_head_ticket() {
-  const unsigned int zero = 0u;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_head_ticket), &zero, sizeof(zero));
-}
-}  // namespace opsamd

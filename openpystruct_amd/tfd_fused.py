@@ -679,7 +679,8 @@ class HeadFn(torch.autograd.Function):
     """The model's head on the [CLS] rows -- fc1 -> LayerNorm -> ReLU -> dropout -> fc2 (TFD:568-575) -- as one launch per direction
     (csrc/seq_layer.hip tfd_head_*_kernel; was four + four).  x16 [B S, d] bf16: the last encoder layer's output; returns [B, C] bf16.
     Backward: the gradient of the [CLS] rows goes into a persistent zero tensor of x16's shape (every other row stays zero), weight /
-    bias gradients where the shadow products send them, LayerNorm gradients straight into their `.grad`."""
+    bias gradients where the shadow products send them, LayerNorm gradients straight into their `.grad` (deterministic mode: through
+    per-workgroup partials summed in a fixed order)."""
 
     @staticmethod
     def forward(ctx, x16, model, B, S, st: _State, loss_spec=None):
@@ -758,8 +759,18 @@ class HeadFn(torch.autograd.Function):
             a.loss_sum = acc.data_ptr() if acc is not None else None
         if g2 is not None:
             a.g2, a.g_sum = g2.data_ptr(), g.data_ptr()
+        part = None
+        if _cabi.get_option("deterministic"):
+            # LayerNorm gamma / beta gradients: per-workgroup column sums, reduced in a fixed order by two jobs of the grouped
+            # weight-gradient launch (no step collecting one: here, on the stream)
+            part = torch.empty(((B + 15) // 16, 2, hid), dtype=torch.float32, device=dev)
+            a.ln_part = part.data_ptr()
         with torch.cuda.device(dev):
             _check(lib.ops_tfd_head_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_head_bwd")
+        if part is not None:
+            for k, q in enumerate((model.norm1.weight, model.norm1.bias)):
+                if not train.queue_column_sums(part[:, k, :], q.grad):
+                    q.grad.add_(part[:, k, :].sum(0))
         train.shadow_param_grads(r2, g, h)
         train.shadow_param_grads(r1, d_a, x16.view(B, S, d)[:, 0, :])       # (row-strided operand: no copy of the [CLS] rows)
         return full, None, None, None, None, None

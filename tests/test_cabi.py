@@ -26,8 +26,11 @@ def test_header_symbols_are_exported(lib):
         assert getattr(lib, name) is not None
 
 
-def test_introspection_calls(lib):
-    assert lib.ops_amd_abi_version() == 13     # 13: ops_frame_solve_batched_f64_ex (OPS_FRAME_REUSE_PLAN), ops_frame_plan_signature; 12: ops_mlp_wgrad_group_norm, OPS_ADAM_NORM_READY; 11: ops_tfd_front_args.n_order (a walked-past cursor wraps); 10: loss on the TFD head's tile, identity_act of the TFD launches, ops_physics_loss_*; 2: ops_beam_sizing_epoch_f32 takes I_last (float32) instead of I64; 3: ops_mlp_* layer blocks; 4: diffusion combine with a bf16 copy / two gradients; 5: encoder-layer launches on tiled weights; 6: head / front-end launches, column-sum jobs and 24 problems in the grouped weight-gradient launch, ln_part; 7: ops_mlp_strip_args.eval_stats; 8: ops_sizing_draw_cases_f64; 9: evaluation slots of ops_mlp_strip_args
+def test_abi_version(lib):
+    assert lib.ops_amd_abi_version() == 14 == _cabi.ABI_VERSION     # 14: ops_tfd_head_bwd_args.ln_part; 13: ops_frame_solve_batched_f64_ex (OPS_FRAME_REUSE_PLAN), ops_frame_plan_signature; 12: ops_mlp_wgrad_group_norm, OPS_ADAM_NORM_READY; 11: ops_tfd_front_args.n_order (a walked-past cursor wraps); 10: loss on the TFD head's tile, identity_act of the TFD launches, ops_physics_loss_*; 2: ops_beam_sizing_epoch_f32 takes I_last (float32) instead of I64; 3: ops_mlp_* layer blocks; 4: diffusion combine with a bf16 copy / two gradients; 5: encoder-layer launches on tiled weights; 6: head / front-end launches, column-sum jobs and 24 problems in the grouped weight-gradient launch, ln_part; 7: ops_mlp_strip_args.eval_stats; 8: ops_sizing_draw_cases_f64; 9: evaluation slots of ops_mlp_strip_args
+
+
+def test_size_and_kernel_name_introspection(lib):
     assert lib.ops_amd_max_elements() >= 100
     assert b"beam_rows_kernel<16, 7" in lib.ops_beam_solve_kernel_name(10000, 100, 0)       # default: the row-staged 16-lane kernel
     assert b"beam_rows_kernel<16, 7" in lib.ops_beam_solve_kernel_name(100000, 100, 0)
@@ -195,6 +198,21 @@ def test_residual_vjp_entry_refuses_bad_arguments(lib):
         assert call(null=k) == _cabi.ERR_INVALID_ARG, k
     assert call(Ne=0) == _cabi.ERR_INVALID_ARG and call(Ne=-1) == _cabi.ERR_INVALID_ARG and call(B=-1) == _cabi.ERR_INVALID_ARG
     assert call(B=0) == _cabi.OK and call(B=0, null=0) == _cabi.OK        # an empty batch is a no-op, checked before the pointers
+    del keep
+
+
+def test_deterministic_head_backward_refuses_a_null_ln_part(lib):
+    """Deterministic mode: the head backward's LayerNorm sums go through per-workgroup partials; without a partial buffer the launch is
+    refused before any HIP call (atomics would add the workgroups in arrival order)."""
+    keep, p = _arg_buffer()
+    a = _cabi.TfdHeadBwdArgs(B=4, S=2, d=16, hid=16, C=4, g=p, Wt2=p, Wt1=p, gamma=p, p_drop=0.0, a16=p, mean=p, rstd=p, h=p, d_a=p,
+                             dcls_rows=p, dgamma=p, dbeta=p)
+    try:
+        assert lib.ops_amd_set_option(b"deterministic", 1) == _cabi.OK and lib.ops_amd_get_option(b"deterministic") == 1
+        assert lib.ops_tfd_head_bwd(ctypes.byref(a), None) == _cabi.ERR_INVALID_ARG
+    finally:
+        lib.ops_amd_set_option(b"deterministic", 0)
+    assert lib.ops_amd_get_option(b"deterministic") == 0
     del keep
 
 

@@ -1028,6 +1028,70 @@ def test_one_launch_head_against_the_framework_ops(B, S, d, hid, C, p):
     assert _rel(full.view(B, S, d)[:, 0, :].float(), x.grad) < 1.5e-2
     assert float(full.view(B, S, d)[:, 1:, :].float().abs().max()) == 0.0 if S > 1 else True
     assert _rel(dg, gr.grad) < 1.5e-2 and _rel(db, br.grad) < 1.5e-2
+    # deterministic mode's form: every workgroup's gamma / beta column sums stored into ln_part instead of added into dgamma / dbeta --
+    # their row sums meet the same bound and equal the atomic sums to float reordering, the rest is the same bits, two launches agree
+    d_a0, full0, dg0, db0 = d_a.clone(), full.clone(), dg.clone(), db.clone()
+
+    def bwd_part():
+        part = torch.full(((B + 15) // 16, 2, hid), float("nan"), device=dev)
+        d_a.fill_(float("nan"))
+        ab.ln_part = part.data_ptr()
+        assert lib.ops_tfd_head_bwd(ctypes.byref(ab), s) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(d_a, d_a0) and torch.equal(full, full0) and torch.equal(dg, dg0) and torch.equal(db, db0)
+        return part
+    part = bwd_part()
+    assert torch.equal(part, bwd_part())
+    pg, pb = part[:, 0, :].sum(0), part[:, 1, :].sum(0)
+    assert _rel(pg, gr.grad) < 1.5e-2 and _rel(pb, br.grad) < 1.5e-2
+    assert bool(((pg - dg).abs() <= 1e-5 * part[:, 0, :].abs().sum(0) + 1e-12).all())
+    assert bool(((pb - db).abs() <= 1e-5 * part[:, 1, :].abs().sum(0) + 1e-12).all())
+
+
+def test_deterministic_head_backward_on_two_streams_at_once():
+    """Deterministic mode: head backward launches of two problems queued on two streams with no sync between them share no state (each
+    workgroup stores its LayerNorm column sums into its own launch's ln_part): each result is the bits of its single-stream launch."""
+    import ctypes
+    from openpystruct_amd import _cabi
+    lib = _cabi.load()
+    dev = torch.device(DEV)
+    bf = dict(dtype=torch.bfloat16, device=dev)
+
+    def problem(B, S, d, hid, C, seed):
+        g = torch.Generator().manual_seed(seed)
+        W1t, W2t = _tiled_pair(lib, (torch.randn(hid, d, generator=g) * 0.1).to(dev))[1], _tiled_pair(lib, (torch.randn(C, hid, generator=g) * 0.1).to(dev))[1]
+        a16, h = torch.randn(B, hid, generator=g).to(**bf), torch.relu(torch.randn(B, hid, generator=g)).to(**bf)
+        mean, rstd = a16.float().mean(1), (a16.float().var(1, unbiased=False) + 1e-5).rsqrt()
+        go, gamma = (torch.randn(B, C, generator=g) * 0.1).to(**bf), (1 + 0.1 * torch.randn(hid, generator=g)).to(dev)
+        out = dict(d_a=torch.empty(B, hid, **bf), full=torch.zeros(B * S, d, **bf), part=torch.empty((B + 15) // 16, 2, hid, device=dev),
+                   dg=torch.zeros(hid, device=dev), db=torch.zeros(hid, device=dev))
+        ab = _cabi.TfdHeadBwdArgs(B=B, S=S, d=d, hid=hid, C=C, g=go.data_ptr(), Wt2=W2t.data_ptr(), Wt1=W1t.data_ptr(), gamma=gamma.data_ptr(),
+                                  p_drop=0.1, a16=a16.data_ptr(), mean=mean.data_ptr(), rstd=rstd.data_ptr(), h=h.data_ptr(), d_a=out["d_a"].data_ptr(),
+                                  dcls_rows=out["full"].data_ptr(), dgamma=out["dg"].data_ptr(), dbeta=out["db"].data_ptr(), ln_part=out["part"].data_ptr())
+        return ab, out, (W1t, W2t, a16, h, mean, rstd, go, gamma)
+
+    probs = [problem(512, 7, 120, 256, 100, 1), problem(37, 3, 64, 72, 12, 2)]
+    try:
+        _cabi.set_option("deterministic", 1)
+        ref = []
+        for ab, out, _ in probs:
+            assert lib.ops_tfd_head_bwd(ctypes.byref(ab), torch.cuda.current_stream().cuda_stream) == 0
+            torch.cuda.synchronize()
+            ref.append({k: v.clone() for k, v in out.items()})
+            out["d_a"].fill_(float("nan")); out["part"].fill_(float("nan")); out["full"].zero_()
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        for st in streams:
+            st.wait_stream(torch.cuda.current_stream())
+        for _ in range(4):
+            for (ab, _, _), st in zip(probs, streams):
+                assert lib.ops_tfd_head_bwd(ctypes.byref(ab), st.cuda_stream) == 0
+        torch.cuda.synchronize()
+    finally:
+        _cabi.set_option("deterministic", 0)
+    for (_, out, _), r in zip(probs, ref):
+        for k in r:
+            assert torch.equal(out[k], r[k]), k
+    assert all(float(r["dg"].abs().max()) == 0.0 and float(r["db"].abs().max()) == 0.0 for r in ref)
 
 
 @pytest.mark.parametrize("B,Nc,d,hid", [(512, 6, 120, 256), (37, 6, 120, 256), (5, 3, 64, 72)])
@@ -1155,8 +1219,9 @@ def test_grouped_launch_column_sum_jobs():
 
 def test_deterministic_mode_makes_the_tfd_step_bit_reproducible():
     """Library option "deterministic" (r06): one row split per weight-gradient product, one workgroup per column-sum strip and for the [CLS] sums,
-    the head's LayerNorm sums in workgroup order -- two runs of one seed then give the SAME BITS (default mode: float atomics land in arrival
-    order and two runs sit on nearby trajectories, ~1e-4 apart), and the same trajectory as the default mode to that spread."""
+    the head's LayerNorm sums as per-workgroup partials that a column-sum job adds up in a fixed order -- two runs of one seed then give the
+    SAME BITS (default mode: float atomics land in arrival order and two runs sit on nearby trajectories, ~1e-4 apart), and the same
+    trajectory as the default mode to that spread."""
     from openpystruct_amd import _cabi, dataprep, sizing, train
     rec = sizing.generate_dataset(1800, sizing.SizingConfig(max_e=30), "cuda", seed=11)
     d = dataprep.prepare(rec, kind="tfd", seed=0, device="cuda")
