@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI (include/openpystruct_amd.h).
+"""ctypes binding of the C ABI, read from include/openpystruct_amd.h: the header is the one place where the entry points, their
+argument structs and the OPS_* constants are written down; nothing here repeats a field, an argument list or a value.
 
 The product path has NO CPU fallback: if the HIP shared library is missing or cannot be
 loaded this module raises, loudly, instead of computing anything elsewhere.
@@ -7,246 +8,142 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
+import types
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-FRAME_REUSE_PLAN = 1     # include/openpystruct_amd.h OPS_FRAME_REUSE_PLAN
-ABI_VERSION = 14     # include/openpystruct_amd.h OPS_AMD_ABI_VERSION
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd.h")
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
-
-# every symbol include/openpystruct_amd.h declares
-EXPORTS = (
-    "ops_beam_solve_batched_f64",
-    "ops_beam_solve_forces_f64",
-    "ops_beam_solve_vjp_f64",
-    "ops_beam_solve_forces_f32",
-    "ops_beam_sizing_step_vm32_f32",
-    "ops_sizing_schedule_f32",
-    "ops_sizing_draw_cases_f64",
-    "ops_beam_sizing_epoch_f32",
-    "ops_beam_sizing_step_f32",
-    "ops_beam_residual_f64",
-    "ops_beam_residual_vjp_f64",
-    "ops_frame_solve_batched_f64",
-    "ops_frame_workspace_bytes",
-    "ops_frame_solve_batched_f64_ex",
-    "ops_frame_plan_signature",
-    "ops_stencil3_bn1_fwd_f32",
-    "ops_stencil3_bn1_bwd_f32",
-    "ops_stencil3_bn1_workspace_bytes",
-    "ops_flat_clip_adam_step_f32",
-    "ops_flat_adam_workspace_bytes",
-    "ops_surrogate_loss_grad_f32",
-    "ops_surrogate_loss_workspace_bytes",
-    "ops_amd_set_option",
-    "ops_amd_get_option",
-    "ops_amd_max_elements",
-    "ops_amd_abi_version",
-    "ops_gather_rows_noise_f32",
-    "ops_fused_bn_act_fwd",
-    "ops_fused_bn_act_bwd",
-    "ops_amd_last_error",
-    "ops_beam_solve_kernel_name",
-    "ops_mlp_strip_launch",
-    "ops_mlp_spart_doubles",
-    "ops_mlp_wgrad_group",
-    "ops_mlp_wgrad_group_norm",
-    "ops_mlp_gather_noise_repack",
-    "ops_mlp_repack_weights",
-    "ops_flat_clip_adam_step_repack_f32",
-    "ops_mlp_gather_noise",
-    "ops_mlp_loss_workspace_bytes",
-    "ops_seq_attention_fwd",
-    "ops_seq_attention_bwd",
-    "ops_dropout_add_layernorm_fwd",
-    "ops_dropout_add_layernorm_bwd",
-    "ops_act_dropout_fwd",
-    "ops_act_dropout_bwd",
-    "ops_linear_wgrad_accumulate",
-    "ops_linear_wgrad_accumulate_group",
-    "ops_diffusion_noise",
-    "ops_diffusion_combine_fwd",
-    "ops_diffusion_combine_bwd",
-    "ops_hbm_copy16",
-    "ops_tfd_encoder_layer_fwd",
-    "ops_tfd_encoder_layer_pair_fwd",
-    "ops_tfd_encoder_layer_pair_bwd",
-    "ops_diffusion_noise_draw",
-    "ops_surrogate_loss_grad_sum_f32",
-    "ops_gather_rows_noise_targets_f32",
-    "ops_tfd_encoder_layer_bwd",
-    "ops_tfd_head_fwd",
-    "ops_tfd_head_bwd",
-    "ops_tfd_front_fwd",
-    "ops_tfd_front_bwd",
-    "ops_physics_loss_part_doubles",
-    "ops_physics_loss_fwd",
-    "ops_physics_loss_bwd",
-    "ops_bayes_sample_f32",
-    "ops_bayes_grad_fold_f32",
-    "ops_bayes_mlp_mc_f32",
-    "ops_mc_moments_f32",
-)
-
-OK, ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = 0, 1, 2, 3
-FIX_UY, FIX_RZ = 1, 2
-
-_lib = None
-
-
-# Bayesian layers of the BTFD / BTFDM surrogates (include/openpystruct_amd.h, csrc/bayes_mlp.hip)
-BAYES_MAX_LAYERS = 8
-BAYES_EPS_DRAW, BAYES_EPS_WRITE, BAYES_EPS_READ = 0, 1, 2
-BAYES_MC_NONE, BAYES_MC_DIFFUSION, BAYES_MC_HEAD = 0, 1, 2
-BAYES_MC_MAX_KH, BAYES_MC_MAX_K, BAYES_MC_MAX_H = 1024, 256, 768
-
-
-class BayesLayer(ctypes.Structure):
-    """Mirror of `ops_bayes_layer`."""
-    _fields_ = [("out_f", ctypes.c_int32), ("in_f", ctypes.c_int32)] + [(n, ctypes.c_void_p) for n in (
-        "w_mu", "w_ls", "b_mu", "b_ls", "w", "b", "w16", "w_eps", "b_eps", "dw", "db", "d_wmu", "d_wls", "d_bmu", "d_bls")]
-
-
-class BayesMcArgs(ctypes.Structure):
-    """Mirror of `ops_bayes_mc_args`."""
-    _vp, _i, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    _fields_ = [("S", _i), ("rows_per_sample", _i), ("K", _i), ("H", _i), ("N", _i), ("x", _vp), ("ldx", _i),
-                ("w1_mu", _vp), ("w1_ls", _vp), ("b1_mu", _vp), ("b1_ls", _vp), ("ln_g", _vp), ("ln_b", _vp), ("ln_eps", _f), ("slope", _f),
-                ("w2_mu", _vp), ("w2_ls", _vp), ("b2_mu", _vp), ("b2_ls", _vp), ("seed", ctypes.c_ulonglong), ("epilogue", _i), ("y", _vp),
-                ("Nc", _i), ("T", _i), ("acp", _vp), ("row_base", ctypes.c_longlong), ("cls", _vp), ("pe", _vp), ("t_out", _vp), ("xeps_out", _vp), ("out_scale", _vp), ("eps_out", _vp), ("h_ws", _vp), ("xn_ws", _vp)]
-
-
-class SizingParams(ctypes.Structure):
-    """Mirror of `ops_sizing_params` (include/openpystruct_amd.h)."""
-    _fields_ = [(n, ctypes.c_double) for n in (
-        "E", "G", "alpha_moment", "alpha_shear", "lr", "gamma", "beta1", "beta2", "adam_eps",
-        "clamp_min", "bend_eps", "area_coef", "tolerance")] + [("patience", ctypes.c_int32), ("max_epochs", ctypes.c_int32)]
-
-
-# layer blocks of the PINN training step (include/openpystruct_amd.h, csrc/mlp_block.hip)
-MLP_MAX_ROWS = 128
-MLP_TAIL_NONE, MLP_TAIL_ACT_DROP, MLP_TAIL_BN_ACT_DROP, MLP_TAIL_BN = 0, 1, 2, 3
-MLP_TAIL_BWD_ACT_DROP, MLP_TAIL_BWD_BN, MLP_TAIL_BWD_BN_ACT_DROP, MLP_TAIL_LOSS = 4, 5, 6, 7
-MLP_ADD_NONE, MLP_ADD_FWD_BLOCK, MLP_ADD_BWD_BLOCK = 0, 1, 2
-MLP_SIDE_NONE, MLP_SIDE_FWD_STENCIL_STATS, MLP_SIDE_BWD_STENCIL_SUMS = 0, 1, 2
-MLP_MAX_WGRAD = 8
-MLP_MAX_REPACK = 16
-MLP_MAX_NORM_RANGES = 32      # OPS_MLP_MAX_NORM_RANGES
-FLAT_ADAM_MAX_PARTS = 1024    # OPS_FLAT_ADAM_MAX_PARTS
-ADAM_NORM_READY = 4           # OPS_ADAM_NORM_READY
-
-
-class MlpStripArgs(ctypes.Structure):
-    """Mirror of `ops_mlp_strip_args`."""
-    _vp, _i, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    _fields_ = [("B", _i), ("N", _i), ("K", _i), ("tail", _i), ("add_mode", _i), ("side", _i),
-                ("A", _vp), ("lda", _i), ("W", _vp), ("ldw", _i), ("bias", _vp),
-                ("Y", _vp), ("ldy", _i), ("Yt", _vp),
-                ("gamma", _vp), ("beta", _vp), ("eps", _f), ("momentum", _f),
-                ("running_mean", _vp), ("running_var", _vp), ("num_batches_tracked", _vp),
-                ("mean", _vp), ("rstd", _vp), ("Zt", _vp), ("Yref_t", _vp),
-                ("slope", _f), ("p_drop", _f), ("seed", ctypes.c_ulonglong), ("call_counter", _vp),
-                ("dgamma", _vp), ("dbeta", _vp), ("dbias", _vp),
-                ("Ot", _vp), ("No", _i), ("dZt", _vp),
-                ("conv_w", _vp), ("conv_b", _vp), ("sgamma", _vp), ("sbeta", _vp), ("seps", _f), ("smomentum", _f),
-                ("srunning_mean", _vp), ("srunning_var", _vp), ("snum_batches_tracked", _vp),
-                ("ssave", _vp), ("spart", _vp), ("sdparams", _vp),
-                ("P", _vp), ("ldp", _i), ("targets_t", _vp), ("nI", _i), ("nD", _i), ("alpha", _vp), ("alpha0", _f),
-                ("min_constraint", _vp), ("max_constraint", _vp), ("box_weight", _f), ("rel_penalty", _f), ("loss_ws", _vp), ("loss_finish_rows", _i), ("loss_C", _i), ("loss", _vp), ("loss_sum", _vp),
-                ("eval_stats", _i), ("n_slots", _i), ("slot_total_rows", _i), ("slot_stride", ctypes.c_int64)]
-
-
-class MlpWgradProblem(ctypes.Structure):
-    """Mirror of `ops_mlp_wgrad_problem`."""
-    _fields_ = [("At", ctypes.c_void_p), ("Bt", ctypes.c_void_p), ("out", ctypes.c_void_p), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
-                ("ldo", ctypes.c_int32)]
-
-
-class WgradProblem(ctypes.Structure):
-    """Mirror of `ops_wgrad_problem`."""
-    _fields_ = [("T", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("dY", ctypes.c_void_p), ("X", ctypes.c_void_p),
-                ("dW", ctypes.c_void_p), ("dbias", ctypes.c_void_p), ("ldy", ctypes.c_int32), ("ldx", ctypes.c_int32)]
-
-
-class TfdLayerArgs(ctypes.Structure):
-    """Mirror of `ops_tfd_layer_args`."""
-    _vp, _i, _f, _u = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_ulonglong
-    _fields_ = [("Bn", _i), ("S", _i), ("H", _i), ("dh", _i), ("d", _i), ("ff", _i), ("x32", _vp),
-                ("W_in", _vp), ("b_in", _vp), ("W_out", _vp), ("b_out", _vp), ("W_1", _vp), ("b_1", _vp), ("W_2", _vp), ("b_2", _vp),
-                ("gamma1", _vp), ("beta1", _vp), ("eps1", _f), ("gamma2", _vp), ("beta2", _vp), ("eps2", _f),
-                ("p_attn", _f), ("p_1", _f), ("p_act", _f), ("p_2", _f),
-                ("seed_attn", _u), ("seed_1", _u), ("seed_act", _u), ("seed_2", _u), ("counter", _vp), ("used_call", _vp),
-                ("qkv", _vp), ("ctx", _vp), ("z1", _vp), ("mean1", _vp), ("rstd1", _vp), ("y1_16", _vp), ("u", _vp), ("h", _vp),
-                ("z2", _vp), ("mean2", _vp), ("rstd2", _vp), ("y32", _vp), ("y16", _vp), ("trace", _vp), ("identity_act", _i)]
-
-
-class TfdLayerBwdArgs(ctypes.Structure):
-    """Mirror of `ops_tfd_layer_bwd_args`."""
-    _vp, _i, _f, _u = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_ulonglong
-    _fields_ = [("Bn", _i), ("S", _i), ("H", _i), ("dh", _i), ("d", _i), ("ff", _i), ("g32", _vp), ("g16", _vp),
-                ("Wt_in", _vp), ("Wt_out", _vp), ("Wt_1", _vp), ("Wt_2", _vp), ("gamma1", _vp), ("gamma2", _vp),
-                ("p_attn", _f), ("p_1", _f), ("p_act", _f), ("p_2", _f),
-                ("seed_attn", _u), ("seed_1", _u), ("seed_act", _u), ("seed_2", _u), ("used_call", _vp),
-                ("qkv", _vp), ("z1", _vp), ("mean1", _vp), ("rstd1", _vp), ("u", _vp), ("z2", _vp), ("mean2", _vp), ("rstd2", _vp),
-                ("d_f", _vp), ("d_u", _vp), ("d_a", _vp), ("dqkv", _vp), ("dx32", _vp),
-                ("dgamma1", _vp), ("dbeta1", _vp), ("dgamma2", _vp), ("dbeta2", _vp), ("trace", _vp), ("ln_part", _vp), ("identity_act", _i)]
-
-
-class TfdHeadArgs(ctypes.Structure):
-    """Mirror of `ops_tfd_head_args`."""
-    _vp, _i, _f, _u = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_ulonglong
-    _fields_ = [("B", _i), ("S", _i), ("d", _i), ("hid", _i), ("C", _i), ("y16", _vp), ("W1", _vp), ("b1", _vp), ("gamma", _vp), ("beta", _vp),
-                ("eps", _f), ("W2", _vp), ("b2", _vp), ("p_drop", _f), ("seed", _u), ("counter", _vp), ("used_call", _vp),
-                ("a16", _vp), ("mean", _vp), ("rstd", _vp), ("h", _vp), ("out", _vp),
-                ("targets", _vp), ("grad", _vp), ("loss_part", _vp), ("alpha", _vp), ("min_constraint", _vp), ("max_constraint", _vp),
-                ("box_weight", _f), ("identity_act", _i), ("target_rows", _vp)]
-
-
-class TfdHeadBwdArgs(ctypes.Structure):
-    """Mirror of `ops_tfd_head_bwd_args`."""
-    _vp, _i, _f = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float
-    _fields_ = [("B", _i), ("S", _i), ("d", _i), ("hid", _i), ("C", _i), ("g", _vp), ("Wt2", _vp), ("Wt1", _vp), ("gamma", _vp), ("p_drop", _f),
-                ("a16", _vp), ("mean", _vp), ("rstd", _vp), ("h", _vp), ("d_a", _vp), ("dcls_rows", _vp), ("dgamma", _vp), ("dbeta", _vp),
-                ("loss_part", _vp), ("alpha", _vp), ("alpha0", _f), ("box_weight", _f), ("loss", _vp), ("loss_sum", _vp), ("g2", _vp), ("g_sum", _vp),
-                ("ln_part", _vp)]
-
-
-class PhysicsLossArgs(ctypes.Structure):
-    """Mirror of `ops_physics_loss_args`."""
-    _vp, _i, _f, _d = ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_double
-    _fields_ = [("B", _i), ("Ne", _i), ("preds", _vp), ("preds_bf16", _i), ("ldp", _i), ("I_scale", _vp), ("I_mean", _vp), ("I_min", _f),
-                ("v_rec", _vp), ("t_rec", _vp), ("v_scale", _vp), ("v_mean", _vp), ("t_scale", _vp), ("t_mean", _vp), ("rows", _vp),
-                ("Fy", _vp), ("x", _vp), ("fix", _vp), ("E", _d), ("wy", _d), ("weight", _f), ("ev", _vp), ("et", _vp), ("part", _vp),
-                ("value", _vp), ("value_sum", _vp), ("dpreds", _vp)]
-
-
-class TfdFrontArgs(ctypes.Structure):
-    """Mirror of `ops_tfd_front_args`."""
-    _vp, _i, _u = ctypes.c_void_p, ctypes.c_int32, ctypes.c_ulonglong
-    _fields_ = [("B", _i), ("Nc", _i), ("d", _i), ("hid", _i), ("T", _i), ("x", _vp), ("alpha_cumprod", _vp), ("seed", _u), ("counter", _vp),
-                ("W0", _vp), ("b0", _vp), ("W2", _vp), ("b2", _vp), ("cls", _vp), ("pe", _vp),
-                ("xn16", _vp), ("h", _vp), ("sa", _vp), ("sb", _vp), ("z", _vp), ("z16", _vp), ("t_out", _vp), ("eps_out", _vp), ("identity_act", _i),
-                ("src", _vp), ("order", _vp), ("cursor", _vp), ("idx_out", _vp), ("sigma", _vp), ("in_seed", _u), ("n_order", ctypes.c_longlong)]
-
-
-class TfdFrontBwdArgs(ctypes.Structure):
-    """Mirror of `ops_tfd_front_bwd_args`."""
-    _vp, _i = ctypes.c_void_p, ctypes.c_int32
-    _fields_ = [("B", _i), ("Nc", _i), ("d", _i), ("hid", _i), ("g32", _vp), ("g16", _vp), ("sa", _vp), ("sb", _vp), ("h", _vp), ("Wt2", _vp),
-                ("dm", _vp), ("d_h", _vp), ("dcls", _vp)]
-
-
-WGRAD_MAX_GROUP = 24
-
-
-class MlpRepackEntry(ctypes.Structure):
-    """Mirror of `ops_mlp_repack_entry`."""
-    _fields_ = [("W", ctypes.c_void_p), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("Wp", ctypes.c_void_p), ("ldw", ctypes.c_int32),
-                ("Wtp", ctypes.c_void_p), ("ldwt", ctypes.c_int32)]
 
 
 class ExtensionMissingError(RuntimeError):
     pass
+
+
+# Every type word the header may use.  By value: the ctypes type of the same name and width (None: only behind a pointer).
+# Pointers: `char*` is c_char_p, a pointer to a struct of the header POINTER(that Structure), every other pointer at any depth
+# c_void_p -- the one argtype that takes what the callers pass: tensor.data_ptr() integers, None, ctypes.byref(...) and ctypes arrays.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "long": ctypes.c_long,
+            "long long": ctypes.c_longlong, "unsigned": ctypes.c_uint, "unsigned long long": ctypes.c_ulonglong,
+            "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double,
+            "void": None, "char": None, "uint8_t": None}
+_DECLARATION = re.compile(r"\s*(?:typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;"        # typedef struct NAME { fields } NAME;
+                          r"|([\w\s*]+?)\b(ops_\w+)\s*\(([^()]*)\)\s*;)")                      # RET ops_xxx(ARGS);
+_INTEGER = re.compile(r"(0[xX][0-9a-fA-F]+|[0-9]+)[uU]?")
+
+
+def _ctype(base: str, depth: int, structs: dict, where: str):
+    """ctypes type of `depth` pointers to the type named by the words `base`."""
+    if base not in _SCALARS and base not in structs:
+        raise ValueError(f"{where}: unknown type {base!r}")
+    if depth == 0:
+        if _SCALARS.get(base) is None:
+            raise ValueError(f"{where}: {base!r} by value")
+        return _SCALARS[base]
+    if depth == 1 and base == "char":
+        return ctypes.c_char_p
+    return ctypes.POINTER(structs[base]) if depth == 1 and base in structs else ctypes.c_void_p
+
+
+def _declarators(text: str, structs: dict, where: str, named: bool = True) -> list:
+    """(name, ctypes type) of every declarator of `TYPE [*]a, [*]b`; named=False: a bare type (the return type of a prototype)."""
+    out, base = [], None
+    for piece in text.split(","):
+        words = piece.replace("*", " ").split()
+        if not all(map(str.isidentifier, words)):       # an array, a bit field, a function pointer, an initialiser
+            raise ValueError(f"{where}: cannot read {text.strip()!r}")
+        words = [w for w in words if w != "const"]
+        name = words.pop() if named and words else None
+        if named and (name is None or name in _SCALARS or name in structs):
+            raise ValueError(f"{where}: no name in {text.strip()!r}")
+        if base is None:
+            base = " ".join(words)
+        elif words:                                     # the later declarators of a line are stars and a name
+            raise ValueError(f"{where}: cannot read {text.strip()!r}")
+        out.append((name, _ctype(base, piece.count("*"), structs, where)))
+    return out
+
+
+def read_header(text: str) -> types.SimpleNamespace:
+    """Parse the text of a C header of the shape of include/openpystruct_amd.h into
+         defines    {OPS_NAME: int}                        every `#define OPS_... <integer literal>`
+         structs    {c_name: ctypes.Structure subclass}    every `typedef struct NAME { ... } NAME;`
+         functions  {c_name: (restype, [argtypes])}        every prototype `RET ops_xxx(ARGS);`
+    Comments, the other preprocessor lines and the `extern "C"` braces are dropped; every character that remains must belong to one
+    of the two declaration forms and every type word must be known, else ValueError with the offending text -- nothing is skipped."""
+    out = types.SimpleNamespace(defines={}, structs={}, functions={})
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    if "\\\n" in text:
+        raise ValueError("line continuation in the header")
+    code = []
+    for line in text.split("\n"):
+        if not line.lstrip().startswith("#"):
+            code.append(line)
+            continue
+        m = re.match(r"\s*#\s*define\s+(OPS_\w+)(.*)", line)
+        if m:
+            if not _INTEGER.fullmatch(m.group(2).strip()):
+                raise ValueError(f"#define {m.group(1)}: not an integer literal: {m.group(2).strip()!r}")
+            out.defines[m.group(1)] = int(m.group(2).strip().rstrip("uU"), 0)
+    text = "\n".join(code)
+    m = re.fullmatch(r'\s*extern\s+"C"\s*\{(.*)\}\s*', text, flags=re.S)
+    text = (m.group(1) if m else text).rstrip()
+    pos = 0
+    while pos < len(text):
+        m = _DECLARATION.match(text, pos)
+        if not m:
+            raise ValueError(f"cannot read the header at: {text[pos:pos + 120].strip()!r}")
+        pos = m.end()
+        tag, body, name, ret, func, args = m.groups()
+        if func is None:
+            if tag != name or name in out.structs:
+                raise ValueError(f"struct {tag}: typedef'd as {name}" if tag != name else f"struct {name} declared twice")
+            fields = [f for decl in body.split(";") if decl.strip() for f in _declarators(decl, out.structs, f"struct {name}")]
+            camel = "".join(w.capitalize() for w in name[4 * name.startswith("ops_"):].split("_"))      # ops_tfd_head_bwd_args -> TfdHeadBwdArgs
+            out.structs[name] = type(camel, (ctypes.Structure,), {"_fields_": fields})
+        else:
+            if func in out.functions:
+                raise ValueError(f"{func} declared twice")
+            params = [] if args.strip() == "void" else [_declarators(a, out.structs, func)[0][1] for a in args.split(",")]
+            restype = None if ret.split() == ["void"] else _declarators(ret, out.structs, func, named=False)[0][1]
+            out.functions[func] = (restype, params)
+    return out
+
+
+def _read_abi() -> types.SimpleNamespace:
+    try:
+        with open(HEADER_PATH) as f:
+            return read_header(f.read())
+    except OSError as e:
+        raise ExtensionMissingError(f"{HEADER_PATH} not readable ({e}): the ctypes binding is derived from the C header") from e
+
+
+_abi = _read_abi()
+EXPORTS = tuple(_abi.functions)     # every symbol include/openpystruct_amd.h declares
+_struct = _abi.structs.__getitem__
+SizingParams = _struct("ops_sizing_params")
+PhysicsLossArgs = _struct("ops_physics_loss_args")
+MlpStripArgs = _struct("ops_mlp_strip_args")
+MlpWgradProblem = _struct("ops_mlp_wgrad_problem")
+MlpRepackEntry = _struct("ops_mlp_repack_entry")
+WgradProblem = _struct("ops_wgrad_problem")
+TfdLayerArgs = _struct("ops_tfd_layer_args")
+TfdLayerBwdArgs = _struct("ops_tfd_layer_bwd_args")
+TfdHeadArgs = _struct("ops_tfd_head_args")
+TfdHeadBwdArgs = _struct("ops_tfd_head_bwd_args")
+TfdFrontArgs = _struct("ops_tfd_front_args")
+TfdFrontBwdArgs = _struct("ops_tfd_front_bwd_args")
+BayesLayer = _struct("ops_bayes_layer")
+BayesMcArgs = _struct("ops_bayes_mc_args")
+# every OPS_AMD_X / OPS_X of the header as X: OK, ERR_*, FIX_*, ABI_VERSION, FRAME_REUSE_PLAN, MLP_*, BAYES_*, WGRAD_MAX_GROUP, ADAM_*, ...
+for _name, _value in _abi.defines.items():
+    _short = _name[len("OPS_AMD_"):] if _name.startswith("OPS_AMD_") else _name[len("OPS_"):]
+    if _short in globals():
+        raise ValueError(f"{HEADER_PATH}: {_name} collides with _cabi.{_short}")
+    globals()[_short] = _value
+
+_lib = None
 
 
 def load():
@@ -263,158 +160,25 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise ExtensionMissingError(f"cannot load {LIB_PATH}: {e}") from e
-    vp, lg, it = ctypes.c_void_p, ctypes.c_long, ctypes.c_int
-    f = lib.ops_beam_solve_batched_f64
-    f.restype = it
-    f.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, vp, it, vp]
-    vj = lib.ops_beam_solve_vjp_f64
-    vj.restype = it
-    vj.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg] + [vp] * 11
-    ff = lib.ops_beam_solve_forces_f64
-    ff.restype = it
-    ff.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg, vp, vp, vp, vp, it, vp]
-    lib.ops_beam_solve_forces_f32.restype = it
-    lib.ops_beam_solve_forces_f32.argtypes = ff.argtypes
-    lib.ops_beam_sizing_step_vm32_f32.restype = it
-    lib.ops_beam_sizing_step_vm32_f32.argtypes = [it, it] + [vp] * 11 + [ctypes.POINTER(SizingParams), vp, vp]
-    lib.ops_sizing_schedule_f32.restype = None
-    lib.ops_sizing_schedule_f32.argtypes = [ctypes.POINTER(SizingParams), vp]
-    lib.ops_sizing_draw_cases_f64.restype = it
-    _ull, _db = ctypes.c_ulonglong, ctypes.c_double
-    lib.ops_sizing_draw_cases_f64.argtypes = [lg, _ull, _ull, it, it, it, it, vp, it, _db, _db, _db, _db, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_beam_sizing_epoch_f32.restype = it
-    lib.ops_beam_sizing_epoch_f32.argtypes = [it, it, vp, lg, vp, lg, vp, lg, vp, lg, vp, lg] + [vp] * 9 + [ctypes.POINTER(SizingParams), vp, vp, it, vp]
-    g = lib.ops_beam_sizing_step_f32
-    g.restype = it
-    g.argtypes = [it, it] + [vp] * 13 + [ctypes.POINTER(SizingParams), vp]
-    r = lib.ops_beam_residual_f64
-    r.restype = it
-    r.argtypes = [it, it, vp, lg, vp, lg, vp, vp, lg, vp, vp, lg, vp, vp, vp, vp, vp]
-    rj = lib.ops_beam_residual_vjp_f64
-    rj.restype = it
-    rj.argtypes = [it, it, vp, lg, vp, lg, vp, vp, lg] + [vp] * 10
-    lib.ops_tfd_encoder_layer_fwd.restype = it
-    lib.ops_tfd_encoder_layer_fwd.argtypes = [ctypes.POINTER(TfdLayerArgs), vp]
-    lib.ops_tfd_encoder_layer_pair_fwd.restype = it
-    lib.ops_tfd_encoder_layer_pair_fwd.argtypes = [ctypes.POINTER(TfdLayerArgs), ctypes.POINTER(TfdLayerArgs), vp]
-    lib.ops_tfd_encoder_layer_pair_bwd.restype = it
-    lib.ops_tfd_encoder_layer_pair_bwd.argtypes = [ctypes.POINTER(TfdLayerBwdArgs), ctypes.POINTER(TfdLayerBwdArgs), vp]
-    lib.ops_tfd_encoder_layer_bwd.restype = it
-    lib.ops_tfd_encoder_layer_bwd.argtypes = [ctypes.POINTER(TfdLayerBwdArgs), vp]
-    lib.ops_tfd_head_fwd.restype = it
-    lib.ops_tfd_head_fwd.argtypes = [ctypes.POINTER(TfdHeadArgs), vp]
-    lib.ops_tfd_head_bwd.restype = it
-    lib.ops_tfd_head_bwd.argtypes = [ctypes.POINTER(TfdHeadBwdArgs), vp]
-    lib.ops_physics_loss_part_doubles.restype = ctypes.c_size_t
-    lib.ops_physics_loss_part_doubles.argtypes = [it, it]
-    lib.ops_physics_loss_fwd.restype = it
-    lib.ops_physics_loss_fwd.argtypes = [ctypes.POINTER(PhysicsLossArgs), vp]
-    lib.ops_physics_loss_bwd.restype = it
-    lib.ops_physics_loss_bwd.argtypes = [ctypes.POINTER(PhysicsLossArgs), vp]
-    lib.ops_tfd_front_fwd.restype = it
-    lib.ops_tfd_front_fwd.argtypes = [ctypes.POINTER(TfdFrontArgs), vp]
-    lib.ops_tfd_front_bwd.restype = it
-    lib.ops_tfd_front_bwd.argtypes = [ctypes.POINTER(TfdFrontBwdArgs), vp]
-    lib.ops_hbm_copy16.restype = it
-    lib.ops_hbm_copy16.argtypes = [vp, vp, ctypes.c_size_t, it, vp]
-    fr = lib.ops_frame_solve_batched_f64
-    fr.restype = it
-    fr.argtypes = [it] * 5 + [vp] * 8 + [lg] + [vp] * 6 + [ctypes.c_size_t, vp]
-    frx = lib.ops_frame_solve_batched_f64_ex
-    frx.restype = it
-    frx.argtypes = [it] * 5 + [vp] * 8 + [lg] + [vp] * 6 + [ctypes.c_size_t, vp, ctypes.c_uint]
-    lib.ops_frame_plan_signature.restype = lg
-    lib.ops_frame_plan_signature.argtypes = [it, it, it]
-    lib.ops_frame_workspace_bytes.restype = ctypes.c_size_t
-    lib.ops_frame_workspace_bytes.argtypes = [it, it, it]
-    fl = ctypes.c_float
-    lib.ops_stencil3_bn1_fwd_f32.restype = it
-    lib.ops_stencil3_bn1_fwd_f32.argtypes = [it, it, vp, vp, vp, vp, vp, fl, fl, it, vp, vp, vp, vp, it, vp, vp, vp]
-    lib.ops_stencil3_bn1_bwd_f32.restype = it
-    lib.ops_stencil3_bn1_bwd_f32.argtypes = [it, it, vp, vp, it, vp, vp, vp, vp, it, vp, vp, vp, vp]
-    lib.ops_stencil3_bn1_workspace_bytes.restype = ctypes.c_size_t
-    lib.ops_flat_clip_adam_step_f32.restype = it
-    lib.ops_flat_clip_adam_step_f32.argtypes = [lg, vp, vp, vp, vp, vp, vp, fl, fl, fl, fl, fl, fl, it, vp, vp, vp]
-    lib.ops_flat_adam_workspace_bytes.restype = ctypes.c_size_t
-    lib.ops_surrogate_loss_grad_f32.restype = it
-    lib.ops_surrogate_loss_grad_f32.argtypes = [it, it, it, it, vp, it, vp, vp, fl, vp, vp, fl, fl, vp, vp, vp, vp]
-    lib.ops_surrogate_loss_grad_sum_f32.restype = it
-    lib.ops_surrogate_loss_grad_sum_f32.argtypes = [it, it, it, it, vp, it, vp, vp, fl, vp, vp, fl, fl, vp, vp, vp, vp, vp]
-    lib.ops_surrogate_loss_workspace_bytes.restype = ctypes.c_size_t
-    ull = ctypes.c_ulonglong
-    lib.ops_fused_bn_act_fwd.restype = it
-    lib.ops_fused_bn_act_fwd.argtypes = [it, it, vp, vp, vp, it, vp, vp, fl, fl, it, vp, vp, vp, fl, it, fl, ull, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_gather_rows_noise_f32.restype = it
-    lib.ops_gather_rows_noise_f32.argtypes = [it, lg, vp, vp, vp, ull, vp, vp, it, vp]
-    lib.ops_gather_rows_noise_targets_f32.restype = it
-    lib.ops_gather_rows_noise_targets_f32.argtypes = [it, lg, vp, vp, vp, ull, vp, vp, it, vp, it, vp, vp]
-    lib.ops_fused_bn_act_bwd.restype = it
-    lib.ops_fused_bn_act_bwd.argtypes = [it, it, vp, it, vp, vp, vp, vp, vp, fl, it, fl, vp, vp, vp, vp, vp]
-    lib.ops_amd_set_option.restype = it
-    lib.ops_amd_set_option.argtypes = [ctypes.c_char_p, lg]
-    lib.ops_amd_get_option.restype = lg
-    lib.ops_amd_get_option.argtypes = [ctypes.c_char_p]
-    lib.ops_mlp_strip_launch.restype = it
-    lib.ops_mlp_strip_launch.argtypes = [ctypes.POINTER(MlpStripArgs), vp]
-    lib.ops_mlp_spart_doubles.restype = ctypes.c_size_t
-    lib.ops_mlp_spart_doubles.argtypes = [it]
-    lib.ops_mlp_wgrad_group.restype = it
-    lib.ops_mlp_wgrad_group.argtypes = [it, ctypes.POINTER(MlpWgradProblem), vp]
-    lib.ops_mlp_wgrad_group_norm.restype = it
-    lib.ops_mlp_wgrad_group_norm.argtypes = [it, ctypes.POINTER(MlpWgradProblem), it, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int32), fl, vp, vp,
-                                             fl, fl, ctypes.POINTER(ctypes.c_int32), vp]
-    lib.ops_mlp_repack_weights.restype = it
-    lib.ops_mlp_repack_weights.argtypes = [it, ctypes.POINTER(MlpRepackEntry), vp]
-    lib.ops_flat_clip_adam_step_repack_f32.restype = it
-    lib.ops_flat_clip_adam_step_repack_f32.argtypes = [lg, vp, vp, vp, vp, vp, vp, fl, fl, fl, fl, fl, fl, it, vp, vp, it,
-                                                       ctypes.POINTER(MlpRepackEntry), vp]
-    lib.ops_mlp_gather_noise.restype = it
-    lib.ops_mlp_gather_noise.argtypes = [it, it, vp, vp, vp, ull, vp, vp, it, vp, vp, it, vp, vp]
-    lib.ops_mlp_gather_noise_repack.restype = it
-    lib.ops_mlp_gather_noise_repack.argtypes = [it, it, vp, vp, vp, ull, vp, vp, it, vp, vp, it, vp, lg, vp, it, ctypes.POINTER(MlpRepackEntry), vp]
-    lib.ops_mlp_loss_workspace_bytes.restype = ctypes.c_size_t
-    lib.ops_seq_attention_fwd.restype = it
-    lib.ops_seq_attention_fwd.argtypes = [it, it, it, it, vp, vp, fl, ull, vp, vp, vp]
-    lib.ops_seq_attention_bwd.restype = it
-    lib.ops_seq_attention_bwd.argtypes = [it, it, it, it, vp, vp, vp, fl, ull, vp, vp]
-    lib.ops_dropout_add_layernorm_fwd.restype = it
-    lib.ops_dropout_add_layernorm_fwd.argtypes = [it, it, vp, vp, it, vp, vp, fl, fl, ull, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_dropout_add_layernorm_bwd.restype = it
-    lib.ops_dropout_add_layernorm_bwd.argtypes = [it, it, vp, vp, vp, vp, vp, vp, fl, ull, vp, vp, vp, vp, vp, vp]
-    lib.ops_act_dropout_fwd.restype = it
-    lib.ops_act_dropout_fwd.argtypes = [lg, vp, vp, fl, fl, ull, vp, vp, vp]
-    lib.ops_diffusion_noise.restype = it
-    lib.ops_diffusion_noise.argtypes = [lg, it, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_diffusion_noise_draw.restype = it
-    lib.ops_diffusion_noise_draw.argtypes = [lg, it, it, vp, vp, ull, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_diffusion_combine_fwd.restype = it
-    lib.ops_diffusion_combine_fwd.argtypes = [it, it, it, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_diffusion_combine_bwd.restype = it
-    lib.ops_diffusion_combine_bwd.argtypes = [it, it, it, vp, vp, vp, vp, vp, vp, vp]
-    lib.ops_linear_wgrad_accumulate_group.restype = it
-    lib.ops_linear_wgrad_accumulate_group.argtypes = [it, ctypes.POINTER(WgradProblem), vp]
-    lib.ops_linear_wgrad_accumulate.restype = it
-    lib.ops_linear_wgrad_accumulate.argtypes = [it, it, it, vp, vp, vp, vp, vp]
-    lib.ops_act_dropout_bwd.restype = it
-    lib.ops_act_dropout_bwd.argtypes = [lg, vp, vp, vp, fl, fl, ull, vp, vp]
-    lib.ops_bayes_sample_f32.restype = it
-    lib.ops_bayes_sample_f32.argtypes = [it, ctypes.POINTER(BayesLayer), ull, vp, it, vp]
-    lib.ops_bayes_grad_fold_f32.restype = it
-    lib.ops_bayes_grad_fold_f32.argtypes = [it, ctypes.POINTER(BayesLayer), ull, vp, it, fl, fl, fl, vp]
-    lib.ops_bayes_mlp_mc_f32.restype = it
-    lib.ops_bayes_mlp_mc_f32.argtypes = [ctypes.POINTER(BayesMcArgs), vp]
-    lib.ops_mc_moments_f32.restype = it
-    lib.ops_mc_moments_f32.argtypes = [it, lg, it, vp, vp, vp, vp, vp, vp]
-    lib.ops_amd_max_elements.restype = it
-    lib.ops_amd_abi_version.restype = it
-    lib.ops_amd_last_error.restype = ctypes.c_char_p
-    lib.ops_beam_solve_kernel_name.restype = ctypes.c_char_p
-    lib.ops_beam_solve_kernel_name.argtypes = [it, it, it]
+    for name, (restype, argtypes) in _abi.functions.items():
+        try:
+            f = getattr(lib, name)
+        except AttributeError as e:
+            raise ExtensionMissingError(f"{LIB_PATH} does not export {name}, which {HEADER_PATH} declares: rebuild with "
+                                        "`python -m openpystruct_amd.build --force`") from e
+        f.restype, f.argtypes = restype, argtypes
     if lib.ops_amd_abi_version() != ABI_VERSION:     # a stale build of another ABI must not be driven with today's argument lists
         raise ExtensionMissingError(f"{LIB_PATH} has C-ABI version {lib.ops_amd_abi_version()}, "
                                     f"this package needs {ABI_VERSION}: rebuild with `python -m openpystruct_amd.build --force`")
     _lib = lib
     return lib
+
+
+def check(rc: int, what: str) -> None:
+    """Raise for the return code of a launch function that is not OK, with the library's message for this thread when there is one."""
+    if rc != OK:
+        msg = load().ops_amd_last_error().decode()
+        raise RuntimeError(f"{what} failed with code {rc}" + (f": {msg}" if msg else ""))
 
 
 def set_option(name: str, value: int) -> None:

@@ -98,8 +98,7 @@ class _BayesSampleFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = lib.ops_bayes_sample_f32(len(layers), _layer_structs(layers, outs=outs, eps=eps), sampler.seed, ctr.data_ptr(),
                                           mode, torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_bayes_sample_f32 failed with code {rc}: {lib.ops_amd_last_error()}")
+        _cabi.check(rc, "ops_bayes_sample_f32")
         ctx.sampler = sampler
         ctx.eps = eps
         ctx.ctr = ctr
@@ -125,8 +124,7 @@ class _BayesSampleFn(torch.autograd.Function):
             rc = lib.ops_bayes_grad_fold_f32(len(layers), _layer_structs(layers, eps=ctx.eps, grads=g, dparams=dparams), sampler.seed,
                                              ctx.ctr.data_ptr(), mode, float(sampler.kl_scale), float(sampler.prior_mu),
                                              float(sampler.prior_sigma), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_bayes_grad_fold_f32 failed with code {rc}: {lib.ops_amd_last_error()}")
+        _cabi.check(rc, "ops_bayes_grad_fold_f32")
         return (None, *dparams)
 
 
@@ -178,8 +176,7 @@ def _mc_args(mlp, x, S, P, ldx, seed, epilogue, y, eps_out=None):
 def _launch_mc(lib, a, dev):
     with torch.cuda.device(dev):
         rc = lib.ops_bayes_mlp_mc_f32(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _cabi.OK:
-        raise RuntimeError(f"ops_bayes_mlp_mc_f32 failed with code {rc}: {lib.ops_amd_last_error()}")
+    _cabi.check(rc, "ops_bayes_mlp_mc_f32")
 
 
 def _check_mc_shapes(S: int, blocks) -> None:
@@ -271,8 +268,7 @@ def predict_with_uncertainty(model, X: torch.Tensor, n_samples: int = 50, seed: 
         mc, sc_ = mean[b0:b0 + bc], std[b0:b0 + bc]
         with torch.cuda.device(dev):
             rc = lib.ops_mc_moments_f32(S, bc * n_elem, n_elem, preds.data_ptr(), _ptr(scale), _ptr(center), mc.data_ptr(), sc_.data_ptr(), stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_mc_moments_f32 failed with code {rc}: {lib.ops_amd_last_error()}")
+        _cabi.check(rc, "ops_mc_moments_f32")
         if return_draws:
             draws["t"][:, b0:b0 + bc] = t_out
             draws["xeps"][:, b0:b0 + bc] = x_out

@@ -112,8 +112,7 @@ def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolut
             out.v.data_ptr(), out.theta.data_ptr(), out.V.data_ptr(), out.M.data_ptr(),
             out.status.data_ptr(), int(tiling) | (TILING_STREAM_OUT if stream_out else 0), stream,
         )
-    if rc != _cabi.OK:
-        raise RuntimeError(f"ops_beam_solve_batched_f64 failed with code {rc}: {lib.ops_amd_last_error().decode()}")
+    _cabi.check(rc, "ops_beam_solve_batched_f64")
     return out
 
 
@@ -161,8 +160,7 @@ def beam_solve_vjp(x, E, I, fix, wy, v, theta, gv=None, gt=None, gV=None, gM=Non
             v.data_ptr(), theta.data_ptr(), ptr(gv), ptr(gt), ptr(gV), ptr(gM),
             gI.data_ptr(), gFy.data_ptr(), gwy.data_ptr(), status.data_ptr(), stream,
         )
-    if rc != _cabi.OK:
-        raise RuntimeError(f"ops_beam_solve_vjp_f64 failed with code {rc}: {lib.ops_amd_last_error().decode()}")
+    _cabi.check(rc, "ops_beam_solve_vjp_f64")
     return gI, gFy, gwy, status
 
 

@@ -224,8 +224,7 @@ def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tens
     if rc == _cabi.ERR_UNSUPPORTED:
         raise NotImplementedError(f"frame too large: n_eq={topo.n_eq}, half bandwidth={topo.kd} (half bandwidth <= 63: a (kd+6)-column ring, one "
                                   f"n_eq vector and two 24-column chunks must fit 160 KB of LDS; beyond 63, up to 1024: one n_eq vector and one column)")
-    if rc != _cabi.OK:
-        raise RuntimeError(f"ops_frame_solve_batched_f64 failed with code {rc}")
+    _cabi.check(rc, "ops_frame_solve_batched_f64")
     return out
 
 
@@ -261,8 +260,7 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
                                               es.data_ptr(), best.data_ptr(), cnt.data_ptr(), ep.data_ptr(), active.data_ptr(),
                                               last.data_ptr(), V32.data_ptr(), M32.data_ptr(), ctypes.byref(hp),
                                               torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_beam_sizing_step_f32 failed with code {rc}")
+        _cabi.check(rc, "ops_beam_sizing_step_f32")
         if loss_history is not None:
             loss_history.append(last.clone())
         if (e + 1) % poll_every == 0 and not bool(active.any()):

@@ -47,8 +47,7 @@ class _FEResidual(torch.autograd.Function):
             rc = lib.ops_beam_residual_f64(B, Ne, x.data_ptr(), N if x.dim() == 2 else 0, E.data_ptr(), Ne if E.numel() != 1 else 0,
                                            I.data_ptr(), fix.data_ptr(), N if fix.dim() == 2 else 0, Fy.data_ptr(), wy.data_ptr(),
                                            Ne if wy.numel() != 1 else 0, v.data_ptr(), theta.data_ptr(), rv.data_ptr(), rt.data_ptr(), s)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_beam_residual_f64 failed with code {rc}")
+        _cabi.check(rc, "ops_beam_residual_f64")
         ctx.save_for_backward(I, v, theta, x, E, fix)
         return rv, rt
 
@@ -68,8 +67,7 @@ class _FEResidual(torch.autograd.Function):
                                                I.data_ptr(), fix.data_ptr(), N if fix.dim() == 2 else 0, v.data_ptr(), theta.data_ptr(),
                                                gv.data_ptr(), gt.data_ptr(), sv.data_ptr(), st_.data_ptr(), dv.data_ptr(), dt.data_ptr(),
                                                dI.data_ptr(), s)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_beam_residual_vjp_f64 failed with code {rc}")
+        _cabi.check(rc, "ops_beam_residual_vjp_f64")
         return dI, dv, dt, None, None, None, None, None
 
 
@@ -152,8 +150,7 @@ class _FusedResidualTerm(torch.autograd.Function):
             a.v_scale, a.v_mean, a.t_scale, a.t_mean = (t.data_ptr() for t in sc)
         with torch.cuda.device(dev):
             rc = lib.ops_physics_loss_fwd(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_physics_loss_fwd failed with code {rc}")
+        _cabi.check(rc, "ops_physics_loss_fwd")
         ctx.args, ctx.keep = a, keep
         ctx.ncols = ncols
         return value
@@ -172,8 +169,7 @@ class _FusedResidualTerm(torch.autograd.Function):
         a.dpreds, a.ldp = dp.data_ptr(), preds.stride(0)
         with torch.cuda.device(dev):
             rc = lib.ops_physics_loss_bwd(ctypes.byref(a), torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_physics_loss_bwd failed with code {rc}")
+        _cabi.check(rc, "ops_physics_loss_bwd")
         return dp, None
 
 

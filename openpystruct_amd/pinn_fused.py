@@ -302,10 +302,6 @@ class PinnFusedStep:
             raise ValueError("more partial sums than the optimiser's workspace holds")
         return tiles + len(ranges)
 
-    def _check(self, rc: int, what: str) -> None:
-        if rc != _cabi.OK:
-            raise RuntimeError(f"{what} failed with code {rc}: {self.lib.ops_amd_last_error().decode()}")
-
     # ---- the step ----
     def repack_in_gather(self, flat_params: torch.Tensor) -> None:
         """r05: from now on every TRAINING gather (sigma given) also rebuilds the tiled bf16 weight copies from `flat_params` (the
@@ -324,14 +320,14 @@ class PinnFusedStep:
         s = torch.cuda.current_stream(self.dev).cuda_stream
         if self.repack_params is not None and sigma is not None:        # a training step's batch: + the weight copies of the last update
             with torch.cuda.device(self.dev):
-                self._check(self.lib.ops_mlp_gather_noise_repack(B, self.F_in, X.data_ptr(), idx.data_ptr(), sigma.data_ptr(),
+                _cabi.check(self.lib.ops_mlp_gather_noise_repack(B, self.F_in, X.data_ptr(), idx.data_ptr(), sigma.data_ptr(),
                                                                  int(seed) & 0x7FFFFFFFFFFFFFFF, self.prep_counter.data_ptr(), self.x.data_ptr(),
                                                                  self.x.shape[1], self.xt.data_ptr(), Y.data_ptr(), self.C, self.targets_t.data_ptr(),
                                                                  self.repack_params.numel(), self.repack_params.data_ptr(), len(self._repack),
                                                                  self._repack, s), "ops_mlp_gather_noise_repack")
             return B
         with torch.cuda.device(self.dev):
-            self._check(self.lib.ops_mlp_gather_noise(B, self.F_in, X.data_ptr(), idx.data_ptr(), sigma.data_ptr() if sigma is not None else None,
+            _cabi.check(self.lib.ops_mlp_gather_noise(B, self.F_in, X.data_ptr(), idx.data_ptr(), sigma.data_ptr() if sigma is not None else None,
                                                       int(seed) & 0x7FFFFFFFFFFFFFFF, self.prep_counter.data_ptr(), self.x.data_ptr(),
                                                       self.x.shape[1], self.xt.data_ptr(), Y.data_ptr(), self.C, self.targets_t.data_ptr(), s),
                         "ops_mlp_gather_noise")
@@ -357,14 +353,14 @@ class PinnFusedStep:
         """bf16 copies of the weights in both layouts from the float32 parameters.  The optimiser refreshes them in its own
         update launch (FlatClipAdam.repack); call this after anything else changed the parameters (load_state_dict)."""
         with torch.cuda.device(self.dev):
-            self._check(self.lib.ops_mlp_repack_weights(len(self._repack), self._repack, torch.cuda.current_stream(self.dev).cuda_stream),
+            _cabi.check(self.lib.ops_mlp_repack_weights(len(self._repack), self._repack, torch.cuda.current_stream(self.dev).cuda_stream),
                         "ops_mlp_repack_weights")
 
     def forward(self, B: int, stream=None) -> None:
         s = stream if stream is not None else torch.cuda.current_stream(self.dev).cuda_stream
         for a in self._fwd:
             a.B = B
-            self._check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (forward)")
+            _cabi.check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (forward)")
 
     def fwd_bwd(self, B: int, repack: bool = False) -> torch.Tensor:
         """Loss of the batch in x / targets_t (mean over its B rows; also added to `loss_sum`) and all parameter gradients.
@@ -378,14 +374,14 @@ class PinnFusedStep:
             self.forward(B, s)
             for a in self._bwd:
                 a.B = B
-                self._check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (backward)")
+                _cabi.check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (backward)")
             if self._norm is not None:
                 nm = self._norm
-                self._check(self.lib.ops_mlp_wgrad_group_norm(len(self._wgrad), self._wgrad, nm["nr"], nm["rp"], nm["rl"], nm["scale"],
+                _cabi.check(self.lib.ops_mlp_wgrad_group_norm(len(self._wgrad), self._wgrad, nm["nr"], nm["rp"], nm["rl"], nm["scale"],
                                                               nm["ws"].data_ptr(), nm["step"].data_ptr(), nm["betas"][0], nm["betas"][1],
                                                               ctypes.byref(nm["nparts"]), s), "ops_mlp_wgrad_group_norm")
             else:
-                self._check(self.lib.ops_mlp_wgrad_group(len(self._wgrad), self._wgrad, s), "ops_mlp_wgrad_group")
+                _cabi.check(self.lib.ops_mlp_wgrad_group(len(self._wgrad), self._wgrad, s), "ops_mlp_wgrad_group")
         return self.loss
 
     def evaluate(self, B: int) -> torch.Tensor:
@@ -396,7 +392,7 @@ class PinnFusedStep:
         with torch.cuda.device(self.dev):
             for a in self._eval:
                 a.B = B
-                self._check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (evaluation)")
+                _cabi.check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (evaluation)")
         return self.eval_loss
 
     def predictions(self, B: int) -> torch.Tensor:
@@ -446,7 +442,7 @@ class PinnFusedStep:
             for i in range(S):
                 idx = rows[i * batch:(i + 1) * batch]
                 x, xt, tt = view(i, self.x), view(i, self.xt), view(i, self.targets_t)
-                self._check(self.lib.ops_mlp_gather_noise(int(idx.numel()), self.F_in, X.data_ptr(), idx.data_ptr(), None, 0, None, x.data_ptr(),
+                _cabi.check(self.lib.ops_mlp_gather_noise(int(idx.numel()), self.F_in, X.data_ptr(), idx.data_ptr(), None, 0, None, x.data_ptr(),
                                                           x.shape[1], xt.data_ptr(), Y.data_ptr(), self.C, tt.data_ptr(), s),
                             "ops_mlp_gather_noise (evaluation slot)")
         self._slot_preds = [view(i, self.preds) for i in range(S)]
@@ -457,7 +453,7 @@ class PinnFusedStep:
         s = torch.cuda.current_stream(self.dev).cuda_stream
         with torch.cuda.device(self.dev):
             for a in self._slot_stages:
-                self._check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (evaluation slots)")
+                _cabi.check(self.lib.ops_mlp_strip_launch(ctypes.byref(a), s), "ops_mlp_strip_launch (evaluation slots)")
 
     def eval_slot_losses(self) -> torch.Tensor:
         """[slots] float32 view: the batch loss of each slot after `evaluate_slots()` (CompositeLoss mean over the slot's rows)."""

@@ -172,8 +172,7 @@ def _draw_cases_device(cfg: SizingConfig, seed: int, dev: torch.device, lo: int,
             float(cfg.L_min), float(cfg.L_max), float(cfg.max_force), float(cfg.min_force), Ls.data_ptr(), r_nodes.data_ptr(),
             nr.data_ptr(), f_nodes.data_ptr(), k.data_ptr(), f_vals.data_ptr(), fix.data_ptr(), Fy.data_ptr(),
             torch.cuda.current_stream(dev).cuda_stream)
-    if rc != _cabi.OK:
-        raise RuntimeError(f"ops_sizing_draw_cases_f64 failed with code {rc}: {_cabi.load().ops_amd_last_error().decode()}")
+    _cabi.check(rc, "ops_sizing_draw_cases_f64")
     if rb:
         xs = torch.linspace(0.0, 1.0, N, **f64)[None, :] * Ls[:, None]
     else:
@@ -407,8 +406,7 @@ class SizingState:
                     self.best_loss.data_ptr(), self.patience_cnt.data_ptr(), self.epochs_run.data_ptr(), self.active.data_ptr(),
                     self.last_loss.data_ptr(), ctypes.byref(self._hp), self._schedule.data_ptr(), self._status.data_ptr(), self._tiling(),
                     torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != _cabi.OK:
-                raise RuntimeError(f"ops_beam_sizing_epoch_f32 failed with code {rc}: {lib.ops_amd_last_error().decode()}")
+            _cabi.check(rc, "ops_beam_sizing_epoch_f32")
             return
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -416,15 +414,13 @@ class SizingState:
                 self.B, Ne, self.x.data_ptr(), N if self.x.dim() == 2 else 0, self.E.data_ptr(), 0, self.I64.data_ptr(), Ne,
                 self.fix.data_ptr(), N if self.fix.dim() == 2 else 0, self.Fy.data_ptr(), N, self.wy.data_ptr(), 0,
                 self._V.data_ptr(), self._M.data_ptr(), self._status.data_ptr(), self.active.data_ptr(), sizing_tiling(N), stream)   # float32 forces: beam_solve.hip only
-            if rc != _cabi.OK:
-                raise RuntimeError(f"ops_beam_solve_forces_f32 failed with code {rc}: {lib.ops_amd_last_error().decode()}")
+            _cabi.check(rc, "ops_beam_solve_forces_f32")
             rc = lib.ops_beam_sizing_step_vm32_f32(
                 self.B, Ne, self.I.data_ptr(), self.I64.data_ptr(), self._V.data_ptr(), self._M.data_ptr(),
                 self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.best_loss.data_ptr(),
                 self.patience_cnt.data_ptr(), self.epochs_run.data_ptr(), self.active.data_ptr(),
                 self.last_loss.data_ptr(), ctypes.byref(self._hp), self._schedule.data_ptr(), stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_beam_sizing_step_vm32_f32 failed with code {rc}")
+        _cabi.check(rc, "ops_beam_sizing_step_vm32_f32")
 
     def _tiling(self) -> int:
         return sizing_tiling(self.N, shared_geometry=self.x.dim() == 1 and self.fix.dim() == 1)

@@ -57,8 +57,7 @@ class _StencilBN(torch.autograd.Function):
                                               bn.running_var.data_ptr(), bn.num_batches_tracked.data_ptr() if training else None,
                                               z.data_ptr(), int(out_bf16), save.data_ptr(), ws.data_ptr(),
                                               torch.cuda.current_stream(x.device).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_stencil3_bn1_fwd_f32 failed with code {rc}")
+        _cabi.check(rc, "ops_stencil3_bn1_fwd_f32")
         ctx.save_for_backward(x, cw3, cb, gamma, save, ws)
         ctx.training = bool(training)
         ctx.cw_shape = cw.shape
@@ -89,8 +88,7 @@ class _StencilBN(torch.autograd.Function):
                                               cw3.data_ptr(), cb.data_ptr(),
                                               gamma.data_ptr(), save.data_ptr(), int(ctx.training), dx.data_ptr(), dp_ptr,
                                               ws.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_stencil3_bn1_bwd_f32 failed with code {rc}")
+        _cabi.check(rc, "ops_stencil3_bn1_bwd_f32")
         if direct:
             return dx, None, None, None, None, None, None, None, None
         return dx, dp[0:3].reshape(ctx.cw_shape), dp[3:4], dp[4:5], dp[5:6], None, None, None, None
@@ -168,8 +166,7 @@ class _FusedTail(torch.autograd.Function):
                 ptr(bn.num_batches_tracked) if (track and training) else None, float(slope), int(use_act), float(p_drop if drop else 0.0),
                 int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(counter) if drop else None, y.data_ptr(), ptr(z), ptr(mean), ptr(rstd), ptr(mask),
                 torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_fused_bn_act_fwd failed with code {rc}")
+        _cabi.check(rc, "ops_fused_bn_act_fwd")
         ctx.save_for_backward(z if need_z else xs[0], mean, rstd, gamma, beta, mask)
         ctx.cfg = (float(slope), int(use_act), float(p_drop if drop else 0.0), dt, direct, [t is not None for t in (x1, x2, x3)],
                    [None if t is None else t.dtype for t in (x1, x2, x3)])
@@ -196,8 +193,7 @@ class _FusedTail(torch.autograd.Function):
             rc = lib.ops_fused_bn_act_bwd(B, F, gy.data_ptr(), int(dt == torch.bfloat16), z.data_ptr(), ptr(mean), ptr(rstd), ptr(gamma),
                                           ptr(beta), slope, use_act, p_drop, ptr(mask), dz.data_ptr(), ptr(dg) if has_bn else None,
                                           ptr(db) if has_bn else None, torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_fused_bn_act_bwd failed with code {rc}")
+        _cabi.check(rc, "ops_fused_bn_act_bwd")
         gx = [None if not pr else (dz if d == dt else dz.to(d)) for pr, d in zip(present, dtypes)]
         return (gx[0], gx[1], gx[2], None if (not has_bn or direct) else dg, None if (not has_bn or direct) else db,
                 None, None, None, None, None, None, None, None)
@@ -360,8 +356,7 @@ class _FusedLoss(torch.autograd.Function):
                                                      maxc.data_ptr() if maxc is not None else None, float(box_w), float(rel_pen),
                                                      loss.data_ptr(), acc.data_ptr() if acc is not None else None, grad.data_ptr(), ws.data_ptr(),
                                                      torch.cuda.current_stream(dev).cuda_stream)
-        if rc != _cabi.OK:
-            raise RuntimeError(f"ops_surrogate_loss_grad_sum_f32 failed with code {rc}")
+        _cabi.check(rc, "ops_surrogate_loss_grad_sum_f32")
         ctx.save_for_backward(grad)
         ctx.unit_grad = bool(unit_grad)
         return loss

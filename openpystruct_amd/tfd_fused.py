@@ -85,11 +85,6 @@ class _State:
         return torch.empty(1, dtype=torch.int64, device=self.device)
 
 
-def _check(rc: int, what: str) -> None:
-    if rc != _cabi.OK:
-        raise RuntimeError(f"{what} failed with code {rc}: {_cabi.load().ops_amd_last_error().decode()}")
-
-
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
@@ -105,8 +100,8 @@ class SeqAttention(torch.autograd.Function):
         out = torch.empty((Bn * S, d), dtype=torch.bfloat16, device=qkv.device)
         used = st.used(site)
         with torch.cuda.device(qkv.device):
-            _check(lib.ops_seq_attention_fwd(Bn, S, H, d // H, qkv.data_ptr(), out.data_ptr(), float(p), st.seed + 7919 * site,
-                                             st.counter.data_ptr(), used.data_ptr(), _stream(qkv.device)), "ops_seq_attention_fwd")
+            _cabi.check(lib.ops_seq_attention_fwd(Bn, S, H, d // H, qkv.data_ptr(), out.data_ptr(), float(p), st.seed + 7919 * site,
+                                                   st.counter.data_ptr(), used.data_ptr(), _stream(qkv.device)), "ops_seq_attention_fwd")
         ctx.save_for_backward(qkv)
         ctx.cfg = (Bn, S, H, d, float(p), st.seed + 7919 * site, used)
         return out
@@ -121,8 +116,8 @@ class SeqAttention(torch.autograd.Function):
             g = g.to(torch.bfloat16)
         dqkv = torch.empty_like(qkv)
         with torch.cuda.device(qkv.device):
-            _check(lib.ops_seq_attention_bwd(Bn, S, H, d // H, qkv.data_ptr(), g.data_ptr(), dqkv.data_ptr(), p, seed, used.data_ptr(),
-                                             _stream(qkv.device)), "ops_seq_attention_bwd")
+            _cabi.check(lib.ops_seq_attention_bwd(Bn, S, H, d // H, qkv.data_ptr(), g.data_ptr(), dqkv.data_ptr(), p, seed, used.data_ptr(),
+                                                   _stream(qkv.device)), "ops_seq_attention_bwd")
         return dqkv, None, None, None, None, None, None
 
 
@@ -143,10 +138,10 @@ class DropoutAddLayerNorm(torch.autograd.Function):
         rstd = torch.empty(T, dtype=torch.float32, device=dev)
         used = st.used(site)
         with torch.cuda.device(dev):
-            _check(lib.ops_dropout_add_layernorm_fwd(T, d, x.data_ptr(), res.data_ptr(), int(res.dtype == torch.bfloat16), gamma.data_ptr(),
-                                                     beta.data_ptr(), float(eps), float(p), st.seed + 7919 * site, st.counter.data_ptr(),
-                                                     used.data_ptr(), y32.data_ptr(), y16.data_ptr(), z.data_ptr(), mean.data_ptr(),
-                                                     rstd.data_ptr(), _stream(dev)), "ops_dropout_add_layernorm_fwd")
+            _cabi.check(lib.ops_dropout_add_layernorm_fwd(T, d, x.data_ptr(), res.data_ptr(), int(res.dtype == torch.bfloat16), gamma.data_ptr(),
+                                                           beta.data_ptr(), float(eps), float(p), st.seed + 7919 * site, st.counter.data_ptr(),
+                                                           used.data_ptr(), y32.data_ptr(), y16.data_ptr(), z.data_ptr(), mean.data_ptr(),
+                                                           rstd.data_ptr(), _stream(dev)), "ops_dropout_add_layernorm_fwd")
         ctx.save_for_backward(z, mean, rstd, gamma, beta)
         ctx.cfg = (float(p), st.seed + 7919 * site, used, st, site, res.dtype)
         ctx.set_materialize_grads(False)        # an unused output's gradient arrives as None, not as a freshly filled zero tensor (one node each)
@@ -173,10 +168,10 @@ class DropoutAddLayerNorm(torch.autograd.Function):
         dg = gamma.grad if direct else torch.zeros_like(gamma)        # the launch ADDS (float atomics)
         db = beta.grad if direct else torch.zeros_like(beta)
         with torch.cuda.device(dev):
-            _check(lib.ops_dropout_add_layernorm_bwd(T, d, g32.data_ptr() if g32 is not None else None, g16.data_ptr() if g16 is not None else None,
-                                                     z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), p, seed, used.data_ptr(),
-                                                     dx.data_ptr(), dres.data_ptr(), dg.data_ptr(), db.data_ptr(), _stream(dev)),
-                   "ops_dropout_add_layernorm_bwd")
+            _cabi.check(lib.ops_dropout_add_layernorm_bwd(T, d, g32.data_ptr() if g32 is not None else None, g16.data_ptr() if g16 is not None else None,
+                                                           z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), p, seed, used.data_ptr(),
+                                                           dx.data_ptr(), dres.data_ptr(), dg.data_ptr(), db.data_ptr(), _stream(dev)),
+                         "ops_dropout_add_layernorm_bwd")
         if res_dtype != torch.float32:
             dres = dres.to(res_dtype)
         return dx, dres, None if direct else dg, None if direct else db, None, None, None, None
@@ -192,8 +187,8 @@ class ActDropout(torch.autograd.Function):
         y = torch.empty_like(x)
         used = st.used(site)
         with torch.cuda.device(x.device):
-            _check(lib.ops_act_dropout_fwd(x.numel(), x.data_ptr(), y.data_ptr(), float(slope), float(p), st.seed + 7919 * site,
-                                           st.counter.data_ptr(), used.data_ptr(), _stream(x.device)), "ops_act_dropout_fwd")
+            _cabi.check(lib.ops_act_dropout_fwd(x.numel(), x.data_ptr(), y.data_ptr(), float(slope), float(p), st.seed + 7919 * site,
+                                                 st.counter.data_ptr(), used.data_ptr(), _stream(x.device)), "ops_act_dropout_fwd")
         ctx.save_for_backward(x)
         ctx.cfg = (float(slope), float(p), st.seed + 7919 * site, used)
         return y
@@ -208,8 +203,8 @@ class ActDropout(torch.autograd.Function):
             g = g.to(torch.bfloat16)
         dx = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            _check(lib.ops_act_dropout_bwd(x.numel(), x.data_ptr(), g.data_ptr(), dx.data_ptr(), slope, p, seed, used.data_ptr(),
-                                           _stream(x.device)), "ops_act_dropout_bwd")
+            _cabi.check(lib.ops_act_dropout_bwd(x.numel(), x.data_ptr(), g.data_ptr(), dx.data_ptr(), slope, p, seed, used.data_ptr(),
+                                                 _stream(x.device)), "ops_act_dropout_bwd")
         return dx, None, None, None, None
 
 
@@ -227,7 +222,7 @@ def flush_pending_backward() -> None:
         pb, pdx, keep = _PENDING_BWD
         _PENDING_BWD = None
         with torch.cuda.device(pdx.device):
-            _check(_cabi.load().ops_tfd_encoder_layer_bwd(ctypes.byref(pb), _stream(pdx.device)), "ops_tfd_encoder_layer_bwd")
+            _cabi.check(_cabi.load().ops_tfd_encoder_layer_bwd(ctypes.byref(pb), _stream(pdx.device)), "ops_tfd_encoder_layer_bwd")
 
 
 
@@ -282,10 +277,10 @@ class EncoderLayerFn(torch.autograd.Function):
                 pa, py, _keep = _PENDING_LAYER
                 _PENDING_LAYER = None
                 assert py.data_ptr() == x32.data_ptr()
-                _check(lib.ops_tfd_encoder_layer_pair_fwd(ctypes.byref(pa), ctypes.byref(a), _stream(dev)), "ops_tfd_encoder_layer_pair_fwd")
+                _cabi.check(lib.ops_tfd_encoder_layer_pair_fwd(ctypes.byref(pa), ctypes.byref(a), _stream(dev)), "ops_tfd_encoder_layer_pair_fwd")
                 ctx.pair_later = True
             else:
-                _check(lib.ops_tfd_encoder_layer_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_encoder_layer_fwd")
+                _cabi.check(lib.ops_tfd_encoder_layer_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_encoder_layer_fwd")
         ctx.save_for_backward(x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2)
         ctx.cfg = (layer, Bn, S, H, dh, d, ff, ps, seeds, used, (rin, rout, r1, r2))
         ctx.set_materialize_grads(False)
@@ -338,10 +333,10 @@ class EncoderLayerFn(torch.autograd.Function):
                     pb, pdx, keep = _PENDING_BWD
                     _PENDING_BWD = None
                     if g32 is not None and g16 is None and pdx.data_ptr() == g32.data_ptr() and _TRACE_BWD is None:
-                        _check(lib.ops_tfd_encoder_layer_pair_bwd(ctypes.byref(pb), ctypes.byref(a), s), "ops_tfd_encoder_layer_pair_bwd")
+                        _cabi.check(lib.ops_tfd_encoder_layer_pair_bwd(ctypes.byref(pb), ctypes.byref(a), s), "ops_tfd_encoder_layer_pair_bwd")
                     else:                        # (not the successor's gradient after all: the two launches)
-                        _check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(pb), s), "ops_tfd_encoder_layer_bwd")
-                        _check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
+                        _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(pb), s), "ops_tfd_encoder_layer_bwd")
+                        _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
                 elif (LAYER_PAIR_BWD and ctx.pair_later and _TRACE_BWD is None and train._WGRAD_QUEUE is not None      # (queue mode: a flush follows)
                       and all(train.shadow_grads_are_deferred(r, T) for r in (r2, r1, rout, rin))):
                     # (only when the four weight-gradient registrations below merely QUEUE: a product the library runs at once -- fewer rows
@@ -351,7 +346,7 @@ class EncoderLayerFn(torch.autograd.Function):
                     # (the saved tensors too: autograd releases them when this call returns, before the launch that reads them)
                     _PENDING_BWD = (a, dx32, (g32, g16, d_f, d_u, d_a, dqkv, part, x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2))
                 else:
-                    _check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
+                    _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
                 if part is not None:
                     flatp = part.view(nwg, 512)
                     for k, q in enumerate((layer.norm2.weight, layer.norm2.bias, layer.norm1.weight, layer.norm1.bias)):
@@ -364,25 +359,25 @@ class EncoderLayerFn(torch.autograd.Function):
                 return dx32, None, None, None, None, None, None, None
             # LayerNorm2 <- (g32, g16)
             d_f, dres2 = torch.empty((T, d), **bf), torch.empty((T, d), **f32)
-            _check(lib.ops_dropout_add_layernorm_bwd(T, d, ptr(g32), ptr(g16), z2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(),
-                                                     layer.norm2.weight.data_ptr(), ps[3], seeds[3], used.data_ptr(), d_f.data_ptr(), dres2.data_ptr(),
-                                                     layer.norm2.weight.grad.data_ptr(), layer.norm2.bias.grad.data_ptr(), s), "ops_dropout_add_layernorm_bwd")
+            _cabi.check(lib.ops_dropout_add_layernorm_bwd(T, d, ptr(g32), ptr(g16), z2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(),
+                                                           layer.norm2.weight.data_ptr(), ps[3], seeds[3], used.data_ptr(), d_f.data_ptr(), dres2.data_ptr(),
+                                                           layer.norm2.weight.grad.data_ptr(), layer.norm2.bias.grad.data_ptr(), s), "ops_dropout_add_layernorm_bwd")
             train.shadow_param_grads(r2, d_f, h)
             d_h = d_f @ r2.w_sh
             d_u = torch.empty((T, ff), **bf)
-            _check(lib.ops_act_dropout_bwd(T * ff, u.data_ptr(), d_h.data_ptr(), d_u.data_ptr(), 0.0, ps[2], seeds[2], used.data_ptr(), s), "ops_act_dropout_bwd")
+            _cabi.check(lib.ops_act_dropout_bwd(T * ff, u.data_ptr(), d_h.data_ptr(), d_u.data_ptr(), 0.0, ps[2], seeds[2], used.data_ptr(), s), "ops_act_dropout_bwd")
             train.shadow_param_grads(r1, d_u, y1_16)
             d_y1 = d_u @ r1.w_sh
             # LayerNorm1 <- (dres2, d_y1)
             d_a, dres1 = torch.empty((T, d), **bf), torch.empty((T, d), **f32)
-            _check(lib.ops_dropout_add_layernorm_bwd(T, d, dres2.data_ptr(), d_y1.data_ptr(), z1.data_ptr(), mean1.data_ptr(), rstd1.data_ptr(),
-                                                     layer.norm1.weight.data_ptr(), ps[1], seeds[1], used.data_ptr(), d_a.data_ptr(), dres1.data_ptr(),
-                                                     layer.norm1.weight.grad.data_ptr(), layer.norm1.bias.grad.data_ptr(), s), "ops_dropout_add_layernorm_bwd")
+            _cabi.check(lib.ops_dropout_add_layernorm_bwd(T, d, dres2.data_ptr(), d_y1.data_ptr(), z1.data_ptr(), mean1.data_ptr(), rstd1.data_ptr(),
+                                                           layer.norm1.weight.data_ptr(), ps[1], seeds[1], used.data_ptr(), d_a.data_ptr(), dres1.data_ptr(),
+                                                           layer.norm1.weight.grad.data_ptr(), layer.norm1.bias.grad.data_ptr(), s), "ops_dropout_add_layernorm_bwd")
             train.shadow_param_grads(rout, d_a, ctxa)
             d_ctx = d_a @ rout.w_sh
             dqkv = torch.empty((T, 3 * d), **bf)
-            _check(lib.ops_seq_attention_bwd(Bn, S, H, dh, qkv.data_ptr(), d_ctx.data_ptr(), dqkv.data_ptr(), ps[0], seeds[0], used.data_ptr(), s),
-                   "ops_seq_attention_bwd")
+            _cabi.check(lib.ops_seq_attention_bwd(Bn, S, H, dh, qkv.data_ptr(), d_ctx.data_ptr(), dqkv.data_ptr(), ps[0], seeds[0], used.data_ptr(), s),
+                         "ops_seq_attention_bwd")
             train.shadow_param_grads(rin, dqkv, x16)
             d_x16 = dqkv @ rin.w_sh
         return dres1, d_x16, None, None, None, None, None, None
@@ -456,7 +451,7 @@ def refresh_layer_tiles(enc: nn.Module) -> None:
         for i0 in range(0, len(ent), _cabi.MLP_MAX_WGRAD):         # (the stand-alone repack call takes 8 matrices)
             n = min(_cabi.MLP_MAX_WGRAD, len(ent) - i0)
             part = (_cabi.MlpRepackEntry * n)(*[ent[i0 + k] for k in range(n)])
-            _check(lib.ops_mlp_repack_weights(n, part, _stream(dev)), "ops_mlp_repack_weights")
+            _cabi.check(lib.ops_mlp_repack_weights(n, part, _stream(dev)), "ops_mlp_repack_weights")
 
 
 def _layer_fused_ok(layer: nn.Module, st: _State) -> bool:
@@ -533,8 +528,8 @@ class DiffusionCombine(torch.autograd.Function):
         z = torch.empty((B, Nc + 1, d), dtype=torch.float32, device=m.device)
         z16 = torch.empty((B * (Nc + 1), d), dtype=torch.bfloat16, device=m.device)
         with torch.cuda.device(m.device):
-            _check(lib.ops_diffusion_combine_fwd(B, Nc, d, m.data_ptr(), xn32.data_ptr(), sa.data_ptr(), sb.data_ptr(), cls.data_ptr(),
-                                                 pe.data_ptr(), z.data_ptr(), z16.data_ptr(), _stream(m.device)), "ops_diffusion_combine_fwd")
+            _cabi.check(lib.ops_diffusion_combine_fwd(B, Nc, d, m.data_ptr(), xn32.data_ptr(), sa.data_ptr(), sb.data_ptr(), cls.data_ptr(),
+                                                       pe.data_ptr(), z.data_ptr(), z16.data_ptr(), _stream(m.device)), "ops_diffusion_combine_fwd")
         ctx.save_for_backward(sa, sb, cls)
         ctx.cfg = (B, Nc, d, st)
         ctx.set_materialize_grads(False)
@@ -558,9 +553,9 @@ class DiffusionCombine(torch.autograd.Function):
         direct = st.direct and cls.grad is not None and cls.grad.dtype == torch.float32 and cls.grad.is_contiguous()
         dcls = cls.grad if direct else torch.zeros_like(cls)
         with torch.cuda.device(dev):
-            _check(lib.ops_diffusion_combine_bwd(B, Nc, d, g.data_ptr() if g is not None else None, g16.data_ptr() if g16 is not None else None,
-                                                 sa.data_ptr(), sb.data_ptr(), dm.data_ptr(), dcls.data_ptr(), _stream(dev)),
-                   "ops_diffusion_combine_bwd")
+            _cabi.check(lib.ops_diffusion_combine_bwd(B, Nc, d, g.data_ptr() if g is not None else None, g16.data_ptr() if g16 is not None else None,
+                                                       sa.data_ptr(), sb.data_ptr(), dm.data_ptr(), dcls.data_ptr(), _stream(dev)),
+                         "ops_diffusion_combine_bwd")
         return dm, None, None, None, None if direct else dcls, None, None, None, None
 
 
@@ -624,7 +619,7 @@ class FrontFn(torch.autograd.Function):
             a.sigma, a.in_seed, a.n_order = gs["sigma"].data_ptr(), gs["seed"], int(gs["order"].numel())
             st.gathered = True
         with torch.cuda.device(dev):
-            _check(lib.ops_tfd_front_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_front_fwd")
+            _cabi.check(lib.ops_tfd_front_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_front_fwd")
         if keep:
             st.draws = (t.view(B, Nc), eps.view(B, Nc, d))
         ctx.save_for_backward(xn16, h, sa, sb)
@@ -655,7 +650,7 @@ class FrontFn(torch.autograd.Function):
                                   sa=sa.data_ptr(), sb=sb.data_ptr(), h=h.data_ptr(), Wt2=tiles["mlp2"][1].data_ptr(), dm=dm_.data_ptr(), d_h=d_h.data_ptr(),
                                   dcls=cls.grad.data_ptr())
         with torch.cuda.device(dev):
-            _check(lib.ops_tfd_front_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_front_bwd")
+            _cabi.check(lib.ops_tfd_front_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_front_bwd")
         train.shadow_param_grads(r2, dm_, h)
         train.shadow_param_grads(r0, d_h, xn16)
         return None, None, None, None
@@ -718,7 +713,7 @@ class HeadFn(torch.autograd.Function):
             a.box_weight = float(crit.penalty_weight)
             ctx.loss = (grad, part, loss, alpha, float("nan") if alpha0 is None else float(alpha0), float(crit.penalty_weight), acc, targets, minc, maxc)
         with torch.cuda.device(dev):
-            _check(lib.ops_tfd_head_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_head_fwd")
+            _cabi.check(lib.ops_tfd_head_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_head_fwd")
         ctx.save_for_backward(x16, a16, mean, rstd, h)
         ctx.cfg = (model, B, S, d, hid, C, p, st, (r1, r2))
         if ctx.loss is not None:
@@ -766,7 +761,7 @@ class HeadFn(torch.autograd.Function):
             part = torch.empty(((B + 15) // 16, 2, hid), dtype=torch.float32, device=dev)
             a.ln_part = part.data_ptr()
         with torch.cuda.device(dev):
-            _check(lib.ops_tfd_head_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_head_bwd")
+            _cabi.check(lib.ops_tfd_head_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_head_bwd")
         if part is not None:
             for k, q in enumerate((model.norm1.weight, model.norm1.bias)):
                 if not train.queue_column_sums(part[:, k, :], q.grad):
@@ -867,16 +862,16 @@ def model_forward(model: nn.Module, x: torch.Tensor, st: _State) -> torch.Tensor
             keep = st.keep_draws or KEEP_DRAWS
             t = torch.empty(rows, dtype=torch.int64, device=x.device) if keep else None
             eps = torch.empty((rows, d), dtype=torch.float32, device=x.device) if keep else None
-            _check(lib.ops_diffusion_noise_draw(rows, d, int(dm.T), x.data_ptr(), dm._acp.data_ptr(), st.seed + 7919 * 100, st.counter.data_ptr(),
-                                                xn32.data_ptr(), xn16.data_ptr(), sa.data_ptr(), sb.data_ptr(), t.data_ptr() if keep else None,
-                                                eps.data_ptr() if keep else None, _stream(x.device)), "ops_diffusion_noise_draw")
+            _cabi.check(lib.ops_diffusion_noise_draw(rows, d, int(dm.T), x.data_ptr(), dm._acp.data_ptr(), st.seed + 7919 * 100, st.counter.data_ptr(),
+                                                      xn32.data_ptr(), xn16.data_ptr(), sa.data_ptr(), sb.data_ptr(), t.data_ptr() if keep else None,
+                                                      eps.data_ptr() if keep else None, _stream(x.device)), "ops_diffusion_noise_draw")
             if keep:
                 st.draws = (t.view(B, Nc), eps.view(B, Nc, d))
         else:
             t = torch.randint(0, dm.T, (B, Nc), device=x.device)
             eps = torch.randn_like(x)
-            _check(lib.ops_diffusion_noise(rows, d, x.data_ptr(), t.data_ptr(), eps.data_ptr(), dm._acp.data_ptr(), xn32.data_ptr(), xn16.data_ptr(),
-                                           sa.data_ptr(), sb.data_ptr(), _stream(x.device)), "ops_diffusion_noise")
+            _cabi.check(lib.ops_diffusion_noise(rows, d, x.data_ptr(), t.data_ptr(), eps.data_ptr(), dm._acp.data_ptr(), xn32.data_ptr(), xn16.data_ptr(),
+                                                 sa.data_ptr(), sb.data_ptr(), _stream(x.device)), "ops_diffusion_noise")
     h = ActDropout.apply(dm.mlp[0](xn16), 0.0, 0.0, st, 101)                      # ReLU
     m = dm.mlp[2](h)
     z, z16 = DiffusionCombine.apply(m, xn32, sa, sb, model.cls_token, model.pos_encoder.pe, B, Nc, st)

@@ -3,6 +3,8 @@ include/openpystruct_amd.h declares (no compute calls here)."""
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -21,13 +23,163 @@ def test_header_symbols_are_exported(lib):
     hdr = open(os.path.join(ROOT, "include", "openpystruct_amd.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     declared = set(re.findall(r"\b(ops_[a-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_cabi.EXPORTS)
+    assert declared == set(_cabi.EXPORTS) and len(_cabi.EXPORTS) == len(declared)
     for name in declared:
         assert getattr(lib, name) is not None
+        assert getattr(lib, name).argtypes is not None, name        # every entry point is called with checked argument types
 
 
 def test_abi_version(lib):
     assert lib.ops_amd_abi_version() == 14 == _cabi.ABI_VERSION     # 14: ops_tfd_head_bwd_args.ln_part; 13: ops_frame_solve_batched_f64_ex (OPS_FRAME_REUSE_PLAN), ops_frame_plan_signature; 12: ops_mlp_wgrad_group_norm, OPS_ADAM_NORM_READY; 11: ops_tfd_front_args.n_order (a walked-past cursor wraps); 10: loss on the TFD head's tile, identity_act of the TFD launches, ops_physics_loss_*; 2: ops_beam_sizing_epoch_f32 takes I_last (float32) instead of I64; 3: ops_mlp_* layer blocks; 4: diffusion combine with a bf16 copy / two gradients; 5: encoder-layer launches on tiled weights; 6: head / front-end launches, column-sum jobs and 24 problems in the grouped weight-gradient launch, ln_part; 7: ops_mlp_strip_args.eval_stats; 8: ops_sizing_draw_cases_f64; 9: evaluation slots of ops_mlp_strip_args
+
+
+_REFEREE = r"""
+#include "openpystruct_amd.h"
+#include <cstddef>
+#include <cstdio>
+#include <type_traits>
+template <class T> void kind() {        // " <sizeof>:<p|f|s|u>" (pointer, floating, signed, unsigned), " 0:v" for void
+  if constexpr (std::is_void_v<T>) std::printf(" 0:v");
+  else std::printf(" %zu:%c", sizeof(T), std::is_pointer_v<T> ? 'p' : std::is_floating_point_v<T> ? 'f' : std::is_signed_v<T> ? 's' : 'u');
+}
+template <class R, class... A> void sig(const char* name, R (*)(A...)) {
+  std::printf("F %s", name); kind<R>(); (kind<A>(), ...); std::printf("\n");
+}
+#define STRUCT(S) std::printf("S %s %zu\n", #S, sizeof(S))
+#define FIELD(S, f) (std::printf("M %s %s %zu", #S, #f, offsetof(S, f)), kind<decltype(S::f)>(), std::printf("\n"))
+#define FUNC(f) sig(#f, static_cast<decltype(&f)>(nullptr))      /* the type only: nothing to link against */
+int main() {
+@CALLS@  return 0;
+}
+"""
+
+
+def _kind(t) -> str:
+    """What the referee prints for a C type, for the ctypes type the binding chose."""
+    if t is None:
+        return "0:v"
+    code = t._type_ if isinstance(getattr(t, "_type_", None), str) else "P"          # POINTER(...): _type_ is the pointee class
+    return f"{ctypes.sizeof(t)}:{'p' if code in 'Pz' else 'f' if code in 'fd' else 's' if code.islower() else 'u'}"
+
+
+def test_binding_agrees_with_the_compiler(tmp_path):
+    """The compiler is the referee of the header reader: a C++ program that includes the real header reports sizeof / offsetof / kind
+    of every struct field and the arity, widths and kinds of every prototype; the ctypes Structures and argtypes must say the same."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not found: the referee program cannot be built")
+    abi = _cabi._abi
+    lines = []
+    for name, cls in abi.structs.items():
+        lines.append(f"  STRUCT({name});\n")
+        lines += [f"  FIELD({name}, {field});\n" for field, _ in cls._fields_]
+    lines += [f"  FUNC({name});\n" for name in abi.functions]
+    src, exe = tmp_path / "referee.cpp", tmp_path / "referee"
+    src.write_text(_REFEREE.replace("@CALLS@", "".join(lines)))
+    subprocess.check_call(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    sizes, members, functions = {}, {}, {}
+    for line in subprocess.check_output([str(exe)], text=True).splitlines():
+        tag, name, *rest = line.split()
+        if tag == "S":
+            sizes[name] = int(rest[0])
+        elif tag == "M":
+            members[name, rest[0]] = (int(rest[1]), rest[2])
+        else:
+            functions[name] = rest
+    assert len(sizes) == len(abi.structs) == 14 and len(functions) == len(abi.functions) == 70
+    for name, cls in abi.structs.items():
+        assert getattr(_cabi, cls.__name__) is cls, f"struct {name} has no line {cls.__name__} = _struct(...) in _cabi.py"
+        assert ctypes.sizeof(cls) == sizes[name], f"struct {name}: ctypes {ctypes.sizeof(cls)} bytes, compiler {sizes[name]}"
+        for field, t in cls._fields_:
+            assert (getattr(cls, field).offset, _kind(t)) == members[name, field], f"struct {name}.{field}"
+    for name, (restype, argtypes) in abi.functions.items():
+        assert [_kind(restype)] + [_kind(t) for t in argtypes] == functions[name], f"function {name}"
+
+
+_ACCEPTED = """
+/* a header of the shape of the real one */
+#ifndef X_H
+#define X_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define OPS_AMD_ONE 1u   /* unsigned suffix */
+#define OPS_HEX 0x200
+#define OPS_PLAIN 24
+typedef struct ops_pair {
+  float a, b;                       /* two declarators */
+  /* a comment between fields */
+  const float* const* p; int32_t n; // two declarations on one line
+  double *x, y;
+  unsigned long long seed; long long* rows; int64_t stride;
+} ops_pair;
+int ops_one(int n, const ops_pair* args, const ops_pair* const* list, void* stream); size_t ops_two(void);
+const char* ops_name(const char* key, long value, unsigned flags);
+void ops_fill(const uint8_t* mask,
+              float* out /* [n] */);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_reads_the_forms_the_header_uses():
+    c = ctypes
+    abi = _cabi.read_header(_ACCEPTED)
+    assert abi.defines == {"OPS_AMD_ONE": 1, "OPS_HEX": 0x200, "OPS_PLAIN": 24}
+    pair = abi.structs["ops_pair"]
+    assert list(abi.structs) == ["ops_pair"] and pair.__name__ == "Pair"
+    assert pair._fields_ == [("a", c.c_float), ("b", c.c_float), ("p", c.c_void_p), ("n", c.c_int32), ("x", c.c_void_p), ("y", c.c_double),
+                             ("seed", c.c_ulonglong), ("rows", c.c_void_p), ("stride", c.c_int64)]
+    assert pair(a=1.5, n=3).n == 3 and c.sizeof(pair) == 64
+    assert abi.functions == {"ops_one": (c.c_int, [c.c_int, c.POINTER(pair), c.c_void_p, c.c_void_p]), "ops_two": (c.c_size_t, []),
+                             "ops_name": (c.c_char_p, [c.c_char_p, c.c_long, c.c_uint]), "ops_fill": (None, [c.c_void_p, c.c_void_p])}
+
+
+@pytest.mark.parametrize("text, complaint", [
+    ("typedef struct ops_a { float w[4]; } ops_a;", "w[4]"),                                        # array member
+    ("typedef struct ops_a { int32_t flag : 1; } ops_a;", "flag : 1"),                                # bit field
+    ("typedef struct ops_a { int n; } ops_a;\ntypedef struct ops_b { ops_a inner; } ops_b;", "'ops_a' by value"),
+    ("typedef struct ops_a { int n; } ops_a;\nint ops_f(ops_a a);", "'ops_a' by value"),
+    ("typedef struct ops_a { struct { int n; } in; } ops_a;", "typedef struct ops_a"),               # nested struct
+    ("struct ops_a { int n; };", "struct ops_a"),                                                    # not the typedef form
+    ("typedef struct ops_a { int n; } ops_b;", "ops_b"),
+    ("int ops_f(void (*callback)(int), void* stream);", "int ops_f"),                                # function-pointer parameter
+    ("int ops_f(uint16_t n);", "unknown type 'uint16_t'"),
+    ("int ops_f(unsigned long n);", "unknown type 'unsigned long'"),
+    ("short ops_f(int n);", "unknown type 'short'"),
+    ("typedef struct ops_a { ops_later* p; } ops_a;", "unknown type 'ops_later'"),
+    ("int ops_f(int);", "no name"),
+    ("int ops_f();", "ops_f"),
+    ("int ops_f(int n);\nstatic int counter;\nint ops_g(int n);", "static int counter"),            # stray text between declarations
+    ("int ops_f(int n) int ops_g(int n);", "int ops_f"),                                             # unsplittable prototype
+    ("int ops_f(int n);\nint ops_f(int n);", "declared twice"),
+    ("int ops_f(int n = 3);", "n = 3"),
+    ("#define OPS_SHIFT (1 << 4)\n", "OPS_SHIFT"),
+    ("#define OPS_PI 3.14\n", "OPS_PI"),
+    ("#define OPS_MAX(a, b) 1\n", "OPS_MAX"),
+    ("#define OPS_LONG 1 \\\n + 2\n", "continuation"),
+])
+def test_header_reader_refuses_what_it_cannot_read(text, complaint):
+    """A declaration the reader skipped would be an entry point driven without checked types: everything it does not understand is an error."""
+    with pytest.raises(ValueError) as e:
+        _cabi.read_header(text)
+    assert complaint in str(e.value)
+
+
+def test_missing_header_is_reported_with_its_path(monkeypatch, tmp_path):
+    monkeypatch.setattr(_cabi, "HEADER_PATH", str(tmp_path / "nowhere.h"))
+    with pytest.raises(_cabi.ExtensionMissingError, match="nowhere.h"):
+        _cabi._read_abi()
+
+
+def test_check_turns_a_return_code_into_an_exception(lib):
+    assert _cabi.check(_cabi.OK, "ops_something") is None
+    z = ctypes.c_void_p(0)
+    rc = lib.ops_beam_solve_batched_f64(-1, 100, z, 0, z, 0, z, 100, z, 0, z, 101, z, 0, z, z, z, z, z, 0, z)
+    with pytest.raises(RuntimeError, match=r"^ops_beam_solve_batched_f64 failed with code 1(: .+)?$"):
+        _cabi.check(rc, "ops_beam_solve_batched_f64")
 
 
 def test_size_and_kernel_name_introspection(lib):
