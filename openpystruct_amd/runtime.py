@@ -145,6 +145,46 @@ def cpu_throttle_counters() -> Dict[str, int]:
     return out
 
 
+def capture_graph(side, device, body, warmups: int = 0, before_each=None, warm=None):
+    """The capture protocol, once: the side stream waits for the current one; on it, `warmups` eager passes (of `warm` where the eager pass
+    differs from the captured one, else of `body`), a synchronise, `body()` captured into a fresh graph; the current stream waits for the
+    side stream.  `before_each()` runs before every pass, the captured one included.  Returns (graph, what `body` returned while capturing).
+    With `side` already current -- inside the caller's own side-stream region -- it adds no waits, and without warm-up passes no synchronise."""
+    import torch
+    current = torch.cuda.current_stream(device)
+    if current != side:
+        side.wait_stream(current)
+        with torch.cuda.stream(side):
+            out = capture_graph(side, device, body, warmups, before_each, warm)
+        current.wait_stream(side)
+        return out
+    for _ in range(warmups):
+        if before_each is not None:
+            before_each()
+        (warm or body)()
+    if before_each is not None:
+        before_each()
+    if warmups:
+        side.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+        value = body()
+    return graph, value
+
+
+def try_capture(what: str, instead: str, log, device, attempt):
+    """`attempt()` -- one or more `capture_graph` calls that stand or fall together -- or, when it raises: a line to `log`, a device
+    synchronise (nothing half-captured stays in flight) and None; the caller then takes the path `instead` names."""
+    import torch
+    try:
+        return attempt()
+    except Exception as e:
+        if log:
+            log(f"HIP graph capture of {what} failed ({e!r}); {instead}")
+        torch.cuda.synchronize(device)
+        return None
+
+
 _MEMSET_OK: Dict[int, bool] = {}
 
 
@@ -158,15 +198,7 @@ def graph_memsets_replay_correctly(device=None) -> bool:
         return _MEMSET_OK[idx]
     with torch.cuda.device(idx):
         g = torch.randn(2048, 64, device=dev, dtype=torch.bfloat16)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            g.sum(0)
-            side.synchronize()
-            gr = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gr, stream=side, capture_error_mode="thread_local"):
-                out = g.sum(0)
-        torch.cuda.current_stream(dev).wait_stream(side)
+        gr, out = capture_graph(torch.cuda.Stream(device=dev), dev, lambda: g.sum(0), 1)
         ok = True
         for _ in range(3):
             g.copy_(torch.randn(2048, 64, device=dev))

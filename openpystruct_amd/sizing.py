@@ -469,17 +469,10 @@ def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25
     epochs_done = 0
     if graph is None and use_graph and poll_every > 1:
         # the epoch body is launch-bound (two short kernels): replay `poll_every` epochs as one HIP graph
-        side = torch.cuda.Stream(device=device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            st.epoch()                      # warm-up outside capture (allocates the solution buffers)
-            epochs_done = 1
-            side.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                for _ in range(poll_every):
-                    st.epoch()
-        torch.cuda.current_stream(device).wait_stream(side)
+        from .runtime import capture_graph
+        # one eager epoch as the warm-up outside capture (it allocates the solution buffers)
+        graph, _ = capture_graph(torch.cuda.Stream(device=device), device, lambda: [st.epoch() for _ in range(poll_every)], 1, warm=st.epoch)
+        epochs_done = 1
         if reuse:
             _EPOCH_GRAPHS[key] = (st, graph)
     if graph is not None:

@@ -679,280 +679,143 @@ def train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *, 
         switches.set("fused_prep", saved[3]); switches.set("fused_physics", saved[4])
 
 
-def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *, autocast_dtype=torch.bfloat16,
-                     sync_bn: bool = False, max_epochs: Optional[int] = None, log=None, seed: int = 0,
-                     use_graph: Optional[bool] = None, physics: Optional[PhysicsTerm] = None,
-                     init_fn=None, batch_order=None) -> Dict[str, object]:
-    """Trains on THIS rank's `data` shard; uses DDP when torch.distributed is initialised with world_size > 1.
-    Returns history, best state dict, validation R^2 (I only) and per-epoch times.
-    `init_fn(model)`: called once on the freshly built model (load a checkpoint, deterministic test weights).
-    `batch_order(epoch) -> LongTensor[n_train]`: the epoch's sample order instead of a random permutation (the
-    reference's DataLoader shuffle, PINN:701, is unseeded; the golden-fixture tests replay the order it drew).
-    `autocast_dtype=torch.float16`: the reference's AMP mode (fp16 autocast + GradScaler, PINN:706, :759-768) on the framework modules; the
-    returned dict then carries `grad_scaler` = {"scale", "skipped_steps", "steps"}."""
-    cfg = cfg or {"pinn": PinnConfig, "tfd": TfdConfig, "fnn": FnnConfig, "gnn": GnnConfig, "fno": FnoConfig, "btfd": BtfdConfig,
-                  "btfdm": BtfdmConfig}[kind]()
-    alpha_term = kind in ("tfd", "fnn", "fno", "btfd", "btfdm")    # (initial_alpha - alpha)^2 in the training loss (TFD:743, FNO:615, BTFD:730)
-    bayes_kl = kind in ("btfd", "btfdm") and cfg.kl == "gaussian"
-    if kind in ("btfd", "btfdm") and cfg.kl not in ("none", "gaussian"):
-        raise ValueError(f"kl must be 'none' or 'gaussian', not {cfg.kl!r}")
-    if kind == "fno":
-        autocast_dtype = None                           # FNO:613 runs with autocast disabled
-    device = torch.device(device)
-    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
-    rank = dist.get_rank() if world > 1 else 0
-    # the data-parallel branch: more than one rank -- or, with OPS_AMD_FORCE_DP=1, a process group of ONE rank (r05: the RCCL path -- flat
-    # all-reduce between graph A and graph B, its async form, the one-graph capture of the collective, dp_segments -- executed on the
-    # single GPU a test box has; a one-rank all-reduce is the identity and 1 / world = 1, so losses equal the plain run bit for bit)
-    dp = world > 1 or (_FORCE_DP and dist.is_available() and dist.is_initialized())
-    torch.manual_seed(seed)            # identical initial weights on every rank
-    model, crit = build_model_and_loss(kind, cfg, data, device)
-    if kind == "tfd" and device.type == "cuda":
-        from . import tfd_fused as _tf
-        _tf.disarm_gather()              # (whatever an earlier run that did not reach its end left armed)
-    if init_fn is not None:
-        init_fn(model)
-    bayes_hip = None
-    if kind in ("btfd", "btfdm") and device.type == "cuda":
-        # the four Bayesian layers: one sampling launch per forward, one fold launch per backward (bayes.py, csrc/bayes_mlp.hip); with
-        # the KL term on, the fold adds its gradient and the loss its (detached) value
-        from . import bayes as _bayes
-        bayes_hip = _bayes.BayesSampler(model, seed=seed * 7919 + 307 + rank, kl_scale=cfg.bnn_kl_scale if bayes_kl else 0.0)
-        model.bayes_sampler = bayes_hip
+class _PhysicsInputs:
+    """The FE-residual term's device-side inputs -- loads, scalers, for the I-only models the recorded displacement fields -- and its two
+    evaluations.  `g_idx`: the fused batch assembly's row output (None where the step gathers its batch some other way)."""
 
-    def kl_term():
-        from . import bayes as _bayes
-        kl = _bayes.bayesian_kl(model)
-        return cfg.bnn_kl_scale * (kl.detach() if bayes_hip is not None else kl)
-
-    if sync_bn and dp:
-        model = nn.SyncBatchNorm.convert_sync_batchnorm(model)
-    net = model
-    # one flat gradient buffer; every .grad is a view into it (autograd accumulates in place)
-    params = [q for q in model.parameters()]
-    flat = torch.zeros(sum(q.numel() for q in params), device=device, dtype=torch.float32)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    g_stash, g_dst, patched = [], [], []
-    fast_encoder = None
-    shared_counter = False
-    if hasattr(model, "direct_param_grads"):   # fused tails (csrc/fused_bn.hip) write BatchNorm parameter gradients into `flat` themselves
-        model.direct_param_grads = device.type == "cuda"
-    torch.manual_seed(seed + 1 + rank)  # different noise / shuffles per rank
-    on_gpu = device.type == "cuda"
-    # the reference's AMP mode: GradScaler(init_scale 65536, growth 2, backoff 0.5, growth interval 2000) -- torch.cuda.amp.GradScaler's defaults
-    fp16_scaler = {"scale": 65536.0, "good": 0, "skipped": 0, "steps": 0} if (on_gpu and autocast_dtype == torch.float16) else None
-    if fp16_scaler is not None:
-        use_graph = False                # the scale and the skip decision are per-step host state, like `scaler.step` / `scaler.update`
-    if use_graph is None:
-        use_graph = on_gpu and os.environ.get("OPS_AMD_GRAPH", "1") == "1"    # the step is launch-bound (~150 tiny kernels): replay it as HIP graphs
-    # under graph replay the learning rate must live in a device tensor, or the scheduler's updates would
-    # never reach the captured optimiser step
-    prep_counter = torch.zeros(2, dtype=torch.int64, device=device) if on_gpu else None     # batch assembly: [calls, workgroups done]
-    if on_gpu:      # clip + Adam over the flat buffers in two HIP launches; loss.alpha NOT included (PINN:696)
-        opt = FlatClipAdam(params, flat, cfg.learning_rate, weight_decay=cfg.weight_decay, max_norm=1.0, decoupled=kind == "gnn")
-        sched = None
-        if _SHADOW_LINEAR and autocast_dtype == torch.bfloat16:
-            g_stash, g_dst, patched = enable_shadow_linears(model, opt, params, flat)
-            if kind == "tfd":
-                from . import tfd_fused          # csrc/seq_block.hip: attention, dropout + add + LayerNorm, ReLU + dropout, diffusion front end
-                if tfd_fused.patch_model(model, seed=seed * 7919 + 211 + rank, direct_param_grads=True):
-                    fast_encoder = model
-                    opt.repack = getattr(model.transformer_encoder, "_ops_tile_entries", None)    # the Adam launch refreshes the layer kernels' weight tiles
-                    if switches.get("fused_prep") == "1":
-                        # the batch-assembly launch advances its call counter once per step: the dropout / noise streams read that one
-                        tfd_fused.share_step_counter(model.transformer_encoder, prep_counter)
-                        shared_counter = True
-    else:
-        opt = (torch.optim.AdamW if kind == "gnn" else torch.optim.Adam)(model.parameters(), lr=cfg.learning_rate,   # GNN:394
-                                                                         weight_decay=cfg.weight_decay)
-        sched = ExponentialLR(opt, gamma=cfg.gamma)
-    # PINN: forward + loss + backward as 13 hand-written launches without autograd (pinn_fused.py / csrc/mlp_block.hip);
-    # the module keeps owning parameters and buffers, evaluation keeps running it
-    engine = None
-    if on_gpu and kind == "pinn" and autocast_dtype == torch.bfloat16 and physics is None and not (sync_bn and dp):
-        from . import pinn_fused
-        if pinn_fused.eligible(model, crit, cfg.batch_size):
-            engine = pinn_fused.PinnFusedStep(model, crit, seed=seed * 7919 + 101 + rank)
-            opt.repack = engine._repack      # the Adam launch refreshes the engine's bf16 weight copies
-            if not dp and switches.get("pinn_norm_fold") == "1":
-                # one rank: the gradients are final when the weight-gradient launch ends, so that launch leaves the clip norm's partial
-                # sums and the optimiser skips its norm launch (a node and ~4.5 us per step; data parallel: the norm is the all-reduced one)
-                opt.norm_ready_parts = engine.enable_norm(flat, opt.ws, opt.step_count, opt.betas)
-            if not dp and switches.get("pinn_repack_in_gather") == "1":
-                # one rank: the weight copies of step n ride on the batch-assembly launch of step n + 1 (adjacent launches that depend on
-                # nothing of each other: one node and ~5 us less per step); the optimiser call no longer rebuilds them
-                opt.repack = None
-                engine.repack_in_gather(opt.p)
-    if use_graph and on_gpu and engine is None and fast_encoder is None:
-        # a step the FRAMEWORK differentiates (comparator paths, the sibling surrogates): its multi-block reductions are only right under
-        # graph replay when captured memset nodes are (runtime.py item 2); the hand-written paths above contain none
-        from . import runtime
-        if not runtime.graph_memsets_replay_correctly(device):
-            use_graph = False
-            if log:
-                log(f"captured hipMemsetAsync nodes replay wrong values in this process ({runtime.PACKET_CAPTURE_ENV}=0 came after its "
-                    "first HIP call?): the framework-differentiated step runs eagerly")
-    Xtr, Ytr, Xva, Yva = (t.to(device) for t in (data.X_train, data.Y_train, data.X_val, data.Y_val))
-    nb_tr = max(1, (Xtr.shape[0] + cfg.batch_size - 1) // cfg.batch_size)
-    if dp:   # every rank must run the same number of steps (collectives inside backward)
-        # a one-row tail batch makes train-mode BatchNorm raise (as in the reference's single process); on one rank of a
-        # data-parallel job that exception would leave the other ranks waiting in the step's all-reduce: drop such a tail
-        if Xtr.shape[0] % cfg.batch_size == 1 and nb_tr > 1 and any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
-            nb_tr -= 1
-        t = torch.tensor([nb_tr], device=device)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN)
-        nb_tr = int(t.item())
-    use_ac = device.type == "cuda" and autocast_dtype is not None
-    hist = {"train": [], "val": [], "epoch_s": []}
-    # Transformer-Diffusion fast path, r04: the front-end launch assembles its own batch (rows order[cursor ..] of the training set + the
-    # input noise) and the head's loss reads its targets through those rows: no batch-assembly launch per step.  The epoch's permutation
-    # lives in `g_order`, `g_cursor` is advanced by the launch itself (reset per epoch).
-    fuse_gather = False
-    g_order = g_cursor = g_noise = None
-    _FUSED_PHYS = on_gpu and switches.get("fused_physics") == "1"      # A/B switch: 0 = physics.fe_residual_loss from framework ops
-    # the loss launch adds every step's value to the epoch's running sum itself (zeroed per epoch): no add node per step
-    # (with the fused physics term both launches add into the same running sum: the epoch's total of data loss + term)
-    loss_acc = torch.zeros((), dtype=torch.float32, device=device) if (on_gpu and _FUSED_LOSS and engine is None and (physics is None or _FUSED_PHYS) and switches.get("loss_acc") == "1") else None
-    # the loss on the head's tile: its value exists once the head's backward launch has run, so a second term can only be tied to it
-    # (not added) -- which needs the running sum to carry the step values
-    head_loss_ok = fast_encoder is not None and _FUSED_LOSS and (physics is None or (_FUSED_PHYS and loss_acc is not None))
-    if (head_loss_ok and shared_counter and Xtr.dtype == torch.float32 and Xtr.dim() == 3
-            and Xtr.is_contiguous() and Ytr.dtype == torch.float32 and Ytr.is_contiguous() and Ytr.dim() == 2):
-        from . import tfd_fused
-        if tfd_fused.gather_fusable(model, device, int(Xtr.shape[2])):
-            fuse_gather = True
-            g_order = torch.arange(max(int(Xtr.shape[0]), cfg.batch_size), device=device) % int(Xtr.shape[0])
-            g_cursor = torch.zeros((), dtype=torch.int64, device=device)
-            g_noise = torch.zeros((), device=device)
-            g_idx = torch.zeros(max(cfg.batch_size, 1), dtype=torch.int64, device=device)
-            tfd_fused.arm_gather(model, Xtr, Ytr, g_order, g_cursor, g_idx, g_noise, (seed * 7919 + 13 + rank) & 0x7FFFFFFFFFFFFFFF)
-
-    if physics is not None:
+    def __init__(self, term: PhysicsTerm, kind: str, cfg, data: SurrogateData, device, fused: bool, g_idx, loss_acc):
         if cfg.n_cases != 1 or data.Fy_train is None:
             raise ValueError("the FE-residual term needs n_cases == 1 and data.Fy_train (per-case loads)")
         if kind != "pinn" and data.v_train is None:
             raise ValueError("the FE-residual term of an I-only model needs the recorded displacements (data.v_train)")
-        from .physics import fe_residual_loss
-        Fy_tr = data.Fy_train.to(device)
-        sI = data.scalers_Y["I"]
-        if kind == "pinn":
-            sD, sR = data.scalers_Y["deflections"], data.scalers_Y["rotations"]
-        else:
-            v_rec = data.v_train.to(device=device, dtype=torch.float64).contiguous()        # (the fused term reads raw float64 rows)
-            t_rec = data.theta_train.to(device=device, dtype=torch.float64).contiguous()
-        px, pfix = physics.x.to(device=device, dtype=torch.float64), physics.fix.to(device=device, dtype=torch.uint8)
-        pE = torch.tensor(float(physics.E), dtype=torch.float64, device=device)      # device scalars: nothing crosses PCIe
-        pwy = torch.tensor(float(physics.wy), dtype=torch.float64, device=device)    # inside a captured step
+        self.term, self.pinn, self.nel, self.fused, self.g_idx, self.loss_acc = term, kind == "pinn", cfg.nelem, fused, g_idx, loss_acc
+        self.Fy = data.Fy_train.to(device)
+        self.sI = data.scalers_Y["I"]
+        if self.pinn:                    # the model's own (v, theta) outputs: their scalers
+            self.disp = (data.scalers_Y["deflections"], data.scalers_Y["rotations"])
+        else:                            # (the fused term reads raw float64 rows)
+            self.disp = (data.v_train.to(device=device, dtype=torch.float64).contiguous(),
+                         data.theta_train.to(device=device, dtype=torch.float64).contiguous())
+        self.x, self.fix = term.x.to(device=device, dtype=torch.float64), term.fix.to(device=device, dtype=torch.uint8)
+        self.E = torch.tensor(float(term.E), dtype=torch.float64, device=device)      # device scalars: nothing crosses PCIe
+        self.wy = torch.tensor(float(term.wy), dtype=torch.float64, device=device)    # inside a captured step
 
-    def physics_inputs(rows, out=None):
+    def inputs(self, rows, out=None):
         """Per-batch loads (and, for the I-only models, recorded displacement fields); `out`: the graph's static buffers.
         Fused term (csrc/beam_residual.hip ops_physics_loss_*): only the ROW INDICES travel -- the launches gather by them."""
-        if _FUSED_PHYS:
-            if fuse_gather:              # the front-end launch leaves the step's rows in g_idx
-                return (g_idx[:rows.numel()],)
+        if self.fused:
+            if self.g_idx is not None:   # the front-end launch leaves the step's rows in g_idx
+                return (self.g_idx[:rows.numel()],)
             if out is None:
                 return (rows,)
             out[0].copy_(rows)
             return out
-        srcs = (Fy_tr,) if kind == "pinn" else (Fy_tr, v_rec, t_rec)
+        srcs = (self.Fy,) if self.pinn else (self.Fy,) + self.disp
         if out is None:
             return tuple(t[rows] for t in srcs)
         for t, o in zip(srcs, out):
             torch.index_select(t, 0, rows, out=o)
         return out
 
-    def physics_loss(preds, pin):
-        nel = cfg.nelem
-        if _FUSED_PHYS:          # three launches; the value is already weighted and enters the total with weight one
+    def loss(self, preds, pin):
+        nel, term = self.nel, self.term
+        if self.fused:           # three launches; the value is already weighted and enters the total with weight one
             from .physics import fused_residual_term
-            disp = (sD, sR) if kind == "pinn" else (v_rec, t_rec)
-            return fused_residual_term(preds, nel, sI, disp, pin[0], Fy_tr, px, float(physics.E), pfix, float(physics.wy), physics.weight, loss_acc)
+            return fused_residual_term(preds, nel, self.sI, self.disp, pin[0], self.Fy, self.x, float(term.E), self.fix, float(term.wy),
+                                       term.weight, self.loss_acc)
+        from .physics import fe_residual_loss
         preds = preds.float()
-        I_p = sI.inverse_transform(preds[:, :nel]).clamp_min(1e-8)
-        if kind == "pinn":
-            v_p = sD.inverse_transform(preds[:, nel:2 * nel + 1])
-            t_p = sR.inverse_transform(preds[:, 2 * nel + 1:])
+        I_p = self.sI.inverse_transform(preds[:, :nel]).clamp_min(1e-8)
+        if self.pinn:
+            v_p = self.disp[0].inverse_transform(preds[:, nel:2 * nel + 1])
+            t_p = self.disp[1].inverse_transform(preds[:, 2 * nel + 1:])
         else:
             v_p, t_p = pin[1], pin[2]
-        return physics.weight * fe_residual_loss(I_p, v_p, t_p, px, pE, pfix, pin[0], pwy).float()
+        return term.weight * fe_residual_loss(I_p, v_p, t_p, self.x, self.E, self.fix, pin[0], self.wy).float()
 
-    if on_gpu and engine is None and switches.get("adam_zero") == "1":
-        opt.zero_grads = True            # `flat` starts zeroed (allocation) and every update leaves it zeroed
 
-    def fwd_bwd(Xb, Yb, noise_t, pin=None, prenoised=False):
+class _Step:
+    """One training step's state and its pieces: [fwd_bwd] (segment A), the gradient all-reduce, [apply_update] (segment B).
+    `_setup_step` sets every attribute; one that belongs to a path the run does not take is None (or False)."""
+
+    def kl_term(self):
+        from . import bayes as _bayes
+        kl = _bayes.bayesian_kl(self.model)
+        return self.cfg.bnn_kl_scale * (kl.detach() if self.bayes_hip is not None else kl)
+
+    def fwd_bwd(self, Xb, Yb, noise_t, pin=None, prenoised=False):
         """Segment A: local gradients of the mean batch loss into `flat`.  `prenoised`: Xb already is the gathered, noisy
-        (and, under autocast, bfloat16) batch written by `gather_noise` -- one launch outside the graph instead of six nodes."""
-        if engine is not None:           # batch and targets sit in the engine's buffers (engine.gather); every gradient is assigned
-            return engine.fwd_bwd(int(Yb.shape[0]))
+        (and, under autocast, bfloat16) batch written by the batch-assembly launch -- one launch outside the graph instead of six nodes."""
+        cfg, crit, loss_acc, flat = self.cfg, self.crit, self.loss_acc, self.flat
+        if self.engine is not None:      # batch and targets sit in the engine's buffers (engine.gather); every gradient is assigned
+            return self.engine.fwd_bwd(int(Yb.shape[0]))
         Xn = Xb if prenoised else Xb + torch.randn_like(Xb) * noise_t   # PINN:756
-        if not (on_gpu and opt.zero_grads):
+        if not (self.on_gpu and self.opt.zero_grads):
             flat.zero_()                                                 # optimizer.zero_grad() (GPU: the update launch zeroes `flat` behind itself)
-        with torch.autocast(device_type=device.type, dtype=autocast_dtype, enabled=use_ac):
+        alpha0 = cfg.initial_alpha if self.alpha_term else None
+        with torch.autocast(device_type=self.device.type, dtype=self.autocast_dtype, enabled=self.use_ac):
             head_loss = None
-            if head_loss_ok:
+            if self.head_loss_ok:
                 # Transformer-Diffusion fast path: the loss on the head's output tile, finished by the head's backward launch
-                from . import tfd_fused
-                tfd_fused.arm_head_loss(Yb, crit, cfg.initial_alpha if alpha_term else None, loss_acc)
-                preds = net(Xn)
-                head_loss = tfd_fused.take_head_loss()
-                if head_loss is None and fuse_gather:
+                self.tfd.arm_head_loss(Yb, crit, alpha0, loss_acc)
+                preds = self.model(Xn)
+                head_loss = self.tfd.take_head_loss()
+                if head_loss is None and self.fuse_gather:
                     # (with the batch assembled by the front-end launch the static target buffer `Yb` is never filled: the framework-side
                     #  loss below would be evaluated against stale targets -- fail loudly instead, ADVICE r04)
                     raise RuntimeError("the head's loss launch did not run although the front-end launch assembles the batch itself "
                                        "(criterion / shape mismatch in tfd_fused.arm_head_loss)")
             else:
-                preds = net(Xn)
+                preds = self.model(Xn)
             if head_loss is not None:
                 loss = head_loss
-            elif on_gpu and _FUSED_LOSS:       # value + d/d preds in one HIP pass instead of ~80 framework kernel nodes
-                loss = fused_loss(crit, preds, Yb, alpha0=cfg.initial_alpha if alpha_term else None, unit_grad=True, acc=loss_acc)
+            elif self.on_gpu and _FUSED_LOSS:       # value + d/d preds in one HIP pass instead of ~80 framework kernel nodes
+                loss = fused_loss(crit, preds, Yb, alpha0=alpha0, unit_grad=True, acc=loss_acc)
             else:
                 loss = crit(preds.float(), Yb)
-                if alpha_term:
+                if self.alpha_term:
                     loss = loss + (cfg.initial_alpha - crit.alpha) ** 2   # TFD:743 / FNN (constant 0: alpha never trains)
-            if bayes_kl:
-                kl = kl_term()
+            if self.bayes_kl:
+                kl = self.kl_term()
                 loss = loss + kl
                 if loss_acc is not None:
                     loss_acc.add_(kl.detach())
-        if physics is not None:
-            term = physics_loss(preds, pin)
+        if self.physics is not None:
+            term = self.physics.loss(preds, pin)
             # (with the running sum both launches have already added their values up: the step's scalar only roots the backward pass,
             #  so the two terms are tied without an addition node -- its value is then the data loss alone)
-            loss = _TieTerms.apply(loss, term) if (loss_acc is not None and _FUSED_PHYS) else loss + term
+            loss = _TieTerms.apply(loss, term) if (loss_acc is not None and self.physics.fused) else loss + term
         global _WGRAD_QUEUE
-        _WGRAD_QUEUE = [] if (g_stash and _GROUP_WGRAD) else None       # split-row weight gradients: one grouped launch after backward
+        _WGRAD_QUEUE = [] if (self.g_stash and _GROUP_WGRAD) else None       # split-row weight gradients: one grouped launch after backward
         try:
             # the root gradient is a persistent ones tensor: no ones_like() fill node per step.  (r03 kept the implicit form because the
             # explicit one "produced" NaNs in bias gradients of framework-path runs; the NaNs were the HIP runtime's captured-memset
             # defect under the framework's own bias-gradient reductions -- runtime.py item 2 -- and the root gradient only moved the
             # memory layout that decided which garbage their semaphores saw)
-            if fp16_scaler is not None:          # scaler.scale(loss).backward() (PINN:761): the root gradient IS the scale
-                loss.backward(gradient=torch.full((), fp16_scaler["scale"], dtype=loss.dtype, device=device))
+            if self.fp16_scaler is not None:     # scaler.scale(loss).backward() (PINN:761): the root gradient IS the scale
+                loss.backward(gradient=torch.full((), self.fp16_scaler["scale"], dtype=loss.dtype, device=self.device))
             elif _EXPLICIT_ROOT:
-                loss.backward(gradient=_root_ones(device))
+                loss.backward(gradient=_root_ones(self.device))
             else:
                 loss.backward()
-            flush_wgrad_queue(device)
+            flush_wgrad_queue(self.device)
         finally:
             _WGRAD_QUEUE = None
-        if g_stash:                      # the shadow-linear weight / bias gradients: one multi-tensor cast-and-copy into `flat`
-            live = [(dd, ss) for dd, ss in zip(g_dst, g_stash) if ss is not None]      # (a product nobody called this step leaves None)
+        if self.g_stash:                      # the shadow-linear weight / bias gradients: one multi-tensor cast-and-copy into `flat`
+            live = [(dd, ss) for dd, ss in zip(self.g_dst, self.g_stash) if ss is not None]      # (a product nobody called this step leaves None)
             if live:
                 torch._foreach_copy_([dd for dd, _ in live], [ss for _, ss in live])
-            for k in range(len(g_stash)):
-                g_stash[k] = None
+            for k in range(len(self.g_stash)):
+                self.g_stash[k] = None
         return loss.detach()
 
-    def apply_update():
+    def apply_update(self):
         """Segment B: average over ranks, clip, Adam."""
-        if fp16_scaler is not None:
+        opt, flat, world = self.opt, self.flat, self.world
+        if self.fp16_scaler is not None:
             # scaler.unscale_ + clip + scaler.step + scaler.update (PINN:763-768): a non-finite gradient skips the step and halves the scale,
             # 2 000 clean steps in a row double it; the unscaling rides in the update launch's gradient scale
-            sc = fp16_scaler
+            sc = self.fp16_scaler
             sc["steps"] += 1
             if bool(torch.isfinite(flat).all()):
                 opt.step(grad_scale=1.0 / (world * sc["scale"]))
@@ -963,299 +826,468 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
                 flat.zero_()
                 sc["scale"] *= 0.5; sc["good"] = 0; sc["skipped"] += 1
             return
-        if on_gpu:
+        if self.on_gpu:
             opt.step(grad_scale=1.0 / world)                             # average, clip (PINN:766), Adam
             return
-        if dp:
+        if self.dp:
             flat.div_(world)
-        torch.nn.utils.clip_grad_norm_(params, 1.0)                      # PINN:766
+        torch.nn.utils.clip_grad_norm_(self.params, 1.0)                 # PINN:766
         opt.step()
 
-    def allreduce_grads():
+    def allreduce_grads(self):
         """ONE flat all-reduce of every parameter gradient (2.38 MB PINN / 1.44 MB TFD)."""
         if _DP_ASYNC:
-            dist.all_reduce(flat, async_op=True).wait()                  # GPU: stream ordering only, the host does not block
+            dist.all_reduce(self.flat, async_op=True).wait()             # GPU: stream ordering only, the host does not block
         else:
-            dist.all_reduce(flat)
+            dist.all_reduce(self.flat)
 
-    def train_step(Xb, Yb, noise_t, rows=None):
-        if engine is not None:
-            engine.gather(Xtr, Ytr, rows, noise_t, engine_seed)
-        loss = fwd_bwd(Xb, Yb, noise_t, physics_inputs(rows) if physics is not None else None)
-        if dp:
-            allreduce_grads()                                            # the step's only collective (RCCL over xGMI)
-        apply_update()
+    def train_step(self, Xb, Yb, noise_t, rows=None):
+        """The eager step (no graph, or a batch size no graph was captured for)."""
+        if self.engine is not None:
+            self.engine.gather(self.Xtr, self.Ytr, rows, noise_t, self.engine_seed)
+        loss = self.fwd_bwd(Xb, Yb, noise_t, self.physics.inputs(rows) if self.physics is not None else None)
+        if self.dp:
+            self.allreduce_grads()                                       # the step's only collective (RCCL over xGMI)
+        self.apply_update()
         return loss
 
-    def val_batch(Xb, Yb):
-        with torch.no_grad(), torch.autocast(device_type=device.type, dtype=autocast_dtype, enabled=use_ac):
-            preds = model(Xb)
-            if on_gpu and _FUSED_LOSS:
-                v = fused_loss(crit, preds, Yb)
-            else:
-                v = crit(preds.float(), Yb)
-            return v + kl_term() if bayes_kl else v                       # BTFD:772
 
-    # Transformer-Diffusion fast path: the validation pass as ONE forward over all validation rows (chunks of <= _VAL_CHUNK rows, whole
-    # reference batches each) + the loss per reference batch on row slices of its output, every value added to `acc` by the loss launch
-    # itself.  The reference's value -- the mean over its batches of the batch losses (TFD:760-775) -- is kept; a step-sized forward
-    # fills 1/18 of the chip, so 20 of them in a row cost ~8x what one 20-fold forward does.  (Rows are independent in evaluation mode;
-    # the diffusion draws of the pass come from one call of the stream instead of one per batch.)
-    val_whole = bool(on_gpu and fast_encoder is not None and _FUSED_LOSS and switches.get("val_whole") == "1")
-    _VAL_CHUNK = cfg.batch_size * max(1, 4096 // max(cfg.batch_size, 1))
-
-    def val_all(acc):
-        nva = int(Xva.shape[0])
-        with torch.no_grad(), torch.autocast(device_type=device.type, dtype=autocast_dtype, enabled=use_ac):
-            for c0 in range(0, nva, _VAL_CHUNK):
-                preds = model(Xva[c0:c0 + _VAL_CHUNK])
-                for b0 in range(c0, min(c0 + _VAL_CHUNK, nva), cfg.batch_size):
-                    b1 = min(b0 + cfg.batch_size, nva)
-                    fused_loss(crit, preds[b0 - c0:b1 - c0], Yva[b0:b1], acc=acc)
-
+def _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use_graph, physics, init_fn) -> _Step:
+    """Model, criterion, flat gradient buffer, optimiser and whichever hand-written pieces the run is eligible for; the data set on the device."""
+    st = _Step()
+    st.kind, st.seed = kind, seed
+    st.cfg = cfg = cfg or {"pinn": PinnConfig, "tfd": TfdConfig, "fnn": FnnConfig, "gnn": GnnConfig, "fno": FnoConfig, "btfd": BtfdConfig,
+                           "btfdm": BtfdmConfig}[kind]()
+    st.alpha_term = kind in ("tfd", "fnn", "fno", "btfd", "btfdm")    # (initial_alpha - alpha)^2 in the training loss (TFD:743, FNO:615, BTFD:730)
+    st.bayes_kl = bayes_kl = kind in ("btfd", "btfdm") and cfg.kl == "gaussian"
+    if kind in ("btfd", "btfdm") and cfg.kl not in ("none", "gaussian"):
+        raise ValueError(f"kl must be 'none' or 'gaussian', not {cfg.kl!r}")
+    if kind == "fno":
+        autocast_dtype = None                           # FNO:613 runs with autocast disabled
+    st.autocast_dtype = autocast_dtype
+    st.device = device = torch.device(device)
+    st.world = world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    st.rank = rank = dist.get_rank() if world > 1 else 0
+    # the data-parallel branch: more than one rank -- or, with OPS_AMD_FORCE_DP=1, a process group of ONE rank (r05: the RCCL path -- flat
+    # all-reduce between graph A and graph B, its async form, the one-graph capture of the collective, dp_segments -- executed on the
+    # single GPU a test box has; a one-rank all-reduce is the identity and 1 / world = 1, so losses equal the plain run bit for bit)
+    st.dp = dp = world > 1 or (_FORCE_DP and dist.is_available() and dist.is_initialized())
+    st.engine_seed = (seed * 7919 + 13 + rank) & 0x7FFFFFFFFFFFFFFF       # the batch-assembly launches' noise stream, whichever launch it is
+    torch.manual_seed(seed)            # identical initial weights on every rank
+    model, crit = build_model_and_loss(kind, cfg, data, device)
+    st.tfd = tfd_fused = None
+    if kind == "tfd" and device.type == "cuda":
+        from . import tfd_fused          # (here and not at the top: a CPU-only process never needs it)
+        st.tfd = tfd_fused
+        tfd_fused.disarm_gather()        # (whatever an earlier run that did not reach its end left armed)
+    if init_fn is not None:
+        init_fn(model)
+    st.bayes_hip = None
+    if kind in ("btfd", "btfdm") and device.type == "cuda":
+        # the four Bayesian layers: one sampling launch per forward, one fold launch per backward (bayes.py, csrc/bayes_mlp.hip); with
+        # the KL term on, the fold adds its gradient and the loss its (detached) value
+        from . import bayes as _bayes
+        st.bayes_hip = _bayes.BayesSampler(model, seed=seed * 7919 + 307 + rank, kl_scale=cfg.bnn_kl_scale if bayes_kl else 0.0)
+        model.bayes_sampler = st.bayes_hip
+    if sync_bn and dp:
+        model = nn.SyncBatchNorm.convert_sync_batchnorm(model)
+    st.model, st.crit = model, crit
+    # one flat gradient buffer; every .grad is a view into it (autograd accumulates in place)
+    st.params = params = [q for q in model.parameters()]
+    st.flat = flat = torch.zeros(sum(q.numel() for q in params), device=device, dtype=torch.float32)
+    off = 0
+    for q in params:
+        q.grad = flat[off:off + q.numel()].view_as(q)
+        off += q.numel()
+    st.g_stash, st.g_dst, st.patched = [], [], []
+    st.fast_encoder = None
+    st.shared_counter = False
+    if hasattr(model, "direct_param_grads"):   # fused tails (csrc/fused_bn.hip) write BatchNorm parameter gradients into `flat` themselves
+        model.direct_param_grads = device.type == "cuda"
+    torch.manual_seed(seed + 1 + rank)  # different noise / shuffles per rank
+    st.on_gpu = on_gpu = device.type == "cuda"
+    # the reference's AMP mode: GradScaler(init_scale 65536, growth 2, backoff 0.5, growth interval 2000) -- torch.cuda.amp.GradScaler's defaults
+    st.fp16_scaler = {"scale": 65536.0, "good": 0, "skipped": 0, "steps": 0} if (on_gpu and autocast_dtype == torch.float16) else None
+    if st.fp16_scaler is not None:
+        use_graph = False                # the scale and the skip decision are per-step host state, like `scaler.step` / `scaler.update`
+    if use_graph is None:
+        use_graph = on_gpu and os.environ.get("OPS_AMD_GRAPH", "1") == "1"    # the step is launch-bound (~150 tiny kernels): replay it as HIP graphs
+    # under graph replay the learning rate must live in a device tensor, or the scheduler's updates would
+    # never reach the captured optimiser step
+    st.prep_counter = torch.zeros(2, dtype=torch.int64, device=device) if on_gpu else None     # batch assembly: [calls, workgroups done]
+    if on_gpu:      # clip + Adam over the flat buffers in two HIP launches; loss.alpha NOT included (PINN:696)
+        st.opt = opt = FlatClipAdam(params, flat, cfg.learning_rate, weight_decay=cfg.weight_decay, max_norm=1.0, decoupled=kind == "gnn")
+        st.sched = None
+        if _SHADOW_LINEAR and autocast_dtype == torch.bfloat16:
+            st.g_stash, st.g_dst, st.patched = enable_shadow_linears(model, opt, params, flat)
+            # csrc/seq_block.hip: attention, dropout + add + LayerNorm, ReLU + dropout, diffusion front end
+            if kind == "tfd" and tfd_fused.patch_model(model, seed=seed * 7919 + 211 + rank, direct_param_grads=True):
+                st.fast_encoder = model
+                opt.repack = getattr(model.transformer_encoder, "_ops_tile_entries", None)    # the Adam launch refreshes the layer kernels' weight tiles
+                if switches.get("fused_prep") == "1":
+                    # the batch-assembly launch advances its call counter once per step: the dropout / noise streams read that one
+                    tfd_fused.share_step_counter(model.transformer_encoder, st.prep_counter)
+                    st.shared_counter = True
+    else:
+        st.opt = opt = (torch.optim.AdamW if kind == "gnn" else torch.optim.Adam)(model.parameters(), lr=cfg.learning_rate,   # GNN:394
+                                                                                   weight_decay=cfg.weight_decay)
+        st.sched = ExponentialLR(opt, gamma=cfg.gamma)
+    # PINN: forward + loss + backward as 13 hand-written launches without autograd (pinn_fused.py / csrc/mlp_block.hip);
+    # the module keeps owning parameters and buffers, evaluation keeps running it
+    st.engine = engine = None
+    if on_gpu and kind == "pinn" and autocast_dtype == torch.bfloat16 and physics is None and not (sync_bn and dp):
+        from . import pinn_fused
+        if pinn_fused.eligible(model, crit, cfg.batch_size):
+            st.engine = engine = pinn_fused.PinnFusedStep(model, crit, seed=seed * 7919 + 101 + rank)
+            opt.repack = engine._repack      # the Adam launch refreshes the engine's bf16 weight copies
+            if not dp and switches.get("pinn_norm_fold") == "1":
+                # one rank: the gradients are final when the weight-gradient launch ends, so that launch leaves the clip norm's partial
+                # sums and the optimiser skips its norm launch (a node and ~4.5 us per step; data parallel: the norm is the all-reduced one)
+                opt.norm_ready_parts = engine.enable_norm(flat, opt.ws, opt.step_count, opt.betas)
+            if not dp and switches.get("pinn_repack_in_gather") == "1":
+                # one rank: the weight copies of step n ride on the batch-assembly launch of step n + 1 (adjacent launches that depend on
+                # nothing of each other: one node and ~5 us less per step); the optimiser call no longer rebuilds them
+                opt.repack = None
+                engine.repack_in_gather(opt.p)
+    if use_graph and on_gpu and engine is None and st.fast_encoder is None:
+        # a step the FRAMEWORK differentiates (comparator paths, the sibling surrogates): its multi-block reductions are only right under
+        # graph replay when captured memset nodes are (runtime.py item 2); the hand-written paths above contain none
+        from . import runtime
+        if not runtime.graph_memsets_replay_correctly(device):
+            use_graph = False
+            if log:
+                log(f"captured hipMemsetAsync nodes replay wrong values in this process ({runtime.PACKET_CAPTURE_ENV}=0 came after its "
+                    "first HIP call?): the framework-differentiated step runs eagerly")
+    st.use_graph = use_graph
+    st.Xtr, st.Ytr, st.Xva, st.Yva = (t.to(device) for t in (data.X_train, data.Y_train, data.X_val, data.Y_val))
+    Xtr, Ytr = st.Xtr, st.Ytr
+    nb_tr = max(1, (Xtr.shape[0] + cfg.batch_size - 1) // cfg.batch_size)
+    if dp:   # every rank must run the same number of steps (collectives inside backward)
+        # a one-row tail batch makes train-mode BatchNorm raise (as in the reference's single process); on one rank of a
+        # data-parallel job that exception would leave the other ranks waiting in the step's all-reduce: drop such a tail
+        if Xtr.shape[0] % cfg.batch_size == 1 and nb_tr > 1 and any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules()):
+            nb_tr -= 1
+        t = torch.tensor([nb_tr], device=device)
+        dist.all_reduce(t, op=dist.ReduceOp.MIN)
+        nb_tr = int(t.item())
+    st.nb_tr = nb_tr
+    st.use_ac = device.type == "cuda" and autocast_dtype is not None
+    # Transformer-Diffusion fast path, r04: the front-end launch assembles its own batch (rows order[cursor ..] of the training set + the
+    # input noise) and the head's loss reads its targets through those rows: no batch-assembly launch per step.  The epoch's permutation
+    # lives in `g_order`, `g_cursor` is advanced by the launch itself (reset per epoch).
+    st.fuse_gather = False
+    st.g_order = st.g_cursor = st.g_noise = st.g_idx = None
+    fused_phys = on_gpu and switches.get("fused_physics") == "1"      # A/B switch: 0 = physics.fe_residual_loss from framework ops
+    # the loss launch adds every step's value to the epoch's running sum itself (zeroed per epoch): no add node per step
+    # (with the fused physics term both launches add into the same running sum: the epoch's total of data loss + term)
+    st.loss_acc = loss_acc = torch.zeros((), dtype=torch.float32, device=device) if (
+        on_gpu and _FUSED_LOSS and engine is None and (physics is None or fused_phys) and switches.get("loss_acc") == "1") else None
+    # the loss on the head's tile: its value exists once the head's backward launch has run, so a second term can only be tied to it
+    # (not added) -- which needs the running sum to carry the step values
+    st.head_loss_ok = st.fast_encoder is not None and _FUSED_LOSS and (physics is None or (fused_phys and loss_acc is not None))
+    if (st.head_loss_ok and st.shared_counter and Xtr.dtype == torch.float32 and Xtr.dim() == 3
+            and Xtr.is_contiguous() and Ytr.dtype == torch.float32 and Ytr.is_contiguous() and Ytr.dim() == 2
+            and tfd_fused.gather_fusable(model, device, int(Xtr.shape[2]))):
+        st.fuse_gather = True
+        st.g_order = torch.arange(max(int(Xtr.shape[0]), cfg.batch_size), device=device) % int(Xtr.shape[0])
+        st.g_cursor = torch.zeros((), dtype=torch.int64, device=device)
+        st.g_noise = torch.zeros((), device=device)
+        st.g_idx = torch.zeros(max(cfg.batch_size, 1), dtype=torch.int64, device=device)
+        tfd_fused.arm_gather(model, Xtr, Ytr, st.g_order, st.g_cursor, st.g_idx, st.g_noise, st.engine_seed)
+    st.physics = _PhysicsInputs(physics, kind, cfg, data, device, fused_phys, st.g_idx, loss_acc) if physics is not None else None
+    if on_gpu and engine is None and switches.get("adam_zero") == "1":
+        opt.zero_grads = True            # `flat` starts zeroed (allocation) and every update leaves it zeroed
     # batch assembly in one launch (csrc/input_prep.hip): gather + noise + cast straight into the graph's input buffer
-    _FUSED_PREP = on_gpu and switches.get("fused_prep") == "1"
+    st.fused_prep = on_gpu and switches.get("fused_prep") == "1"
     # bf16 batches only where the first module is a (shadow) Linear, which casts its operand to bf16 anyway
-    prep_bf16 = bool(on_gpu and use_ac and autocast_dtype == torch.bfloat16 and patched and kind in ("pinn", "fnn", "gnn"))
+    st.prep_bf16 = bool(on_gpu and st.use_ac and autocast_dtype == torch.bfloat16 and st.patched and kind in ("pinn", "fnn", "gnn"))
+    st.y_in_prep = bool(on_gpu and Ytr.dtype == torch.float32 and Ytr.is_contiguous() and switches.get("prep_targets") == "1")      # the targets travel in the same launch
+    return st
 
-    engine_seed = (seed * 7919 + 13 + rank) & 0x7FFFFFFFFFFFFFFF
 
-    y_in_prep = bool(on_gpu and Ytr.dtype == torch.float32 and Ytr.is_contiguous() and switches.get("prep_targets") == "1")      # the targets travel in the same launch
+class _CapturedStep:
+    """The training step as HIP graphs over static buffers, and what feeds them: `graph` (the whole step; with `graph_b`: segment A, the
+    eager all-reduce, segment B), `graph_t` (the epoch's last, partial batch).  All None where the step runs eagerly."""
 
-    def gather_noise(idx, out, out_y=None):
-        """Returns whether the targets were gathered too (out_y given and float32)."""
-        if engine is not None:           # batch AND targets straight into the engine's layouts
-            engine.gather(Xtr, Ytr, idx, s_noise, engine_seed)
-            return True
-        lib = opt._lib
-        Fdim = 1
-        for d_ in Xtr.shape[1:]:
-            Fdim *= int(d_)
-        with_y = out_y is not None and y_in_prep and out_y.dtype == torch.float32 and out_y.is_contiguous()
-        Cdim = int(Ytr[0].numel()) if with_y else 0
-        with torch.cuda.device(device):
-            rc = lib.ops_gather_rows_noise_targets_f32(int(idx.numel()), Fdim, Xtr.data_ptr(), idx.data_ptr(), s_noise.data_ptr(),
-                                                       (seed * 7919 + 13 + rank) & 0x7FFFFFFFFFFFFFFF, prep_counter.data_ptr(), out.data_ptr(),
-                                                       int(out.dtype == torch.bfloat16), Ytr.data_ptr() if with_y else None, Cdim,
-                                                       out_y.data_ptr() if with_y else None, torch.cuda.current_stream(device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"ops_gather_rows_noise_targets_f32 failed with code {rc}")
-        return with_y
-
-    graph = graph_b = vgraph = graph_t = vgraph_t = slot_graph = vgraph_all = None
-    ev_graphs, val_rows = {}, None
-    # PINN: validation through the engine's evaluation pass (running statistics, no dropout) when the validation set has its layout
-    engine_eval = bool(engine is not None and switches.get("pinn_engine_eval") == "1" and Xva.dtype == torch.float32
-                       and Xva.is_contiguous() and Yva.dtype == torch.float32 and Yva.is_contiguous() and Xva.dim() == 2
-                       and cfg.batch_size <= _cabi_rows())
-    graph_mode_one = False
-    bs = cfg.batch_size
-    if use_graph and Xtr.shape[0] >= bs:
+    def __init__(self, st: _Step, log):
+        self.st = st
+        self.side = self.graph = self.graph_b = self.graph_t = None
+        self.one_graph = False           # the data-parallel step with its collective inside `graph`
+        self.sX = self.sY = self.sP = self.s_noise = self.s_loss = self.sXt = self.sYt = self.s_loss_t = None
+        device, engine, Xtr, Ytr, bs = st.device, st.engine, st.Xtr, st.Ytr, st.cfg.batch_size
+        if not (st.use_graph and Xtr.shape[0] >= bs):
+            return
         # static buffers + a few eager warm-up steps on a side stream, then capture one full-batch step:
-        # not dp -> one graph; dp -> [fwd_bwd] graph, eager all-reduce, [apply_update] graph
-        sX, sY = torch.zeros_like(Xtr[:bs], dtype=torch.bfloat16 if (_FUSED_PREP and prep_bf16) else Xtr.dtype), torch.zeros_like(Ytr[:bs])
-        s_noise = torch.zeros((), device=device)
-        sP = None
-        if physics is not None:                  # static per-batch physics inputs, gathered before every replay
-            sP = physics_inputs(torch.arange(bs, device=device))
-            if not fuse_gather:          # (fused batch assembly: the rows are the front-end launch's own index output)
-                sP = tuple(torch.zeros_like(t[:bs]) for t in sP)
-        snap = (copy.deepcopy(model.state_dict()), copy.deepcopy(opt.state_dict()))
-        side = torch.cuda.Stream(device=device)
+        # not dp -> one graph; dp -> one graph with the collective in it, or [fwd_bwd] graph, eager all-reduce, [apply_update] graph
+        from .runtime import capture_graph, try_capture
+        rewind = st.g_cursor.zero_ if st.fuse_gather else None
+        self.sX, self.sY = torch.zeros_like(Xtr[:bs], dtype=torch.bfloat16 if (st.fused_prep and st.prep_bf16) else Xtr.dtype), torch.zeros_like(Ytr[:bs])
+        self.s_noise = torch.zeros((), device=device)
+        if st.physics is not None:               # static per-batch physics inputs, gathered before every replay
+            self.sP = st.physics.inputs(torch.arange(bs, device=device))
+            if not st.fuse_gather:       # (fused batch assembly: the rows are the front-end launch's own index output)
+                self.sP = tuple(torch.zeros_like(t[:bs]) for t in self.sP)
+        snap = (copy.deepcopy(st.model.state_dict()), copy.deepcopy(st.opt.state_dict()))
+        self.side = side = torch.cuda.Stream(device=device)
+
+        def fwd(tail=False):
+            X, Y, P = (self.sXt, self.sYt, None) if tail else (self.sX, self.sY, self.sP)
+            return st.fwd_bwd(X, Y, self.s_noise, P, prenoised=st.fused_prep)
+
+        def step(tail=False, collective=False):
+            loss = fwd(tail)
+            if collective:
+                dist.all_reduce(st.flat)
+            st.apply_update()
+            return loss
+
+        def graphs():                    # the whole step; data parallel: segment A, and segment B behind the eager collective
+            ga, loss = capture_graph(side, device, fwd if st.dp else step)
+            return ga, loss, (capture_graph(side, device, st.apply_update)[0] if st.dp else None)
+
+        def tail_graph(nt):
+            self.sXt, self.sYt = (None if engine is not None else torch.zeros_like(self.sX[:nt])), torch.zeros_like(self.sY[:nt])
+            if engine is not None:       # the engine's own buffers are the graph's inputs: Yb only carries the row count
+                engine.gather(Xtr, Ytr, torch.arange(nt, device=device), self.s_noise, st.engine_seed)
+            else:
+                self.sXt.copy_(self.sX[:nt]); self.sYt.copy_(self.sY[:nt])
+            return capture_graph(side, device, lambda: step(tail=True), 2, rewind)
+
         side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):
-            sX.copy_(Xtr[:bs]); sY.copy_(Ytr[:bs])
-            if sP is not None:
-                physics_inputs(torch.arange(bs, device=device), out=sP)
+        with torch.cuda.stream(side):    # (capture_graph, called on the side stream, adds no waits of its own)
+            self.sX.copy_(Xtr[:bs]); self.sY.copy_(Ytr[:bs])
+            if self.sP is not None:
+                st.physics.inputs(torch.arange(bs, device=device), out=self.sP)
             if engine is not None:
-                engine.gather(Xtr, Ytr, torch.arange(bs, device=device), s_noise, engine_seed)
+                engine.gather(Xtr, Ytr, torch.arange(bs, device=device), self.s_noise, st.engine_seed)
             # (fused batch assembly: every launch advances g_cursor by its batch; warm-up and capture passes each start at row 0 so that no
             #  pass reads g_order past its end -- the kernel wraps as well, ops_tfd_front_args.n_order; the epoch loop zeroes it again)
             for _ in range(3):
-                if fuse_gather:
-                    g_cursor.zero_()
-                fwd_bwd(sX, sY, s_noise, sP, prenoised=_FUSED_PREP)
-                apply_update()                   # warm-up only: no collective needed for capture-readiness
-            if fuse_gather:
-                g_cursor.zero_()
+                if rewind:
+                    rewind()
+                step()                           # warm-up only: no collective needed for capture-readiness
+            if rewind:
+                rewind()
             side.synchronize()
-            try:
-                graph = torch.cuda.CUDAGraph()
-                one_graph = False
-                if dp and _DP_ONE_GRAPH and dist.get_backend() == "nccl":
-                    try:                 # the collective inside the capture: one replay per step, no host work between the segments
-                        g1 = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g1, stream=side, capture_error_mode="thread_local"):
-                            s_loss = fwd_bwd(sX, sY, s_noise, sP, prenoised=_FUSED_PREP)
-                            dist.all_reduce(flat)
-                            apply_update()
-                        graph, one_graph = g1, True
-                        graph_mode_one = True
-                    except Exception as e:
-                        if log:
-                            log(f"capturing the gradient all-reduce failed ({e!r}); two graphs around an eager collective")
-                        torch.cuda.synchronize(device)
-                        graph = torch.cuda.CUDAGraph()
-                if not one_graph:
-                    with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                        s_loss = fwd_bwd(sX, sY, s_noise, sP, prenoised=_FUSED_PREP)
-                        if not dp:
-                            apply_update()
-                    if dp:
-                        graph_b = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(graph_b, stream=side, capture_error_mode="thread_local"):
-                            apply_update()
-            except Exception as e:          # same arithmetic eagerly; the step is then launch-bound
-                if log:
-                    log(f"HIP graph capture failed ({e!r}); training eagerly")
-                graph = graph_b = None
-                torch.cuda.synchronize(device)
+            got = None
+            if st.dp and _DP_ONE_GRAPH and dist.get_backend() == "nccl":
+                # the collective inside the capture: one replay per step, no host work between the segments
+                got = try_capture("the step with its gradient all-reduce", "two graphs around an eager collective", log, device,
+                                  lambda: capture_graph(side, device, lambda: step(collective=True)) + (None,))
+                self.one_graph = got is not None
+            if got is None:                  # on failure: the same arithmetic eagerly; the step is then launch-bound
+                got = try_capture("the training step", "training eagerly", log, device, graphs)
+            if got is not None:
+                self.graph, self.s_loss, self.graph_b = got
             # the epoch's LAST (partial) batch as a graph of its own: an eager step is ~25 launches' worth of host time (0.3-0.4 ms of a
             # 5 ms TFD epoch), and eager model passes between replays are what the flaky-NaN hunt of r03 kept running into
             nt = int(Xtr.shape[0]) % bs
-            if (graph is not None and not dp and sP is None and nt >= 2 and nb_tr == Xtr.shape[0] // bs + 1
+            if (self.graph is not None and not st.dp and self.sP is None and nt >= 2 and st.nb_tr == Xtr.shape[0] // bs + 1
                     and switches.get("tail_graph") == "1"):
-                try:
-                    sXt, sYt = (None if engine is not None else torch.zeros_like(sX[:nt])), torch.zeros_like(sY[:nt])
-                    if engine is not None:       # the engine's own buffers are the graph's inputs: Yb only carries the row count
-                        engine.gather(Xtr, Ytr, torch.arange(nt, device=device), s_noise, engine_seed)
-                    else:
-                        sXt.copy_(sX[:nt]); sYt.copy_(sY[:nt])
-                    for _ in range(2):
-                        if fuse_gather:
-                            g_cursor.zero_()
-                        fwd_bwd(sXt, sYt, s_noise, None, prenoised=_FUSED_PREP)
-                        apply_update()
-                    if fuse_gather:
-                        g_cursor.zero_()
-                    side.synchronize()
-                    graph_t = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph_t, stream=side, capture_error_mode="thread_local"):
-                        s_loss_t = fwd_bwd(sXt, sYt, s_noise, None, prenoised=_FUSED_PREP)
-                        apply_update()
-                except Exception as e:
-                    if log:
-                        log(f"HIP graph capture of the tail batch failed ({e!r}); that step runs eagerly")
-                    graph_t = None
-                    torch.cuda.synchronize(device)
+                got = try_capture("the tail batch", "that step runs eagerly", log, device, lambda: tail_graph(nt))
+                if got is not None:
+                    self.graph_t, self.s_loss_t = got
         torch.cuda.current_stream(device).wait_stream(side)
-        model.load_state_dict(snap[0]); opt.load_state_dict(snap[1])     # the warm-up steps never happened
-        if on_gpu:
-            opt.refresh_shadow()
-            if engine is not None:
-                engine.repack_now()
-            if fast_encoder is not None:
-                from . import tfd_fused
-                tfd_fused.refresh_layer_tiles(fast_encoder.transformer_encoder)
-        # the validation pass as graphs too (eval mode, loss accumulated into v_acc): one for the full batches, one for the last partial one
+        st.model.load_state_dict(snap[0]); st.opt.load_state_dict(snap[1])     # the warm-up steps never happened
+        st.opt.refresh_shadow()
+        if engine is not None:
+            engine.repack_now()
+        if st.fast_encoder is not None:
+            st.tfd.refresh_layer_tiles(st.fast_encoder.transformer_encoder)
+
+    def feed(self, idx, sX, sY):
+        """Rows `idx` of the training set into the static buffers of the full-batch graph (sX, sY) or of the tail graph (sXt, sYt)."""
+        st, Xtr, Ytr = self.st, self.st.Xtr, self.st.Ytr
+        if st.fuse_gather:               # the captured step's first launch assembles the batch itself
+            return
+        if st.engine is not None:        # batch AND targets straight into the engine's layouts (no physics term with the engine)
+            st.engine.gather(Xtr, Ytr, idx, self.s_noise, st.engine_seed)
+            return
+        with_y = False
+        if st.fused_prep:                # gather + noise (+ bf16 cast) and, where they are float32, the targets in one launch
+            from . import _cabi
+            with_y = st.y_in_prep and sY.dtype == torch.float32 and sY.is_contiguous()
+            with torch.cuda.device(st.device):
+                rc = st.opt._lib.ops_gather_rows_noise_targets_f32(
+                    int(idx.numel()), int(Xtr[0].numel()), Xtr.data_ptr(), idx.data_ptr(), self.s_noise.data_ptr(), st.engine_seed,
+                    st.prep_counter.data_ptr(), sX.data_ptr(), int(sX.dtype == torch.bfloat16), Ytr.data_ptr() if with_y else None,
+                    int(Ytr[0].numel()) if with_y else 0, sY.data_ptr() if with_y else None, torch.cuda.current_stream(st.device).cuda_stream)
+            _cabi.check(rc, "ops_gather_rows_noise_targets_f32")
+        else:
+            torch.index_select(Xtr, 0, idx, out=sX)                      # gather straight into the graph's input buffers
+        if not with_y:
+            torch.index_select(Ytr, 0, idx, out=sY)
+        if self.sP is not None:          # (full batches only: no tail graph is captured with a physics term)
+            st.physics.inputs(idx, out=self.sP)
+
+
+class _Validation:
+    """The epoch's validation pass, `run()`, in the one of four modes the run is eligible for: the engine's evaluation slots in one graph;
+    the engine's pass per batch (graphs keyed by row count, eager otherwise); one forward over the whole set (`val_whole`), captured or
+    eager; the module per batch (graphs keyed by row count, eager otherwise).  The constructor captures what its mode replays."""
+
+    def __init__(self, st: _Step, cap: _CapturedStep, log):
+        self.st, cfg, engine, Xva, Yva = st, st.cfg, st.engine, st.Xva, st.Yva
+        self.nb_va = max(1, (Xva.shape[0] + cfg.batch_size - 1) // cfg.batch_size)
+        # Transformer-Diffusion fast path: the validation pass as ONE forward over all validation rows (chunks of <= `chunk` rows, whole
+        # reference batches each) + the loss per reference batch on row slices of its output, every value added to `acc` by the loss launch
+        # itself.  The reference's value -- the mean over its batches of the batch losses (TFD:760-775) -- is kept; a step-sized forward
+        # fills 1/18 of the chip, so 20 of them in a row cost ~8x what one 20-fold forward does.  (Rows are independent in evaluation mode;
+        # the diffusion draws of the pass come from one call of the stream instead of one per batch.)
+        self.val_whole = bool(st.on_gpu and st.fast_encoder is not None and _FUSED_LOSS and switches.get("val_whole") == "1")
+        self.chunk = cfg.batch_size * max(1, 4096 // max(cfg.batch_size, 1))
+        # PINN: validation through the engine's evaluation pass (running statistics, no dropout) when the validation set has its layout
+        self.engine_eval = bool(engine is not None and switches.get("pinn_engine_eval") == "1" and Xva.dtype == torch.float32
+                                and Xva.is_contiguous() and Yva.dtype == torch.float32 and Yva.is_contiguous() and Xva.dim() == 2
+                                and cfg.batch_size <= _cabi_rows())
+        self.slot_graph = self.vgraph_all = self.val_rows = self.v_acc = None
+        self.ev_graphs, self.vgraphs = {}, {}    # row count -> (graph, static row indices) of the engine / (graph, static batch, targets) of the module
+        if cap.graph is None:
+            return
+        # the pass as graphs too (evaluation mode, loss accumulated on the device): one for the full batches, one for the last partial one
+        from .runtime import capture_graph, try_capture
+        side, device, bs = cap.side, st.device, cfg.batch_size
         nvt = int(Xva.shape[0]) % bs
-        if engine_eval and graph is not None and switches.get("pinn_eval_slots") == "1":
+        if self.engine_eval and switches.get("pinn_eval_slots") == "1":
             # PINN: the whole validation set per launch sequence -- every batch in an evaluation slot (pinn_fused.make_eval_slots:
             # gathered once, the rows never change), the engine's 7 evaluation launches run all slots side by side (grid.y): 7 nodes
             # per epoch instead of 14 batches x 8 launches of ~6 us
-            try:
-                side.wait_stream(torch.cuda.current_stream(device))
-                with torch.cuda.stream(side):
-                    engine.make_eval_slots(Xva, Yva, cfg.batch_size)
-                    engine.evaluate_slots()
-                    side.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                        engine.evaluate_slots()
-                torch.cuda.current_stream(device).wait_stream(side)
-                slot_graph = g
-            except Exception as e:
-                if log:
-                    log(f"HIP graph capture of the slotted evaluation pass failed ({e!r}); one batch after the other")
-                slot_graph = None
-                torch.cuda.synchronize(device)
-        if engine_eval and graph is not None and slot_graph is None:
+            def slots():
+                engine.make_eval_slots(Xva, Yva, bs)
+                return capture_graph(side, device, engine.evaluate_slots, 1)
+            got = try_capture("the slotted evaluation pass", "one batch after the other", log, device, slots)
+            self.slot_graph = got[0] if got is not None else None
+        if self.engine_eval and self.slot_graph is None:
             # PINN: the engine's own evaluation pass (forward stages on the running statistics + loss, 8 launches per batch) instead of
             # the module's ~30-node forward; gather + evaluate captured per batch size, the row indices in a static buffer
-            val_rows = torch.arange(Xva.shape[0], device=device)
+            self.val_rows = torch.arange(Xva.shape[0], device=device)
             for n in sorted({bs if Xva.shape[0] >= bs else 0, nvt} - {0}):
-                try:
-                    vi = val_rows[:n].clone()
-                    side.wait_stream(torch.cuda.current_stream(device))
-                    with torch.cuda.stream(side):
-                        engine.gather(Xva, Yva, vi, None, 0); engine.evaluate(n)
-                        side.synchronize()
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                            engine.gather(Xva, Yva, vi, None, 0); engine.evaluate(n)
-                    torch.cuda.current_stream(device).wait_stream(side)
-                    ev_graphs[n] = (g, vi)
-                except Exception as e:
-                    if log:
-                        log(f"HIP graph capture of the engine's evaluation pass failed ({e!r}); those batches run eagerly")
-                    torch.cuda.synchronize(device)
-        elif graph is not None and (Xva.shape[0] >= bs or nvt >= 1):
-            v_acc = torch.zeros((), device=device)
-            net.eval()
+                vi = self.val_rows[:n].clone()
+                got = try_capture("the engine's evaluation pass", "those batches run eagerly", log, device,
+                                  lambda: capture_graph(side, device, lambda: (engine.gather(Xva, Yva, vi, None, 0), engine.evaluate(n)), 1))
+                if got is not None:
+                    self.ev_graphs[n] = (got[0], vi)
+        elif Xva.shape[0] >= bs or nvt >= 1:
+            # the module's pass.  (Also captured next to a slot graph, where run() never replays it: inherited, and dropping those set-up
+            # launches is a change of its own.)
+            self.v_acc = v_acc = torch.zeros((), device=device)
+            st.model.eval()
 
-            def capture_val(rows):
+            def per_batch(rows):
                 bx, by = torch.zeros_like(Xva[:rows]), torch.zeros_like(Yva[:rows])
-                side.wait_stream(torch.cuda.current_stream(device))
-                with torch.cuda.stream(side), torch.no_grad():
-                    bx.copy_(Xva[:rows]); by.copy_(Yva[:rows])
-                    for _ in range(2):
-                        val_batch(bx, by)
-                    side.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                        v_acc.add_(val_batch(bx, by))
-                torch.cuda.current_stream(device).wait_stream(side)
-                return g, bx, by
+                bx.copy_(Xva[:rows]); by.copy_(Yva[:rows])
+                graph, _ = capture_graph(side, device, lambda: v_acc.add_(self._batch(bx, by)), 2, warm=lambda: self._batch(bx, by))
+                return graph, bx, by
 
-            def capture_val_all():
-                side.wait_stream(torch.cuda.current_stream(device))
-                with torch.cuda.stream(side):
-                    for _ in range(2):
-                        val_all(v_acc)
-                    side.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
-                        val_all(v_acc)
-                torch.cuda.current_stream(device).wait_stream(side)
-                return g
-
-            try:
-                if val_whole:
-                    vgraph_all = capture_val_all()
+            def graphs():
+                if self.val_whole:
+                    self.vgraph_all = capture_graph(side, device, lambda: self._whole(v_acc), 2)[0]
                 elif Xva.shape[0] >= bs:
-                    vgraph, vX, vY = capture_val(bs)
-                if not val_whole and nvt >= 1 and not dp and switches.get("tail_graph") == "1":
-                    vgraph_t, vXt, vYt = capture_val(nvt)
-            except Exception as e:
-                if log:
-                    log(f"HIP graph capture of the validation pass failed ({e!r}); evaluating eagerly")
-                vgraph = vgraph_t = vgraph_all = None
-                torch.cuda.synchronize(device)
+                    self.vgraphs[bs] = per_batch(bs)
+                if not self.val_whole and nvt >= 1 and not st.dp and switches.get("tail_graph") == "1":
+                    self.vgraphs[nvt] = per_batch(nvt)
+                return True
+            if try_capture("the validation pass", "evaluating eagerly", log, device, graphs) is None:
+                self.vgraph_all = None
+                self.vgraphs.clear()
             v_acc.zero_()
-            net.train()
+            st.model.train()
 
+    def _batch(self, Xb, Yb):
+        st = self.st
+        with torch.no_grad(), torch.autocast(device_type=st.device.type, dtype=st.autocast_dtype, enabled=st.use_ac):
+            preds = st.model(Xb)
+            if st.on_gpu and _FUSED_LOSS:
+                v = fused_loss(st.crit, preds, Yb)
+            else:
+                v = st.crit(preds.float(), Yb)
+            return v + st.kl_term() if st.bayes_kl else v                 # BTFD:772
+
+    def _whole(self, acc):
+        st, Xva, Yva, bs = self.st, self.st.Xva, self.st.Yva, self.st.cfg.batch_size
+        nva = int(Xva.shape[0])
+        with torch.no_grad(), torch.autocast(device_type=st.device.type, dtype=st.autocast_dtype, enabled=st.use_ac):
+            for c0 in range(0, nva, self.chunk):
+                preds = st.model(Xva[c0:c0 + self.chunk])
+                for b0 in range(c0, min(c0 + self.chunk, nva), bs):
+                    b1 = min(b0 + bs, nva)
+                    fused_loss(st.crit, preds[b0 - c0:b1 - c0], Yva[b0:b1], acc=acc)
+
+    def run(self):
+        """The summed validation loss of the epoch (a device scalar; the caller divides by `nb_va`)."""
+        st, engine, Xva, Yva, bs = self.st, self.st.engine, self.st.Xva, self.st.Yva, self.st.cfg.batch_size
+        if engine is not None and engine.repack_params is not None and self.engine_eval:
+            engine.repack_now()          # (the engine's evaluation launches read the weight copies: the last update's are not built yet)
+        vt = torch.zeros((), device=st.device)
+        if self.engine_eval and self.slot_graph is not None:
+            self.slot_graph.replay()
+            return engine.eval_slot_losses().sum()
+        if self.engine_eval:
+            engine.eval_loss_sum.zero_()
+            if self.val_rows is None:
+                self.val_rows = torch.arange(Xva.shape[0], device=st.device)
+            for b in range(self.nb_va):
+                rows = self.val_rows[b * bs:(b + 1) * bs]
+                gk = self.ev_graphs.get(int(rows.numel()))
+                if gk is not None:
+                    gk[1].copy_(rows)
+                    gk[0].replay()
+                else:
+                    engine.gather(Xva, Yva, rows, None, 0)
+                    engine.evaluate(int(rows.numel()))
+            return engine.eval_loss_sum.clone()
+        if self.val_whole:
+            if self.vgraph_all is None:
+                self._whole(vt)
+                return vt
+            self.vgraph_all.replay()
+        else:
+            for b in range(self.nb_va):
+                xb, yb = Xva[b * bs:(b + 1) * bs], Yva[b * bs:(b + 1) * bs]
+                gk = self.vgraphs.get(int(xb.shape[0]))
+                if gk is not None:
+                    gk[1].copy_(xb); gk[2].copy_(yb)
+                    gk[0].replay()
+                else:
+                    vt += self._batch(xb, yb)
+            if not self.vgraphs:
+                return vt
+        vt += self.v_acc                 # what the replays added up
+        self.v_acc.zero_()
+        return vt
+
+
+def _run_epochs(st: _Step, n_epochs: int, batch_order, log):
+    """The captures, then the epochs; returns (history, best validation loss, its state dict, the data-parallel profile's event quadruples
+    or None, the step's mode).  The graphs (and their private memory pools) belong to two objects that are locals of THIS frame and in no
+    reference cycle: they are gone when it returns, before anything else runs on the device."""
+    cap = _CapturedStep(st, log)
+    val = _Validation(st, cap, log)
     # "the warm-up steps never happened" for the dropout / noise streams too: their call counters go back to zero, so that a seeded run
     # draws the same masks however many warm-up and capture passes its launch mode needed (one graph, two graphs around the collective,
     # with or without a tail graph, eager) -- r05: the one-rank data-parallel run reproduces the plain run
-    if on_gpu:
-        prep_counter.zero_()
-        if engine is not None:
-            engine.drop_counter.zero_(); engine.prep_counter.zero_()
-        if fuse_gather:
-            g_cursor.zero_()
+    if st.on_gpu:
+        st.prep_counter.zero_()
+        if st.engine is not None:
+            st.engine.drop_counter.zero_(); st.engine.prep_counter.zero_()
+        if st.fuse_gather:
+            st.g_cursor.zero_()
+    cfg, device, model, opt, engine, loss_acc = st.cfg, st.device, st.model, st.opt, st.engine, st.loss_acc
+    Xtr, Ytr, bs, nb_tr, graph = st.Xtr, st.Ytr, st.cfg.batch_size, st.nb_tr, cap.graph
+    hist = {"train": [], "val": [], "epoch_s": []}
     best_val, best_state, no_improve = float("inf"), None, 0
-    n_epochs = max_epochs if max_epochs is not None else cfg.num_epochs
     # the epochs' shuffles come from a generator of their own: the framework's global one is consumed by eager steps (input noise,
     # framework dropout) but not by graph replays, so the batch order of epoch 2 would depend on which steps happened to run eagerly
     perm_gen = torch.Generator(device=device)
-    perm_gen.manual_seed(seed * 1000003 + 17 + rank)
-    seg_ev = [] if (_DP_PROFILE and on_gpu and graph is not None) else None      # per-step event quadruples (first epoch excluded below)
-    first_one_graph_replay = bool(graph_mode_one)        # the captured collective's first replay runs under the stall timer
+    perm_gen.manual_seed(st.seed * 1000003 + 17 + st.rank)
+    seg_ev = [] if (_DP_PROFILE and st.on_gpu and graph is not None) else None      # per-step event quadruples (first epoch excluded by the caller)
+    first_one_graph_replay = cap.one_graph               # the captured collective's first replay runs under the stall timer
+    own_sum = engine is not None or loss_acc is not None # a launch of the step adds its loss to the epoch's running sum itself
     for epoch in range(1, n_epochs + 1):
-        if device.type == "cuda":
+        if st.on_gpu:
             torch.cuda.synchronize(device)
         t0 = time.perf_counter()
-        net.train()
+        model.train()
         noise = cfg.sigma_0 * (cfg.gamma_noise ** epoch)                     # PINN:743
         if batch_order is not None:
             order = torch.as_tensor(batch_order(epoch), dtype=torch.long).reshape(-1).to(device)
@@ -1268,149 +1300,77 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
             loss_acc.zero_()                                                 # ... and so does the fused loss launch of the other loops
         noise_t = torch.tensor(noise, device=device)
         if graph is not None:
-            s_noise.copy_(noise_t)                                           # constant within the epoch
-        if fuse_gather:                                                      # the front-end launch walks this permutation with its own cursor
-            g_order[:order.numel()].copy_(order)
-            g_cursor.zero_()
-            g_noise.copy_(noise_t)
+            cap.s_noise.copy_(noise_t)                                       # constant within the epoch
+        if st.fuse_gather:                                                   # the front-end launch walks this permutation with its own cursor
+            st.g_order[:order.numel()].copy_(order)
+            st.g_cursor.zero_()
+            st.g_noise.copy_(noise_t)
         for b in range(nb_tr):
             # `order` is the DataLoader shuffle; permute_data (PINN:753) re-permutes inside the batch, which
             # changes neither the batch statistics nor the mean loss, so it is folded into `order`
             idx = order[b * bs:(b + 1) * bs]
             if graph is not None and idx.numel() == bs:
-                got_y = False
-                if fuse_gather:
-                    got_y = True                                             # (the captured step's first launch assembles the batch itself)
-                elif _FUSED_PREP or engine is not None:
-                    got_y = gather_noise(idx, sX, sY)                        # gather + noise (+ bf16 cast) + targets in one launch
-                else:
-                    torch.index_select(Xtr, 0, idx, out=sX)                  # gather straight into the graph's input buffers
-                if engine is None and not got_y:
-                    torch.index_select(Ytr, 0, idx, out=sY)
-                if sP is not None and not fuse_gather:
-                    physics_inputs(idx, out=sP)
+                cap.feed(idx, cap.sX, cap.sY)
                 if first_one_graph_replay:
                     first_one_graph_replay = False
                     with _StallGuard(_DP_STALL_S, "the first replay of the data-parallel step graph (gradient all-reduce captured)"):
                         graph.replay()
                         torch.cuda.synchronize(device)
-                    if engine is None and loss_acc is None:
-                        tot += s_loss
+                    if not own_sum:
+                        tot += cap.s_loss
                     continue
                 if seg_ev is not None and len(seg_ev) < 4096:
                     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
                     ev[0].record()
                     graph.replay()
                     ev[1].record()
-                    if graph_b is not None:
-                        allreduce_grads()
+                    if cap.graph_b is not None:
+                        st.allreduce_grads()
                         ev[2].record()
-                        graph_b.replay()
+                        cap.graph_b.replay()
                     else:
                         ev[2].record()
                     ev[3].record()
                     seg_ev.append(ev)
                 else:
                     graph.replay()
-                    if graph_b is not None:
-                        allreduce_grads()
-                        graph_b.replay()
-                if engine is None and loss_acc is None:
-                    tot += s_loss
-                if _DEBUG_NAN and engine is None:
-                    _debug_nan(model, opt, flat, s_loss, epoch, b, sX, sY)
-            elif graph_t is not None and idx.numel() == sYt.shape[0]:
-                got_y = False
-                if engine is not None:
-                    got_y = gather_noise(idx, None)                          # into the engine's buffers
-                elif fuse_gather:
-                    got_y = True
-                elif _FUSED_PREP:
-                    got_y = gather_noise(idx, sXt, sYt)
-                else:
-                    torch.index_select(Xtr, 0, idx, out=sXt)
-                if not got_y:
-                    torch.index_select(Ytr, 0, idx, out=sYt)
-                graph_t.replay()
-                if loss_acc is None and engine is None:
-                    tot += s_loss_t
-                if _DEBUG_NAN and engine is None:
-                    _debug_nan(model, opt, flat, s_loss_t, epoch, -b, sXt, sYt)
+                    if cap.graph_b is not None:
+                        st.allreduce_grads()
+                        cap.graph_b.replay()
+                step_loss, where = cap.s_loss, (b, cap.sX, cap.sY)
+            elif cap.graph_t is not None and idx.numel() == cap.sYt.shape[0]:
+                cap.feed(idx, cap.sXt, cap.sYt)
+                cap.graph_t.replay()
+                step_loss, where = cap.s_loss_t, (-b, cap.sXt, cap.sYt)
             elif engine is not None:
-                train_step(None, Ytr[:idx.numel()], noise_t, idx)            # Yb only carries the row count here
+                st.train_step(None, Ytr[:idx.numel()], noise_t, idx)         # Yb only carries the row count here
             else:
-                if shared_counter and not fuse_gather:
-                    prep_counter[0:1].add_(1)                                # (no batch-assembly launch on this path: advance the streams here)
-                step_loss = train_step(Xtr[idx], Ytr[idx], noise_t, idx)
-                if loss_acc is None:
-                    tot += step_loss
-                if _DEBUG_NAN and engine is None:
-                    _debug_nan(model, opt, flat, step_loss, epoch, -b, Xtr[idx], Ytr[idx])
+                if st.shared_counter and not st.fuse_gather:
+                    st.prep_counter[0:1].add_(1)                             # (no batch-assembly launch on this path: advance the streams here)
+                step_loss = st.train_step(Xtr[idx], Ytr[idx], noise_t, idx)
+                where = (-b, Xtr[idx], Ytr[idx]) if _DEBUG_NAN else None
+            if not own_sum:
+                tot += step_loss
+            if _DEBUG_NAN and engine is None:
+                _debug_nan(model, opt, st.flat, step_loss, epoch, *where)
         if engine is not None:
             tot = engine.loss_sum.clone()
         elif loss_acc is not None:
             tot = loss_acc.clone()
-        train_loss = _allreduce_mean(tot / nb_tr, world, dp)
-        if dp:   # BatchNorm running statistics are per rank during the epoch: average them before evaluating
+        train_loss = _allreduce_mean(tot / nb_tr, st.world, st.dp)
+        if st.dp:   # BatchNorm running statistics are per rank during the epoch: average them before evaluating
             for buf in model.buffers():
                 if buf.is_floating_point():
                     dist.all_reduce(buf)
-                    buf.div_(world)
-        net.eval()
-        if engine is not None and engine.repack_params is not None and engine_eval:
-            engine.repack_now()          # (the engine's evaluation launches read the weight copies: the last update's are not built yet)
-        vt = torch.zeros((), device=device)
-        nb_va = max(1, (Xva.shape[0] + cfg.batch_size - 1) // cfg.batch_size)
-        nb_run = nb_va
-        if engine_eval and slot_graph is not None:
-            slot_graph.replay()
-            nb_run = 0
-        elif engine_eval:
-            engine.eval_loss_sum.zero_()
-            if val_rows is None:
-                val_rows = torch.arange(Xva.shape[0], device=device)
-        elif val_whole:
-            if vgraph_all is not None:
-                vgraph_all.replay()
-                vt += v_acc
-                v_acc.zero_()
-            else:
-                val_all(vt)
-            nb_run = 0
-        for b in range(nb_run):
-            sl = slice(b * cfg.batch_size, (b + 1) * cfg.batch_size)
-            if engine_eval:
-                rows = val_rows[sl]
-                gk = ev_graphs.get(int(rows.numel()))
-                if gk is not None:
-                    gk[1].copy_(rows)
-                    gk[0].replay()
-                else:
-                    engine.gather(Xva, Yva, rows, None, 0)
-                    engine.evaluate(int(rows.numel()))
-                continue
-            if vgraph is not None and Xva[sl].shape[0] == bs:
-                vX.copy_(Xva[sl]); vY.copy_(Yva[sl])
-                vgraph.replay()
-            elif vgraph_t is not None and Xva[sl].shape[0] == vXt.shape[0]:
-                vXt.copy_(Xva[sl]); vYt.copy_(Yva[sl])
-                vgraph_t.replay()
-            else:
-                vt += val_batch(Xva[sl], Yva[sl])
-        if engine_eval and slot_graph is not None:
-            vt = engine.eval_slot_losses().sum()
-        elif engine_eval:
-            vt = engine.eval_loss_sum.clone()
-        elif (vgraph is not None or vgraph_t is not None) and not val_whole:
-            vt += v_acc
-            v_acc.zero_()
-        val_loss = _allreduce_mean(vt / nb_va, world, dp)
-        if sched is not None:
-            sched.step()                                                     # PINN:788
+                    buf.div_(st.world)
+        model.eval()
+        val_loss = _allreduce_mean(val.run() / val.nb_va, st.world, st.dp)
+        if st.sched is not None:
+            st.sched.step()                                                  # PINN:788
         else:
             opt.lr.mul_(cfg.gamma)                                           # ExponentialLR on the device scalar
         tl, vl = float(train_loss), float(val_loss)                          # the epoch's only host syncs
-        if device.type == "cuda":
+        if st.on_gpu:
             torch.cuda.synchronize(device)
         hist["train"].append(tl); hist["val"].append(vl); hist["epoch_s"].append(time.perf_counter() - t0)
         if vl < best_val:                                                    # PINN:791-799
@@ -1418,54 +1378,65 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
             best_state = copy.deepcopy(model.state_dict())
         else:
             no_improve += 1
-        if log and rank == 0:
+        if log and st.rank == 0:
             log(f"Epoch {epoch}/{n_epochs} | Train Loss={tl:.6f}, Val Loss={vl:.6f}, Time={hist['epoch_s'][-1]:.2f}s")
         if no_improve >= cfg.patience:
             break
-    # the captured graphs (and their private memory pools) go before anything else runs on this device: the closures above form
-    # reference cycles that would otherwise keep them alive until some later garbage collection
-    step_was_captured = graph is not None
-    graph = graph_b = vgraph = graph_t = vgraph_t = slot_graph = vgraph_all = None
-    ev_graphs.clear()
-    if on_gpu:
+    step_mode = "one graph incl. the all-reduce" if cap.one_graph else "graph A | all-reduce | graph B" if graph is not None else "eager"
+    return hist, best_val, best_state, seg_ev, step_mode
+
+
+def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *, autocast_dtype=torch.bfloat16,
+                     sync_bn: bool = False, max_epochs: Optional[int] = None, log=None, seed: int = 0,
+                     use_graph: Optional[bool] = None, physics: Optional[PhysicsTerm] = None,
+                     init_fn=None, batch_order=None) -> Dict[str, object]:
+    """Trains on THIS rank's `data` shard; uses DDP when torch.distributed is initialised with world_size > 1.
+    Returns history, best state dict, validation R^2 (I only) and per-epoch times.
+    `init_fn(model)`: called once on the freshly built model (load a checkpoint, deterministic test weights).
+    `batch_order(epoch) -> LongTensor[n_train]`: the epoch's sample order instead of a random permutation (the
+    reference's DataLoader shuffle, PINN:701, is unseeded; the golden-fixture tests replay the order it drew).
+    `autocast_dtype=torch.float16`: the reference's AMP mode (fp16 autocast + GradScaler, PINN:706, :759-768) on the framework modules; the
+    returned dict then carries `grad_scaler` = {"scale", "skipped_steps", "steps"}.
+    (An exception in `_run_epochs` skips the teardown below, as it always has: the next run's set-up disarms what this one left armed.)"""
+    st = _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use_graph, physics, init_fn)
+    cfg, model, device = st.cfg, st.model, st.device
+    hist, best_val, best_state, seg_ev, step_mode = _run_epochs(st, max_epochs if max_epochs is not None else cfg.num_epochs, batch_order, log)
+    if st.on_gpu:
         import gc
-        gc.collect()
+        gc.collect()                     # (no cycle of this module's making is left to collect; kept for whatever a model's own pieces form)
         torch.cuda.synchronize(device)
         # BLAS workspaces that were allocated while capturing live in the graphs' private pools but stay cached per (handle, stream):
         # a later run whose side stream gets the same id would hand that freed memory to its GEMMs as scratch space (seen as NaNs /
         # drifting losses in a framework-path TFD run after a fast-path one in the same process)
         clear_blas_workspaces()
-    disable_shadow_linears(patched)      # the returned model is a plain module again
-    if fast_encoder is not None:
-        from . import tfd_fused
-        tfd_fused.disarm_gather()
-        tfd_fused.unpatch_model(fast_encoder)
+    disable_shadow_linears(st.patched)   # the returned model is a plain module again
+    if st.fast_encoder is not None:
+        st.tfd.disarm_gather()
+        st.tfd.unpatch_model(st.fast_encoder)
     if hasattr(model, "direct_param_grads"):
         model.direct_param_grads = False
     if best_state is not None:
         model.load_state_dict(best_state)
     model.eval()
+    Xva, Yva, nel, sI = st.Xva, st.Yva, cfg.nelem, data.scalers_Y["I"]
     with torch.no_grad():
         preds = torch.cat([model(Xva[i:i + cfg.batch_size]).float() for i in range(0, Xva.shape[0], cfg.batch_size)])
-    nel = cfg.nelem
-    sI = data.scalers_Y["I"]
     p = sI.inverse_transform(preds[:, :nel]).clamp(0.0, 1e10)                # PINN:843-848
     t = sI.inverse_transform(Yva[:, :nel]).clamp(0.0, 1e10)
     # (the reference's evaluation block, PINN:815-852 / TFD:800-829: best checkpoint reloaded, evaluation-mode pass over the validation
     #  set in loader order, inertias un-standardised and clipped to [0, 1e10], r2_score on the raveled arrays)
     out = {"model": model, "history": hist, "best_val": best_val, "best_state": best_state, "r2_val_I": r2_score(t, p),
-           "val_pred_I": p, "val_true_I": t, "epochs": len(hist["train"]), "steps_per_epoch": nb_tr}
-    if fp16_scaler is not None:
-        out["grad_scaler"] = {"scale": fp16_scaler["scale"], "skipped_steps": fp16_scaler["skipped"], "steps": fp16_scaler["steps"]}
-    if dp:
-        out["dp_mode"] = {"world": world, "forced_one_rank": bool(world == 1), "backend": dist.get_backend(), "async": bool(_DP_ASYNC),
-                          "step": ("one graph incl. the all-reduce" if graph_mode_one else "graph A | all-reduce | graph B" if step_was_captured
-                                   else "eager")}
+           "val_pred_I": p, "val_true_I": t, "epochs": len(hist["train"]), "steps_per_epoch": st.nb_tr}
+    if st.fp16_scaler is not None:
+        out["grad_scaler"] = {"scale": st.fp16_scaler["scale"], "skipped_steps": st.fp16_scaler["skipped"], "steps": st.fp16_scaler["steps"]}
+    if st.dp:
+        out["dp_mode"] = {"world": st.world, "forced_one_rank": bool(st.world == 1), "backend": dist.get_backend(), "async": bool(_DP_ASYNC),
+                          "step": step_mode}
     if seg_ev:                           # mean device time of the step's segments over the profiled steps (first epoch's excluded)
-        use = seg_ev[nb_tr:] or seg_ev
+        use = seg_ev[st.nb_tr:] or seg_ev
         mean = lambda i, j: 1e3 * sum(e[i].elapsed_time(e[j]) for e in use) / len(use)      # noqa: E731
         out["dp_segments"] = {"steps": len(use), "step_us": mean(0, 3), "graph_a_us": mean(0, 1), "allreduce_us": mean(1, 2),
-                              "graph_b_us": mean(2, 3), "one_graph": bool(graph_mode_one), "world": world}
+                              "graph_b_us": mean(2, 3), "one_graph": step_mode.startswith("one graph"), "world": st.world}
     return out
 
 
