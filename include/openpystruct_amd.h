@@ -180,7 +180,12 @@ int ops_sizing_draw_cases_f64(long B, unsigned long long first_case, unsigned lo
  *   I_last  [B,Ne] float32 out: written ONCE per case, in the call in which it stops (patience or max_epochs): the
  *           inertias its last solve ran on.  The reference records shear / moment / displacements of that solve next to
  *           the I of one Adam step later (:189-208 vs :239); a caller reproduces them with one solve on (double)I_last.
- * Other arguments as in ops_beam_solve_batched_f64 (geometry, supports, loads) and ops_beam_sizing_step_vm32_f32 (state). */
+ * Other arguments as in ops_beam_solve_batched_f64 (geometry, supports, loads) and ops_beam_sizing_step_vm32_f32 (state).
+ * Ne <= 128 (the fused step holds two elements per lane): OPS_AMD_ERR_UNSUPPORTED above, whatever the tiling.  `tiling`: 0 = the
+ * row-staged 16-lane kernel for shared geometry and one constraint mask, the 16-lane kernel of the plain solve for per-case
+ * geometry (both up to Ne = 111), beyond that the first of 32 and 64 lanes per beam that fits; 8, 16, 32 or 64 = that tiling of
+ * the plain solve; 16 | OPS_AMD_TILING_ROWS = the row-staged kernel (OPS_AMD_ERR_UNSUPPORTED with per-case geometry or
+ * supports).  No other row-staged tiling runs a fused epoch: 8 | OPS_AMD_TILING_ROWS and 6 return OPS_AMD_ERR_UNSUPPORTED. */
 int ops_beam_sizing_epoch_f32(int B, int Ne, const double* x, long x_bstride, const double* E, long E_bstride,
                               const uint8_t* fix, long fix_bstride, const double* Fy, long Fy_bstride, const double* wy,
                               long wy_bstride, float* I, float* I_last, float* exp_avg, float* exp_avg_sq, float* best_loss,

@@ -61,6 +61,8 @@ __device__ __forceinline__ void step_case(int lane, long b, int Ne, const Sizing
     bc2s = (float)sqrt(1.0 - pow(hp.beta2, (double)(t + 1)));
     step_size = lr_t / bc1;
   }
+  // 1 - beta in double, rounded once: what torch hands addcmul_ / lerp_ (1.0f - 0.999f is 4.7e-5 off 0.001)
+  const float omb1 = (float)(1.0 - hp.beta1), omb2 = (float)(1.0 - hp.beta2);
   float lsum_I = 0.f, lsum_b = 0.f, lsum_s = 0.f;
   float Inew[K];
 #pragma unroll
@@ -81,8 +83,8 @@ __device__ __forceinline__ void step_case(int lane, long b, int Ne, const Sizing
       // d/dI: 1 - a_M * M^2 * 2E / den_b^2 - a_V * V^2 / den_s^2 * G * 0.03 * 0.5 / sqrt(I)
       const float g = 1.0f - (float)hp.alpha_moment * ((m * m) / (den_b * den_b)) * twoE -
                       (float)hp.alpha_shear * ((v * v) / (den_s * den_s)) * (Gf * (float)hp.area_coef * (0.5f / sq));
-      const float ea = (float)hp.beta1 * r.m[k] + (1.0f - (float)hp.beta1) * g;
-      const float es = (float)hp.beta2 * r.v[k] + (1.0f - (float)hp.beta2) * g * g;
+      const float ea = (float)hp.beta1 * r.m[k] + omb1 * g;
+      const float es = (float)hp.beta2 * r.v[k] + omb2 * g * g;
       a.exp_avg[o] = ea;
       a.exp_avg_sq[o] = es;
       const float denom = sqrtf(es) / bc2s + (float)hp.adam_eps;

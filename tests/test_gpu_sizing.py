@@ -100,8 +100,9 @@ def test_ops_shim_results_of_one_analyze_survive_the_next(oa):
 @pytest.mark.parametrize("patience,n", [(5, 32), (10, 6)])       # 32 cases at patience 5: BASELINE config 1 (SingleCore.py:257)
 def test_sizing_loop_vs_per_case_oracle(oa, patience, n):
     """Batched loop (HIP solve + HIP optimiser step) vs the reference's per-case torch-CPU loop restated in
-    oracle/sizing_oracle.py.  float32 optimiser arithmetic: sums are ordered differently on the GPU, so the
-    trajectories agree to float32 round-off accumulated over ~250 Adam steps, not bit for bit."""
+    oracle/sizing_oracle.py.  float32 optimiser arithmetic: one epoch agrees with torch's to a few float32 eps
+    (tests/test_gpu_sizing_step.py), but the loss is summed in another order on the GPU and the solves differ in their last
+    bits, so the trajectories agree to float32 round-off accumulated over ~250 Adam steps, not bit for bit."""
     from openpystruct_amd import sizing
     cfg = sizing.SizingConfig(patience=patience)
     cases = sizing.make_cases(n, cfg, seed=123)
