@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI, read from include/openpystruct_amd.h: the header is the one place where the entry points, their
-argument structs and the OPS_* constants are written down; nothing here repeats a field, an argument list or a value.
+argument structs and the OPS_* constants are written down; nothing here repeats a field, an argument list or a value.  Entry points
+added without touching that header's declarations come from extension headers next to it (EXTENSION_HEADER_PATHS), read the same way.
 
 The product path has NO CPU fallback: if the HIP shared library is missing or cannot be
 loaded this module raises, loudly, instead of computing anything elsewhere.
@@ -13,6 +14,8 @@ import types
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd.h")
+# additions to the C ABI that change no declaration of HEADER_PATH (and so not OPS_AMD_ABI_VERSION) have headers of their own
+EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_vjp.h"),)
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
 
@@ -111,16 +114,22 @@ def read_header(text: str) -> types.SimpleNamespace:
     return out
 
 
-def _read_abi() -> types.SimpleNamespace:
+def _read_abi(path: str = "") -> types.SimpleNamespace:
+    path = path or HEADER_PATH
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return read_header(f.read())
     except OSError as e:
-        raise ExtensionMissingError(f"{HEADER_PATH} not readable ({e}): the ctypes binding is derived from the C header") from e
+        raise ExtensionMissingError(f"{path} not readable ({e}): the ctypes binding is derived from the C header") from e
 
 
 _abi = _read_abi()
 EXPORTS = tuple(_abi.functions)     # every symbol include/openpystruct_amd.h declares
+_extensions = {path: _read_abi(path) for path in EXTENSION_HEADER_PATHS}      # prototypes only
+for _path, _ext in _extensions.items():
+    if _ext.structs or _ext.defines or set(_ext.functions) & set(EXPORTS):
+        raise ValueError(f"{_path}: an extension header declares new entry points and nothing else")
+EXTENSION_EXPORTS = tuple(name for _ext in _extensions.values() for name in _ext.functions)
 _struct = _abi.structs.__getitem__
 SizingParams = _struct("ops_sizing_params")
 PhysicsLossArgs = _struct("ops_physics_loss_args")
@@ -160,11 +169,12 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the machine
         raise ExtensionMissingError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (restype, argtypes) in _abi.functions.items():
+    declared = [(HEADER_PATH, _abi)] + list(_extensions.items())
+    for header, name, restype, argtypes in [(h, n, *sig) for h, abi in declared for n, sig in abi.functions.items()]:
         try:
             f = getattr(lib, name)
         except AttributeError as e:
-            raise ExtensionMissingError(f"{LIB_PATH} does not export {name}, which {HEADER_PATH} declares: rebuild with "
+            raise ExtensionMissingError(f"{LIB_PATH} does not export {name}, which {header} declares: rebuild with "
                                         "`python -m openpystruct_amd.build --force`") from e
         f.restype, f.argtypes = restype, argtypes
     if lib.ops_amd_abi_version() != ABI_VERSION:     # a stale build of another ABI must not be driven with today's argument lists

@@ -194,15 +194,30 @@ def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tens
         loads = loads.to(torch.float64).contiguous()
         lbs = topo.Nn * 3 if loads.dim() == 3 else 0
     if out is None:
-        f64 = dict(dtype=torch.float64, device=dev)
-        out = FrameSolution(torch.empty((B, topo.Nn, 3), **f64), torch.empty((B, topo.Ne, 6), **f64),
-                            torch.empty((B, topo.Ne), **f64), torch.empty((B, topo.Ne), **f64),
-                            torch.empty((B,), dtype=torch.int32, device=dev))
+        out = _empty_solution(topo, B, dev)
+    _run_solve(topo, I, loads, lbs, out, topo.d_w, "_ws")
+    return out
+
+
+def _empty_solution(topo: FrameTopology, B: int, dev) -> FrameSolution:
+    f64 = dict(dtype=torch.float64, device=dev)
+    return FrameSolution(torch.empty((B, topo.Nn, 3), **f64), torch.empty((B, topo.Ne, 6), **f64),
+                         torch.empty((B, topo.Ne), **f64), torch.empty((B, topo.Ne), **f64),
+                         torch.empty((B,), dtype=torch.int32, device=dev))
+
+
+def _run_solve(topo: FrameTopology, I: torch.Tensor, loads: torch.Tensor, lbs: int, out: FrameSolution, d_w: torch.Tensor,
+               cache_name: str) -> None:
+    """One call of the solve on the current stream, with the workspace and plan bookkeeping.  `cache_name`: the attribute of the
+    topology that keeps the workspaces of solves with this `d_w` -- the plan holds the consistent loads of the element loads
+    (csrc/frame_wave.hpp frame_plan_kernel: rhs_base), so a plan is kept only for the element loads it was built with."""
+    lib = _cabi.load()
+    B, dev = I.shape[0], I.device
     ws_bytes = int(lib.ops_frame_workspace_bytes(B, topo.n_eq, topo.kd))
     ws, flags, entry = None, 0, None
     if ws_bytes:       # factor storage + the topology's assembly plan: HBM workspace, cached on the topology PER STREAM (two solves on one
         # topology from different streams or threads must not share factor columns or plan)
-        cache = topo.__dict__.setdefault("_ws", {})
+        cache = topo.__dict__.setdefault(cache_name, {})
         key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
         entry = cache.get(key)
         if entry is None or entry[0].numel() < ws_bytes:
@@ -216,7 +231,7 @@ def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tens
     with torch.cuda.device(dev):
         rc = lib.ops_frame_solve_batched_f64_ex(
             B, topo.Nn, topo.Ne, topo.n_eq, topo.kd, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
-            topo.d_w.data_ptr(), topo.d_elem_eq.data_ptr(), topo.d_node_eq.data_ptr(), I.data_ptr(), loads.data_ptr(), lbs,
+            d_w.data_ptr(), topo.d_elem_eq.data_ptr(), topo.d_node_eq.data_ptr(), I.data_ptr(), loads.data_ptr(), lbs,
             out.disp.data_ptr(), out.forces.data_ptr(), out.V.data_ptr(), out.M.data_ptr(), out.status.data_ptr(),
             ws.data_ptr() if ws is not None else None, ws_bytes, torch.cuda.current_stream(dev).cuda_stream, flags)
     if entry is not None:
@@ -225,7 +240,88 @@ def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tens
         raise NotImplementedError(f"frame too large: n_eq={topo.n_eq}, half bandwidth={topo.kd} (half bandwidth <= 63: a (kd+6)-column ring, one "
                                   f"n_eq vector and two 24-column chunks must fit 160 KB of LDS; beyond 63, up to 1024: one n_eq vector and one column)")
     _cabi.check(rc, "ops_frame_solve_batched_f64")
-    return out
+
+
+class _AdjointTables(NamedTuple):
+    conn: torch.Tensor         # [Ne,2] int32
+    ptr: torch.Tensor          # [Nn+1] int32
+    idx: torch.Tensor          # [2 Ne] int32: 2 * element + end, per node in element order
+    zero_w: torch.Tensor       # [Ne,2] float64 zeros: the adjoint solve has no element loads
+
+
+def _adjoint_tables(topo: FrameTopology) -> _AdjointTables:
+    """What the VJP needs beyond the forward's arrays, built once per topology and kept on it (as `_ws` is)."""
+    t = topo.__dict__.get("_adj")
+    if t is None:
+        if topo.conn.min() < 0 or topo.conn.max() >= topo.Nn:
+            raise ValueError("conn names a node that does not exist")
+        ends = np.argsort(topo.conn.reshape(-1), kind="stable")          # entry 2 e + end of conn: sorted by node, element order within
+        ptr = np.zeros(topo.Nn + 1, dtype=np.int64)
+        np.cumsum(np.bincount(topo.conn.reshape(-1), minlength=topo.Nn), out=ptr[1:])
+        mk = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=topo.device)  # noqa: E731
+        t = topo.__dict__["_adj"] = _AdjointTables(mk(topo.conn, torch.int32), mk(ptr, torch.int32), mk(ends, torch.int32),
+                                                   torch.zeros((topo.Ne, 2), dtype=torch.float64, device=topo.device))
+    return t
+
+
+def frame_solve_vjp(topo: FrameTopology, I: torch.Tensor, disp: torch.Tensor, g_disp: Optional[torch.Tensor] = None,
+                    g_forces: Optional[torch.Tensor] = None, gV: Optional[torch.Tensor] = None, gM: Optional[torch.Tensor] = None,
+                    status: Optional[torch.Tensor] = None):
+    """Vector-Jacobian product of `frame_solve`: given the forward's `disp` [B,Nn,3] and the cotangents of disp
+    [B,Nn,3], forces [B,Ne,6], V and M [B,Ne] (None = zero), returns (gI [B,Ne], g_loads [B,Nn,3] per frame, status [B] int32).
+    Three launches on the current stream: the adjoint right-hand side, the solve once more (K is symmetric; its own workspace, no
+    element loads), the per-element contraction (csrc/frame_vjp.hip).  A frame whose factorisation fails has status != 0 and NaN rows;
+    `status` [B] int32: the forward's status, when given a frame that failed there gets a NaN gI row whatever its `disp` holds."""
+    lib = _cabi.load()
+    if not torch.is_tensor(I) or not I.is_cuda:
+        raise RuntimeError("frame_solve_vjp needs GPU tensors: openpystruct_amd has no CPU fallback")
+    if I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne:
+        raise ValueError(f"I must be float64 [B, {topo.Ne}]")
+    I = I.contiguous()
+    B, dev = I.shape[0], I.device
+    shapes = dict(disp=(B, topo.Nn, 3), g_disp=(B, topo.Nn, 3), g_forces=(B, topo.Ne, 6), gV=(B, topo.Ne), gM=(B, topo.Ne))
+
+    def dense(name, t):
+        if t is None:
+            return None
+        if t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != shapes[name]:
+            raise ValueError(f"{name} must be float64 {list(shapes[name])} on {dev}")
+        return t.contiguous()
+
+    disp, g_disp, g_forces, gV, gM = (dense(k, v) for k, v in (("disp", disp), ("g_disp", g_disp), ("g_forces", g_forces), ("gV", gV), ("gM", gM)))
+    if disp is None:
+        raise ValueError("disp: the forward's displacements are needed")
+    if status is not None:
+        if status.dtype != torch.int32 or status.device != dev or tuple(status.shape) != (B,):
+            raise ValueError(f"status must be int32 [{B}] on {dev}")
+        status = status.contiguous()
+    adj = _adjoint_tables(topo)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    rhs = torch.empty((B, topo.Nn, 3), dtype=torch.float64, device=dev)
+    gI = torch.empty((B, topo.Ne), dtype=torch.float64, device=dev)
+    if B == 0:
+        return gI, rhs, torch.empty((0,), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_adjoint_rhs_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+                                           adj.conn.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), I.data_ptr(), ptr(g_disp),
+                                           ptr(g_forces), ptr(gV), ptr(gM), rhs.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_adjoint_rhs_f64")
+    sol = _empty_solution(topo, B, dev)                     # disp = lambda; the adjoint's forces, V, M are not used
+    _run_solve(topo, I, rhs, topo.Nn * 3, sol, adj.zero_w, "_ws_adjoint")
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_grad_contract_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(),
+                                             disp.data_ptr(), sol.disp.data_ptr(), ptr(g_forces), ptr(gV), ptr(gM), ptr(status),
+                                             sol.status.data_ptr(), gI.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_grad_contract_f64")
+    return gI, sol.disp, sol.status
+
+
+def differentiable_frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tensor] = None) -> FrameSolution:
+    """`frame_solve` through the registered operator `openpystruct_amd::frame_solve` (torch_op.py): gradients reach I and, when
+    given, loads ([Nn,3] shared or [B,Nn,3]); status is not differentiable.  The graph keeps `topo` alive until it is freed."""
+    from . import torch_op
+    return torch_op.frame_solve_autograd(topo, I, loads)
 
 
 def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,

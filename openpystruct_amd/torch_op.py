@@ -9,13 +9,22 @@ The op is differentiable: its autograd formula calls a second r
 `openpystruct_amd::beam_solve_vjp` (csrc/beam_vjp.hip, with a fake implementation of its own), so forward and backward
 both trace under FakeTensor / `torch.compile` and capture into HIP graphs.  Gradients reach I, E, Fy and wy; a shared
 scalar E or wy receives the sum over all elements.  status is not differentiable; x and fix get no gradient, and x
-requiring one is an error rather than a silent None."""
+requiring one is an error rather than a silent None.
+
+`torch.ops.openpystruct_amd.frame_solve` / `frame_solve_vjp` are the same pair for the frame solve (DESIGN.md §9f,
+csrc/frame_vjp.hip).  Operator arguments are tensors and ints: the inertias, the loads and the
+integer under which the `FrameTopology` -- whose arrays and per-stream workspaces the solve uses -- is registered here, and
+its node count (the output shapes of the fake implementation); `frame_solve_autograd` (= `frames.differentiable_frame_solve`) fills them
+in.  Gradients reach I and loads; status is not differentiable."""
 from __future__ import annotations
 
+import itertools
+import weakref
 from typing import Optional, Tuple
 
 import torch
 
+from . import frames
 from .beam import beam_solve, beam_solve_vjp
 
 T = torch.Tensor
@@ -69,3 +78,76 @@ def _backward(ctx, gv, gt, gV, gM, gstatus):
 
 
 beam_solve_op.register_autograd(_backward, setup_context=_setup_context)
+
+
+# ---- the frame solve ----
+# A FrameTopology is host state (numpy arrays, the workspaces per stream): the operators name it by an integer, valid while the object lives.
+_topologies = weakref.WeakValueDictionary()
+_topology_ids = itertools.count(1)
+
+
+def _topology_id(topo: frames.FrameTopology) -> int:
+    tid = topo.__dict__.get("_op_id")
+    if tid is None:
+        tid = topo.__dict__["_op_id"] = next(_topology_ids)
+        _topologies[tid] = topo
+    return tid
+
+
+def _topology(tid: int) -> frames.FrameTopology:
+    topo = _topologies.get(tid)
+    if topo is None:
+        raise RuntimeError(f"openpystruct_amd::frame_solve: no live FrameTopology is registered as {tid}")
+    return topo
+
+
+@torch.library.custom_op("openpystruct_amd::frame_solve", mutates_args=(), device_types="cuda")
+def frame_solve_op(I: T, loads: T, n_nodes: int, topology: int) -> Tuple[T, T, T, T, T]:
+    topo = _topology(topology)
+    if n_nodes != topo.Nn:
+        raise ValueError(f"openpystruct_amd::frame_solve: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
+    s = frames.frame_solve(topo, I, loads)
+    return s.disp, s.forces, s.V, s.M, s.status
+
+
+@frame_solve_op.register_fake
+def _(I, loads, n_nodes, topology):
+    B, Ne = I.shape
+    return (I.new_empty((B, n_nodes, 3)), I.new_empty((B, Ne, 6)), I.new_empty((B, Ne)), I.new_empty((B, Ne)),
+            I.new_empty((B,), dtype=torch.int32))
+
+
+@torch.library.custom_op("openpystruct_amd::frame_solve_vjp", mutates_args=(), device_types="cuda")
+def frame_solve_vjp_op(I: T, disp: T, status: Optional[T], g_disp: Optional[T], g_forces: Optional[T], gV: Optional[T],
+                       gM: Optional[T], topology: int) -> Tuple[T, T, T]:
+    return frames.frame_solve_vjp(_topology(topology), I, disp, g_disp, g_forces, gV, gM, status)
+
+
+@frame_solve_vjp_op.register_fake
+def _(I, disp, status, g_disp, g_forces, gV, gM, topology):
+    return I.new_empty(I.shape), disp.new_empty(disp.shape), I.new_empty((I.shape[0],), dtype=torch.int32)
+
+
+def _frame_setup_context(ctx, inputs, output):
+    I, loads, n_nodes, topology = inputs
+    ctx.mark_non_differentiable(output[4])
+    ctx.save_for_backward(I, output[0], output[4])
+    # the operators name the topology by an integer that is valid while the object lives: the graph keeps it alive
+    ctx.topo, ctx.topology, ctx.loads_shared = _topologies.get(topology), topology, loads.dim() == 2
+
+
+def _frame_backward(ctx, g_disp, g_forces, gV, gM, gstatus):
+    I, disp, status = ctx.saved_tensors
+    gI, g_loads, _ = torch.ops.openpystruct_amd.frame_solve_vjp(I, disp, status, g_disp, g_forces, gV, gM, ctx.topology)
+    if ctx.needs_input_grad[1] and ctx.loads_shared:       # one [Nn,3] load set for the batch: the sum over the frames
+        g_loads = g_loads.sum(0)
+    return (gI if ctx.needs_input_grad[0] else None, g_loads if ctx.needs_input_grad[1] else None, None, None)
+
+
+frame_solve_op.register_autograd(_frame_backward, setup_context=_frame_setup_context)
+
+
+def frame_solve_autograd(topo: frames.FrameTopology, I: T, loads: Optional[T] = None) -> frames.FrameSolution:
+    if loads is None:
+        loads = topo.d_loads
+    return frames.FrameSolution(*torch.ops.openpystruct_amd.frame_solve(I, loads, topo.Nn, _topology_id(topo)))
