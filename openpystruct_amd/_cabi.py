@@ -15,7 +15,8 @@ import types
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd.h")
 # additions to the C ABI that change no declaration of HEADER_PATH (and so not OPS_AMD_ABI_VERSION) have headers of their own
-EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_vjp.h"),)
+EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_vjp.h"),
+                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_grad.h"))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
 
@@ -68,14 +69,17 @@ def _declarators(text: str, structs: dict, where: str, named: bool = True) -> li
     return out
 
 
-def read_header(text: str) -> types.SimpleNamespace:
+def read_header(text: str, known_structs: dict = None) -> types.SimpleNamespace:
     """Parse the text of a C header of the shape of include/openpystruct_amd.h into
          defines    {OPS_NAME: int}                        every `#define OPS_... <integer literal>`
          structs    {c_name: ctypes.Structure subclass}    every `typedef struct NAME { ... } NAME;`
          functions  {c_name: (restype, [argtypes])}        every prototype `RET ops_xxx(ARGS);`
     Comments, the other preprocessor lines and the `extern "C"` braces are dropped; every character that remains must belong to one
-    of the two declaration forms and every type word must be known, else ValueError with the offending text -- nothing is skipped."""
+    of the two declaration forms and every type word must be known, else ValueError with the offending text -- nothing is skipped.
+    `known_structs`: structs of a header this one includes (an extension header's argument lists may name them); they may be used, not
+    declared again, and are not part of the result."""
     out = types.SimpleNamespace(defines={}, structs={}, functions={})
+    scope = dict(known_structs or {})
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     if "\\\n" in text:
         raise ValueError("line continuation in the header")
@@ -100,35 +104,36 @@ def read_header(text: str) -> types.SimpleNamespace:
         pos = m.end()
         tag, body, name, ret, func, args = m.groups()
         if func is None:
-            if tag != name or name in out.structs:
+            if tag != name or name in scope:
                 raise ValueError(f"struct {tag}: typedef'd as {name}" if tag != name else f"struct {name} declared twice")
-            fields = [f for decl in body.split(";") if decl.strip() for f in _declarators(decl, out.structs, f"struct {name}")]
+            fields = [f for decl in body.split(";") if decl.strip() for f in _declarators(decl, scope, f"struct {name}")]
             camel = "".join(w.capitalize() for w in name[4 * name.startswith("ops_"):].split("_"))      # ops_tfd_head_bwd_args -> TfdHeadBwdArgs
-            out.structs[name] = type(camel, (ctypes.Structure,), {"_fields_": fields})
+            out.structs[name] = scope[name] = type(camel, (ctypes.Structure,), {"_fields_": fields})
         else:
             if func in out.functions:
                 raise ValueError(f"{func} declared twice")
-            params = [] if args.strip() == "void" else [_declarators(a, out.structs, func)[0][1] for a in args.split(",")]
-            restype = None if ret.split() == ["void"] else _declarators(ret, out.structs, func, named=False)[0][1]
+            params = [] if args.strip() == "void" else [_declarators(a, scope, func)[0][1] for a in args.split(",")]
+            restype = None if ret.split() == ["void"] else _declarators(ret, scope, func, named=False)[0][1]
             out.functions[func] = (restype, params)
     return out
 
 
-def _read_abi(path: str = "") -> types.SimpleNamespace:
+def _read_abi(path: str = "", known_structs: dict = None) -> types.SimpleNamespace:
     path = path or HEADER_PATH
     try:
         with open(path) as f:
-            return read_header(f.read())
+            return read_header(f.read(), known_structs)
     except OSError as e:
         raise ExtensionMissingError(f"{path} not readable ({e}): the ctypes binding is derived from the C header") from e
 
 
 _abi = _read_abi()
 EXPORTS = tuple(_abi.functions)     # every symbol include/openpystruct_amd.h declares
-_extensions = {path: _read_abi(path) for path in EXTENSION_HEADER_PATHS}      # prototypes only
+# prototypes and the argument structs that are new with them (they may name the main header's structs, not redeclare them)
+_extensions = {path: _read_abi(path, _abi.structs) for path in EXTENSION_HEADER_PATHS}
 for _path, _ext in _extensions.items():
-    if _ext.structs or _ext.defines or set(_ext.functions) & set(EXPORTS):
-        raise ValueError(f"{_path}: an extension header declares new entry points and nothing else")
+    if _ext.defines or set(_ext.functions) & set(EXPORTS):
+        raise ValueError(f"{_path}: an extension header declares new entry points and their argument structs, nothing else")
 EXTENSION_EXPORTS = tuple(name for _ext in _extensions.values() for name in _ext.functions)
 _struct = _abi.structs.__getitem__
 SizingParams = _struct("ops_sizing_params")
@@ -145,6 +150,7 @@ TfdFrontArgs = _struct("ops_tfd_front_args")
 TfdFrontBwdArgs = _struct("ops_tfd_front_bwd_args")
 BayesLayer = _struct("ops_bayes_layer")
 BayesMcArgs = _struct("ops_bayes_mc_args")
+SizingObjective = _extensions[EXTENSION_HEADER_PATHS[1]].structs["ops_sizing_objective"]
 # every OPS_AMD_X / OPS_X of the header as X: OK, ERR_*, FIX_*, ABI_VERSION, FRAME_REUSE_PLAN, MLP_*, BAYES_*, WGRAD_MAX_GROUP, ADAM_*, ...
 for _name, _value in _abi.defines.items():
     _short = _name[len("OPS_AMD_"):] if _name.startswith("OPS_AMD_") else _name[len("OPS_"):]

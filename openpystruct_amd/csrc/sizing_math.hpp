@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/openpystruct_amd.h"
 #include "lane_common.hpp"
 
@@ -44,8 +46,19 @@ __device__ __forceinline__ void load_case(int lane, long b, int Ne, const Sizing
   }
 }
 
-template <int K, class FV, class FM>
-__device__ __forceinline__ void step_case(int lane, long b, int Ne, const SizingArgs& a, const CaseRegs<K>& r, FV getV, FM getM) {
+// Where the Adam gradient of a case comes from, decided at compile time.  ExplicitGrad: the reference's explicit-terms formula
+// below (M and V held fixed).  GivenGrad: dL/dI computed elsewhere (csrc/sizing_grad.hip: explicit part + adjoint solve), rounded
+// to float32, plus a term the caller adds to the case's loss before the early-stop decision (extra; NULL: none).
+struct ExplicitGrad {};
+struct GivenGrad {
+  const double* grad;     // this case's row [Ne]
+  const double* extra;    // this case's entry, or NULL
+};
+
+template <int K, class FV, class FM, class FG = ExplicitGrad>
+__device__ __forceinline__ void step_case(int lane, long b, int Ne, const SizingArgs& a, const CaseRegs<K>& r, FV getV, FM getM,
+                                          FG gsrc = FG{}) {
+  constexpr bool kExplicit = std::is_same<FG, ExplicitGrad>::value;
   const ops_sizing_params& hp = a.hp;
   const int t = r.t;
   const float twoE = (float)(2.0 * hp.E), Gf = (float)hp.G;
@@ -81,8 +94,12 @@ __device__ __forceinline__ void step_case(int lane, long b, int Ne, const Sizing
       lsum_b += (m * m) / den_b;
       lsum_s += (v * v) / den_s;
       // d/dI: 1 - a_M * M^2 * 2E / den_b^2 - a_V * V^2 / den_s^2 * G * 0.03 * 0.5 / sqrt(I)
-      const float g = 1.0f - (float)hp.alpha_moment * ((m * m) / (den_b * den_b)) * twoE -
-                      (float)hp.alpha_shear * ((v * v) / (den_s * den_s)) * (Gf * (float)hp.area_coef * (0.5f / sq));
+      float g;
+      if constexpr (kExplicit)
+        g = 1.0f - (float)hp.alpha_moment * ((m * m) / (den_b * den_b)) * twoE -
+            (float)hp.alpha_shear * ((v * v) / (den_s * den_s)) * (Gf * (float)hp.area_coef * (0.5f / sq));
+      else
+        g = (float)gsrc.grad[e];
       const float ea = (float)hp.beta1 * r.m[k] + omb1 * g;
       const float es = (float)hp.beta2 * r.v[k] + omb2 * g * g;
       a.exp_avg[o] = ea;
@@ -94,7 +111,9 @@ __device__ __forceinline__ void step_case(int lane, long b, int Ne, const Sizing
       Inew[k] = In;
     }
   }
-  const float loss = wave_sum(lsum_I) + (float)hp.alpha_moment * wave_sum(lsum_b) + (float)hp.alpha_shear * wave_sum(lsum_s);
+  float loss = wave_sum(lsum_I) + (float)hp.alpha_moment * wave_sum(lsum_b) + (float)hp.alpha_shear * wave_sum(lsum_s);
+  if constexpr (!kExplicit)
+    if (gsrc.extra) loss += (float)*gsrc.extra;
   // early stopping (SingleCore.py:211-219), decided identically by every lane
   float best = r.best;
   int cnt = r.cnt;
@@ -124,11 +143,11 @@ __device__ __forceinline__ void step_case(int lane, long b, int Ne, const Sizing
 }
 
 // the stand-alone form: one case, Ne <= 512
-template <class FV, class FM>
-__device__ __forceinline__ void sizing_case(int lane, long b, int Ne, const SizingArgs& a, FV getV, FM getM) {
+template <class FV, class FM, class FG = ExplicitGrad>
+__device__ __forceinline__ void sizing_case(int lane, long b, int Ne, const SizingArgs& a, FV getV, FM getM, FG gsrc = FG{}) {
   CaseRegs<8> r;
   load_case<8>(lane, b, Ne, a, r);
-  step_case<8>(lane, b, Ne, a, r, getV, getM);
+  step_case<8>(lane, b, Ne, a, r, getV, getM, gsrc);
 }
 
 }  // namespace opsamd

@@ -324,12 +324,72 @@ def sizing_tiling(n_nodes: int, shared_geometry: bool = False) -> int:
     return 16 | TILING_ROWS if shared_geometry else 16
 
 
+GRADIENTS = ("explicit", "total")
+
+
+def _objective(gradient: str, alpha_deflection: float, deflection_limit: Optional[float]) -> tuple:
+    """The checked (gradient, alpha_deflection, deflection_limit) of a sizing run.  "explicit": the reference's gradient (M and V
+    held fixed), which cannot see a deflection term; "total": the gradient of the loss through the solve."""
+    if gradient not in GRADIENTS:
+        raise ValueError(f"gradient must be one of {GRADIENTS}, got {gradient!r}")
+    alpha_deflection = float(alpha_deflection)
+    if not alpha_deflection >= 0.0:
+        raise ValueError("alpha_deflection must be >= 0")
+    if alpha_deflection > 0.0:
+        if gradient == "explicit":
+            raise ValueError('alpha_deflection > 0 needs gradient="total": the deflection term depends on I only through the solve, '
+                             "the explicit gradient is blind to it")
+        if deflection_limit is None or not float(deflection_limit) > 0.0:
+            raise ValueError("alpha_deflection > 0 needs a deflection_limit > 0")
+    return gradient, alpha_deflection, float(deflection_limit) if alpha_deflection > 0.0 else 0.0
+
+
+def beam_sizing_gradient(x, E, I, fix, wy, sol: BeamSolution, hp, alpha_deflection: float = 0.0,
+                         deflection_limit: Optional[float] = None, active: Optional[torch.Tensor] = None,
+                         out: Optional[Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]] = None):
+    """dL/dI [B,Ne] of the sizing objective (float64, M, V and v as functions of I) from the forward solution `sol`
+    of `beam_solve(x, E, I, fix, Fy, wy)`: one launch (csrc/sizing_grad.hip).  `hp`: a `SizingConfig` or an `ops_sizing_params`.
+    Returns (grad, loss_extra, status): loss_extra [B] is the value of the deflection term (None when alpha_deflection == 0),
+    status [B] non-zero for a beam whose factorisation failed (its row is NaN).  Rows of cases with active[b] == 0 are not
+    written (`out` supplies the buffers to keep).  Asynchronous on the current stream."""
+    from .beam import _check_inputs
+    dev, B, Ne, x, E, I, fix, wy, _ = _check_inputs("beam_sizing_gradient", x, E, I, fix, wy)
+    N = Ne + 1
+    _, aD, vlim = _objective("total", alpha_deflection, deflection_limit)
+    hp = hp.c_params() if isinstance(hp, SizingConfig) else hp
+    for name, t, cols in (("sol.v", sol.v, N), ("sol.theta", sol.theta, N), ("sol.V", sol.V, Ne), ("sol.M", sol.M, Ne)):
+        if tuple(t.shape) != (B, cols) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {(B, cols)} on {dev}")
+    if active is not None and (tuple(active.shape) != (B,) or active.dtype != torch.uint8 or active.device != dev):
+        raise ValueError(f"active must be a uint8 tensor of shape {(B,)} on {dev}")
+    if out is None:
+        out = (torch.empty((B, Ne), dtype=torch.float64, device=dev),
+               torch.empty((B,), dtype=torch.float64, device=dev) if aD > 0.0 else None,
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    grad, extra, status = out
+    obj = _cabi.SizingObjective(alpha_deflection=aD, deflection_limit=vlim)
+    with torch.cuda.device(dev):
+        rc = _cabi.load().ops_beam_sizing_grad_f64(
+            B, Ne, x.data_ptr(), N if x.dim() == 2 else 0, E.data_ptr(), Ne if E.numel() != 1 else 0, I.data_ptr(), Ne,
+            fix.data_ptr(), N if fix.dim() == 2 else 0, wy.data_ptr(), Ne if wy.numel() != 1 else 0, sol.v.data_ptr(),
+            sol.theta.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), ctypes.byref(hp), ctypes.byref(obj),
+            active.data_ptr() if active is not None else None, grad.data_ptr(), extra.data_ptr() if extra is not None else None,
+            status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _cabi.check(rc, "ops_beam_sizing_grad_f64")
+    return grad, extra, status
+
+
 class SizingState:
     """Device-resident optimiser state of a shard (what the reference keeps per sample in Python objects)."""
 
-    def __init__(self, cases: Cases, cfg: SizingConfig, device: torch.device):
+    def __init__(self, cases: Cases, cfg: SizingConfig, device: torch.device, gradient: str = "explicit",
+                 alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
         B, N = cases.Fy.shape
         Ne = N - 1
+        self.objective = _objective(gradient, alpha_deflection, deflection_limit)
+        self._total = gradient == "total"
+        if self._total and Ne > 512:
+            raise ValueError(f'gradient="total" serves up to 512 elements per beam (the optimiser step kernel), got {Ne}')
         f64 = dict(dtype=torch.float64, device=device)
         f32 = dict(dtype=torch.float32, device=device)
         self.B, self.N, self.Ne, self.cfg, self.device = B, N, Ne, cfg, device
@@ -343,7 +403,7 @@ class SizingState:
         self.wy = torch.tensor(cfg.uniform_udl, **f64)
         self.I = torch.full((B, Ne), cfg.I_0, **f32)                    # I_tensor, :163
         # fused epochs keep no widened copy: the kernel records, once per case, the float32 inertias of its last solve
-        self._fused = _FUSED_EPOCH and Ne <= 128
+        self._fused = _FUSED_EPOCH and Ne <= 128 and not self._total
         self.I_last = torch.full((B, Ne), cfg.I_0, **f32) if self._fused else None
         self.I64 = None if self._fused else self.I.double()      # separate solve + step launches: the solver's input
         self.exp_avg = torch.zeros((B, Ne), **f32)
@@ -358,15 +418,24 @@ class SizingState:
         self.sol: Optional[BeamSolution] = None
         self._V = torch.empty((B, Ne), **f32)         # element end forces of the epoch's solve, rounded like :189-190
         self._M = torch.empty((B, Ne), **f32)
+        if self._total:      # the exact gradient of this epoch's loss and the value of its deflection term (csrc/sizing_grad.hip)
+            self._grad = torch.empty((B, Ne), **f64)
+            self._loss_extra = torch.zeros((B,), **f64) if self.objective[1] > 0.0 else None
+            self._obj = _cabi.SizingObjective(alpha_deflection=self.objective[1], deflection_limit=self.objective[2])
+            self._grad_status = torch.zeros((B,), dtype=torch.int32, device=device)
         self._status = torch.zeros((B,), dtype=torch.int32, device=device)
         self._hp = cfg.c_params()
         sched = np.zeros((max(int(cfg.max_e), 1), 2), dtype=np.float32)          # per-epoch step size / bias correction
         _cabi.load().ops_sizing_schedule_f32(ctypes.byref(self._hp), sched.ctypes.data)
         self._schedule = torch.as_tensor(sched, device=device)
 
-    def reset(self, cases: Cases, cfg: SizingConfig) -> bool:
+    def reset(self, cases: Cases, cfg: SizingConfig, gradient: str = "explicit", alpha_deflection: float = 0.0,
+              deflection_limit: Optional[float] = None) -> bool:
         """Re-arm this state IN PLACE for another shard of the same shape (the buffers a captured epoch graph points at stay
-        where they are).  False: the new cases do not fit these buffers (shape, shared geometry / supports, hyper-parameters)."""
+        where they are).  False: the new cases do not fit these buffers (shape, shared geometry / supports, hyper-parameters) or
+        the run asks for another gradient mode or objective than the captured launches carry."""
+        if _objective(gradient, alpha_deflection, deflection_limit) != self.objective:
+            return False
         if tuple(cases.Fy.shape) != (self.B, self.N) or bytes(cfg.c_params()) != bytes(self._hp) or int(cfg.max_e) != int(self.cfg.max_e):
             return False
         shared_geom = bool((cases.node_positions == cases.node_positions[:1]).all())
@@ -408,6 +477,25 @@ class SizingState:
                     torch.cuda.current_stream(self.device).cuda_stream)
             _cabi.check(rc, "ops_beam_sizing_epoch_f32")
             return
+        if self._total:
+            # three launches: the float64 solve on I64, dL/dI through it (explicit part + adjoint solve), the gradient-fed step
+            self.sol = beam_solve(self.x, self.E, self.I64, self.fix, self.Fy, self.wy, tiling=sizing_tiling(N), out=self.sol)
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                extra = self._loss_extra.data_ptr() if self._loss_extra is not None else None
+                rc = lib.ops_beam_sizing_grad_f64(
+                    self.B, Ne, self.x.data_ptr(), N if self.x.dim() == 2 else 0, self.E.data_ptr(), 0, self.I64.data_ptr(), Ne,
+                    self.fix.data_ptr(), N if self.fix.dim() == 2 else 0, self.wy.data_ptr(), 0, self.sol.v.data_ptr(),
+                    self.sol.theta.data_ptr(), self.sol.V.data_ptr(), self.sol.M.data_ptr(), ctypes.byref(self._hp),
+                    ctypes.byref(self._obj), self.active.data_ptr(), self._grad.data_ptr(), extra, self._grad_status.data_ptr(), stream)
+                _cabi.check(rc, "ops_beam_sizing_grad_f64")
+                rc = lib.ops_beam_sizing_step_grad_f32(
+                    self.B, Ne, self.I.data_ptr(), self.I64.data_ptr(), self.sol.V.data_ptr(), self.sol.M.data_ptr(),
+                    self._grad.data_ptr(), extra, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.best_loss.data_ptr(),
+                    self.patience_cnt.data_ptr(), self.epochs_run.data_ptr(), self.active.data_ptr(), self.last_loss.data_ptr(),
+                    None, None, ctypes.byref(self._hp), self._schedule.data_ptr(), stream)
+            _cabi.check(rc, "ops_beam_sizing_step_grad_f32")
+            return
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = lib.ops_beam_solve_forces_f32(
@@ -445,8 +533,12 @@ _POLL_FLAGS: Dict[tuple, tuple] = {}
 
 
 def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25, use_graph: bool = True,
-                   reuse: bool = False, record_loss: bool = False) -> SizingState:
-    """Run the sizing loop of every case to its early stop (or max_e).  Returns the final device state.  With `reuse` the
+                   reuse: bool = False, record_loss: bool = False, gradient: str = "explicit", alpha_deflection: float = 0.0,
+                   deflection_limit: Optional[float] = None) -> SizingState:
+    """Run the sizing loop of every case to its early stop (or max_e).  Returns the final device state.  `gradient`: "explicit"
+    steps on the reference's gradient (M and V held fixed: its loop, pinned bit for bit); "total" on the exact gradient of the
+    loss through the solve, three launches per epoch, and may add a serviceability term
+    `alpha_deflection * sum_n (max(0, |v_n| - deflection_limit) / deflection_limit)^2` to the loss.  With `reuse` the
     state buffers and the captured graph of the previous shard of the same shape are re-armed in place: tensors of an
     earlier returned state are then overwritten (`generate_dataset` copies what it hands out).  `record_loss` keeps every
     epoch's `total_loss` (SingleCore.py:199) per case in `state.loss_history` [epochs, B] (rows past a case's `epochs_run`
@@ -459,11 +551,11 @@ def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25
     st, graph = (None, None)
     if reuse and use_graph and poll_every > 1 and key in _EPOCH_GRAPHS:
         st, graph = _EPOCH_GRAPHS[key]
-        if not st.reset(cases, cfg):
+        if not st.reset(cases, cfg, gradient, alpha_deflection, deflection_limit):
             st, graph = None, None
             del _EPOCH_GRAPHS[key]
     if st is None:
-        st = SizingState(cases, cfg, device)
+        st = SizingState(cases, cfg, device, gradient, alpha_deflection, deflection_limit)
     if st.B == 0:
         return st
     epochs_done = 0
@@ -521,15 +613,18 @@ RECORD_KEYS = ("roller_x_locations", "force_x_locations", "force_values", "I_val
 
 def generate_dataset(n_cases: int, cfg: Optional[SizingConfig] = None, device="cuda", seed: int = 20250307,
                      rank: int = 0, world: int = 1, poll_every: int = 25,
-                     case_range: Optional[Tuple[int, int]] = None) -> Dict[str, object]:
+                     case_range: Optional[Tuple[int, int]] = None, gradient: str = "explicit", alpha_deflection: float = 0.0,
+                     deflection_limit: Optional[float] = None) -> Dict[str, object]:
     """The reference's `main()` (SingleCore.py:251-264) for this rank's shard: returns the 13 record fields
-    (SingleCore.py:235-249) as tensors / lists, plus `epochs_run`, `status` and the global case ids."""
+    (SingleCore.py:235-249) as tensors / lists, plus `epochs_run`, `status` and the global case ids.  `gradient`,
+    `alpha_deflection`, `deflection_limit`: as in `optimize_cases`."""
     cfg = cfg or SizingConfig()
     lo, hi = shard_range(n_cases, rank, world)
     if case_range is not None:               # a sub-range of this rank's shard (generate_dataset_to_files)
         lo, hi = lo + case_range[0], min(hi, lo + case_range[1])
     cases = make_cases(n_cases, cfg, seed, device=device, lo=lo, hi=hi)     # generated on the GPU: only the blocks this range touches
-    st = optimize_cases(cases, cfg, device, poll_every=poll_every, reuse=True)     # everything handed out below is a copy
+    st = optimize_cases(cases, cfg, device, poll_every=poll_every, reuse=True, gradient=gradient, alpha_deflection=alpha_deflection,
+                        deflection_limit=deflection_limit)     # everything handed out below is a copy
     sol = st.sol
     rot, defl = sol.theta.clone(), sol.v.clone()
     if cfg.zero_last_node:
@@ -660,7 +755,8 @@ def load_records(path: str, device="cpu") -> Dict[str, object]:
 
 
 def generate_dataset_to_files(n_cases: int, out_dir: str, cfg: Optional[SizingConfig] = None, device="cuda", seed: int = 20250307,
-                              rank: int = 0, world: int = 1, chunk: int = 100000, resume: bool = True) -> List[str]:
+                              rank: int = 0, world: int = 1, chunk: int = 100000, resume: bool = True, gradient: str = "explicit",
+                              alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None) -> List[str]:
     """`generate_dataset` for this rank's shard, flushed chunk by chunk (`save_records`) so that an interrupted run keeps
     what it has -- the reference writes ONE json at the very end (SingleCore.py:263) and loses everything on a crash
     (SURVEY section 5).  With `resume`, chunks whose file exists are skipped after checking that the file records the same
@@ -674,12 +770,15 @@ def generate_dataset_to_files(n_cases: int, out_dir: str, cfg: Optional[SizingCo
         path = os.path.join(out_dir, f"records_{lo + c0:09d}_{lo + c1:09d}.pt")
         files.append(path)
         meta = {"seed": int(seed), "n_cases": int(n_cases), "cfg": repr(cfg or SizingConfig()), "range": [lo + c0, lo + c1]}
+        if gradient != "explicit":      # (files of the default mode keep the meta they always had)
+            meta["objective"] = list(_objective(gradient, alpha_deflection, deflection_limit))
         if resume and os.path.exists(path):
             have = torch.load(path, map_location="cpu", weights_only=True).get("meta")
             if have != meta:      # a file of another dataset (seed / size / configuration): never mix silently
                 raise ValueError(f"{path} was generated with {have}, this run is {meta}; use another out_dir or resume=False")
             continue
-        rec = generate_dataset(n_cases, cfg, device, seed, rank, world, case_range=(c0, c1))
+        rec = generate_dataset(n_cases, cfg, device, seed, rank, world, case_range=(c0, c1), gradient=gradient,
+                               alpha_deflection=alpha_deflection, deflection_limit=deflection_limit)
         rec["meta"] = meta
         save_records(rec, path + ".tmp")
         os.replace(path + ".tmp", path)          # a file either is complete or does not exist

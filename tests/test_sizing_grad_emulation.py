@@ -1,0 +1,242 @@
+"""The exact-gradient sizing mode without a GPU: the gradient kernel's per-lane arithmetic
+(openpystruct_amd/csrc/sizing_grad_math.hpp over beam_adjoint.hpp) run lane by lane on the CPU (tests/csrc/emul_sizing_grad.cpp)
+against autograd of the float64 objective through the dense model (tests/sizing_total_ref.py), for every tiling the kernel is
+compiled for; that reference itself against central differences of the objective; the gradient-fed step's float64 reference
+against the explicit one and its float32 round-off; the C ABI of the two new entry points.  tests/test_gpu_sizing_total.py runs
+the kernels themselves."""
+import ctypes
+import os
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+from oracle import sizing_oracle as so
+from tests import sizing_step_cases as sc
+from tests import sizing_total_ref as tr
+from tests.beam_dense import cond_free, gI_term_scale, random_case
+
+torch = pytest.importorskip("torch")
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GRAD_TILINGS = [(16, 7), (32, 4), (64, 4), (64, 8), (64, 16)]   # csrc/sizing_grad.hip kGradTilings
+_emul = None
+
+
+def emul_lib():
+    """g++ build of tests/csrc/emul_sizing_grad.cpp (the recipe of tests/test_beam_vjp_emulation.py::emul_lib)."""
+    global _emul
+    if _emul is None:
+        src = os.path.join(ROOT, "tests", "csrc", "emul_sizing_grad.cpp")
+        hdrs = [os.path.join(ROOT, "openpystruct_amd", "csrc", h) for h in ("beam_math.hpp", "beam_adjoint.hpp", "sizing_grad_math.hpp")]
+        so_path = os.path.join(ROOT, "tests", "csrc", "libemul_sizing_grad.so")
+        if not os.path.exists(so_path) or os.path.getmtime(so_path) < max(os.path.getmtime(f) for f in [src] + hdrs):
+            subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", so_path, src])
+        _emul = ctypes.CDLL(so_path)
+        f = _emul.emul_beam_sizing_grad_f64
+        f.restype = ctypes.c_int
+        vp, lg = ctypes.c_void_p, ctypes.c_long
+        f.argtypes = [ctypes.c_int] * 4 + [vp, lg] * 4 + [vp] * 8
+    return _emul
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def obj_constants(hp, obj):
+    """The kernel's SizingObj from ops_sizing_params and the objective, as ops_beam_sizing_grad_f64 forms it."""
+    return np.array([hp.alpha_moment, hp.alpha_shear, 2.0 * hp.E, hp.bend_eps, hp.G * hp.area_coef, obj.alpha_deflection,
+                     obj.deflection_limit if obj.alpha_deflection > 0.0 else 1.0])
+
+
+def emul_grad(P, M, x, E, I, fix, outs, hp, obj):
+    B, Ne = I.shape
+    N = Ne + 1
+    x, I, v, th, V, Mm = (np.ascontiguousarray(a, dtype=np.float64) for a in (x, I) + tuple(outs))
+    E = np.ascontiguousarray(np.atleast_1d(np.asarray(E, dtype=np.float64)))
+    fix = np.ascontiguousarray(fix, dtype=np.uint8)
+    o = obj_constants(hp, obj)
+    grad, extra, st = np.empty((B, Ne)), np.empty(B), np.empty(B, dtype=np.int32)
+    rc = emul_lib().emul_beam_sizing_grad_f64(
+        P, M, B, Ne, _p(x), N if x.ndim == 2 else 0, _p(E), Ne if E.ndim == 2 else 0, _p(I), Ne, _p(fix),
+        N if fix.ndim == 2 else 0, _p(v), _p(th), _p(V), _p(Mm), _p(o), _p(grad), _p(extra), _p(st))
+    assert rc == 0, rc
+    return grad, extra, st
+
+
+def median_limit(v, fix):
+    """The batch median of |v| over the nodes that are free to deflect: about half of them are beyond it.  (A single element
+    between two supports has no such node: any limit, the term is zero.)"""
+    free = np.broadcast_to((np.asarray(fix) & 1) == 0, v.shape)
+    return float(np.median(np.abs(v[free]))) if free.any() else 1.0
+
+
+def grad_error(grad, r, x, I, wy):
+    """The gradient's error over what the adjoint's rounding scales with (tests.beam_dense.gI_term_scale of the objective's
+    own cotangents), as tests/test_beam_vjp_emulation.py measures gI."""
+    return float(np.linalg.norm(grad - r.grad) / max(np.linalg.norm(r.grad), gI_term_scale(x, I, wy, r.outs, r.cot)))
+
+
+@pytest.mark.parametrize("P,M", GRAD_TILINGS)
+@pytest.mark.parametrize("Ne", [1, 2, 5, 13, 100, 255, 1023])
+@pytest.mark.parametrize("per_beam", [False, True])
+@pytest.mark.parametrize("deflection", [False, True])
+def test_emulated_gradient_vs_autograd_of_the_objective(P, M, Ne, per_beam, deflection):
+    if P * M < Ne + 1:
+        pytest.skip("tiling too small for this Ne")
+    if Ne > 100 and P * M > 4 * (Ne + 1):
+        pytest.skip("covered by a tighter tiling")
+    rng = np.random.default_rng(1000 * Ne + P + M + per_beam)
+    B = 1 if Ne > 255 else 3
+    x, fix, I, Fy = random_case(rng, B, Ne, per_beam=per_beam)
+    E = 2.0e11
+    wy = rng.uniform(-2e3, 0, size=(B, Ne)) if per_beam else np.float64(-750.0)
+    hp = sc.beam_hp()
+    free_obj = tr.objective()
+    outs = tr.total_gradient_ref(x, E, I, fix, Fy, wy, hp, free_obj).outs
+    obj = tr.objective(100.0, median_limit(outs[0], fix)) if deflection else free_obj
+    r = tr.total_gradient_ref(x, E, I, fix, Fy, wy, hp, obj)
+    grad, extra, st = emul_grad(P, M, x, E, I, fix, r.outs, hp, obj)
+    assert (st == 0).all()
+    xs = x if x.ndim == 1 else x[0]
+    fs = fix if fix.ndim == 1 else fix[0]
+    tol = max(1e-8, 4e-16 * cond_free(xs, E, I[0], fs))
+    err = grad_error(grad, r, x, I, wy)
+    assert err < tol, (err, tol)
+    if deflection:
+        assert (r.loss_extra > 0).any() or Ne == 1
+        assert (np.abs(extra - r.loss_extra) <= 1e-12 * r.loss_extra).all(), (extra, r.loss_extra)
+    else:
+        assert (extra == 0.0).all()
+
+
+def test_emulated_gradient_singular_beam_is_nan():
+    x = np.linspace(0, 10, 11)
+    fix = np.zeros(11, dtype=np.uint8); fix[0] = fix[-1] = 1
+    I = np.full((2, 10), 0.1); I[0, 4] = -0.1
+    outs = (np.ones((2, 11)), np.ones((2, 11)), np.ones((2, 10)), np.ones((2, 10)))
+    grad, extra, st = emul_grad(16, 7, x, 2e11, I, fix, outs, sc.beam_hp(), tr.objective(10.0, 0.5))
+    assert st[0] != 0 and st[1] == 0
+    assert np.isnan(grad[0]).all() and np.isnan(extra[0])
+    assert np.isfinite(grad[1]).all() and np.isfinite(extra[1])
+
+
+def _gapped_limit(v, fix):
+    """A deflection limit near the median of |v| over the free nodes with no node close to it: the geometric mean of the two
+    neighbouring values, among the middle half of the sorted ones, that are furthest apart."""
+    free = np.broadcast_to((np.asarray(fix) & 1) == 0, v.shape)
+    a = np.sort(np.abs(v[free]))
+    a = a[a > 0]
+    lo, hi = len(a) // 4, 3 * len(a) // 4
+    k = lo + int(np.argmax(a[lo + 1:hi + 1] / a[lo:hi]))
+    return float(np.sqrt(a[k] * a[k + 1]))
+
+
+@pytest.mark.parametrize("deflection", [False, True])
+def test_reference_gradient_matches_central_differences_of_the_objective(deflection):
+    """Pins total_gradient_ref independently of autograd: directional derivatives against central differences of L (float64,
+    dense model).  Ne = 12, B = 4, relative step 1e-4, three random directions, agreement 2e-5 -- the figures of
+    tests/test_gpu_beam_grad.py::test_vjp_matches_central_differences_of_the_forward.  No node sits within 1e-3 v_lim of the
+    limit, where the deflection term's second derivative jumps."""
+    rng = np.random.default_rng(5)
+    B, Ne = 4, 12
+    x, fix, I, Fy = random_case(rng, B, Ne, per_beam=True)
+    wy = rng.uniform(-2e3, -100, size=(B, Ne))
+    hp, E = sc.beam_hp(), 2e11
+    v = tr.total_gradient_ref(x, E, I, fix, Fy, wy, hp, tr.objective()).outs[0]
+    obj = tr.objective(100.0, _gapped_limit(v, fix)) if deflection else tr.objective()
+    r = tr.total_gradient_ref(x, E, I, fix, Fy, wy, hp, obj)
+    if deflection:
+        free = (fix & 1) == 0
+        assert (np.abs(np.abs(v[free]) - obj.deflection_limit) >= 1e-3 * obj.deflection_limit).all()
+        beyond = (np.abs(v[free]) > obj.deflection_limit).mean()
+        assert 0.2 < beyond < 0.8, beyond
+        assert (r.loss_extra > 0).any()
+    np.testing.assert_allclose(r.loss, tr.total_loss(x, E, I, fix, Fy, wy, hp, obj), rtol=1e-14)
+    h = 1e-4
+    for _ in range(3):
+        dI = rng.standard_normal((B, Ne)) * I            # relative direction
+        fd = (tr.total_loss(x, E, I + h * dI, fix, Fy, wy, hp, obj).sum() - tr.total_loss(x, E, I - h * dI, fix, Fy, wy, hp, obj).sum()) / (2 * h)
+        assert abs(fd - (r.grad * dI).sum()) <= 2e-5 * abs(fd), (fd, (r.grad * dI).sum())
+
+
+def test_reference_gradient_is_explicit_part_plus_the_vjp_of_its_cotangents():
+    """The decomposition the kernel computes: dL/dI = explicit part + gI of the solve's VJP with (gv, 0, gV, gM)."""
+    from tests.test_beam_vjp_emulation import dense_reference
+    rng = np.random.default_rng(9)
+    B, Ne = 3, 20
+    x, fix, I, Fy = random_case(rng, B, Ne)
+    hp = sc.beam_hp()
+    v = tr.total_gradient_ref(x, 2e11, I, fix, Fy, -750.0, hp, tr.objective()).outs[0]
+    r = tr.total_gradient_ref(x, 2e11, I, fix, Fy, -750.0, hp, tr.objective(100.0, median_limit(v, fix)))
+    _, gI, _, _ = dense_reference(x, 2e11, I, fix, Fy, -750.0, r.cot)
+    np.testing.assert_allclose(r.explicit + gI, r.grad, rtol=1e-9, atol=1e-9 * np.abs(r.grad).max())
+
+
+def _step_inputs(Ne, t, B=13):
+    rng = np.random.default_rng([Ne, t, 3])
+    I, m, v = sc.optimiser_state(rng, B, Ne)
+    V, M = sc.random_forces(rng, B, Ne)
+    grad = rng.standard_normal((B, Ne)) * np.exp(rng.uniform(np.log(1e-2), np.log(1e2), size=(B, Ne)))
+    extra = rng.uniform(0.0, 50.0, size=B)
+    return I, m, v, V, M, grad, extra
+
+
+@pytest.mark.parametrize("hp_name", ["beam", "frame"])
+def test_step_reference_with_the_explicit_gradient_is_the_explicit_reference(hp_name):
+    hp = {"beam": sc.beam_hp, "frame": sc.frame_hp}[hp_name]()
+    I, m, v, V, M, _, _ = _step_inputs(37, 17)
+    B = I.shape[0]
+    t, best, cnt = np.full(B, 17), np.full(B, np.inf), np.zeros(B, dtype=np.int64)
+    ref = so.sizing_step_reference(I, m, v, V, M, t, best, cnt, hp)
+    g32 = (1.0 - ref["tM"] - ref["tV"]).astype(np.float32)
+    got = tr.step_grad_reference(I, m, v, V, M, g32, None, t, best, cnt, hp)
+    np.testing.assert_array_equal(got["loss"], ref["loss"])
+    for k in ("exp_avg", "exp_avg_sq", "I"):     # the explicit gradient rounded to float32 on its way in: 2^-24 relative
+        np.testing.assert_allclose(got[k], ref[k], rtol=4e-7, atol=4e-7 * np.abs(ref[k]).max())
+    with_extra = tr.step_grad_reference(I, m, v, V, M, g32, np.full(B, 2.5), t, best, cnt, hp)
+    np.testing.assert_allclose(with_extra["loss"], ref["loss"] + 2.5, rtol=1e-15)
+
+
+@pytest.mark.parametrize("hp_name", ["beam", "frame"])
+def test_float32_round_off_of_the_gradient_fed_step(hp_name):
+    """What float32 arithmetic alone does to the gradient-fed step, in eps32, measured as tests/test_sizing_step_reference.py
+    measures the explicit one: below the stand-alone kernels' bound sizing_step_cases.STEP_BOUND."""
+    hp = {"beam": sc.beam_hp, "frame": sc.frame_hp}[hp_name]()
+    worst = {}
+    for Ne in (1, 2, 63, 64, 65, 127, 128, 129, 511, 512):
+        for t in (0, 1, 17, hp.max_epochs - 1):
+            I, m, v, V, M, grad, extra = _step_inputs(Ne, t)
+            tt = np.full(I.shape[0], t)
+            for ex in (None, extra):
+                ref = tr.step_grad_reference(I, m, v, V, M, grad, ex, tt, np.full(I.shape[0], np.inf), 0 * tt, hp)
+                errs = so.sizing_step_errors(ref, I, m, v, *tr.step_grad_float32(I, m, v, V, M, grad, ex, tt, hp), hp)
+                for k, e in errs.items():
+                    worst[k] = max(worst.get(k, 0.0), e)
+    print(hp_name, "float32 restatement of the gradient-fed step:", worst)
+    assert max(worst.values()) < sc.STEP_BOUND, worst
+
+
+def test_new_entry_points_are_declared_by_an_extension_header():
+    from openpystruct_amd import _cabi
+    assert {"ops_beam_sizing_grad_f64", "ops_beam_sizing_step_grad_f32"} <= set(_cabi.EXTENSION_EXPORTS)
+    assert [n for n, _ in _cabi.SizingObjective._fields_] == ["alpha_deflection", "deflection_limit"]
+    assert ctypes.sizeof(_cabi.SizingObjective) == 16
+    header = _cabi._extensions[_cabi.EXTENSION_HEADER_PATHS[-1]]
+    restype, argtypes = header.functions["ops_beam_sizing_grad_f64"]
+    assert restype is ctypes.c_int
+    assert argtypes[16] == ctypes.POINTER(_cabi.SizingParams) and argtypes[17] == ctypes.POINTER(_cabi.SizingObjective)
+
+
+def test_objective_arguments_are_checked_on_the_host():
+    from openpystruct_amd import sizing
+    assert sizing._objective("explicit", 0.0, None) == ("explicit", 0.0, 0.0)
+    assert sizing._objective("total", 100.0, 0.01) == ("total", 100.0, 0.01)
+    for bad in (("explicit", 1.0, 0.01), ("total", 1.0, None), ("total", 1.0, 0.0), ("total", -1.0, 0.01), ("adjoint", 0.0, None)):
+        with pytest.raises(ValueError):
+            sizing._objective(*bad)
+    cases = types.SimpleNamespace(Fy=torch.zeros((2, 600)))
+    with pytest.raises(ValueError, match="512"):
+        sizing.SizingState(cases, sizing.SizingConfig(num_nodes=600), torch.device("cpu"), gradient="total")
