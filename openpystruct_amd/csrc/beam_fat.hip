@@ -97,8 +97,10 @@ template <int P, int M, bool RZ, bool FAT, int PF>
 __device__ __forceinline__ void row_solve_lanes(const FatAcc<P * M>& acc, int g, int j, int& bad, RowOut<M, FAT>& out, ParkH<M, FAT>& hs,
                                                 IfacePiece* pieces, unsigned lane, unsigned long long* stamps) {
   SegState<M> st;
+  // 16 x 7 ran at 134 of the 168 VGPRs that three waves per SIMD allow: room for kD of its 7 elements (160 with them)
+  std::conditional_t<P == 16 && M == 7, KeepD<M>, KeepNone> keep;
   __asm__ volatile("" ::: "memory");
-  seg_condense_pf<M, RZ>(st, acc, bad);
+  seg_condense_pf<M, RZ>(st, acc, bad, keep);
   __asm__ volatile("" ::: "memory");
   FAT_STAMP(6);
   Vec2 uL, uR{0.0, 0.0};
@@ -133,16 +135,23 @@ __device__ __forceinline__ void row_solve_lanes(const FatAcc<P * M>& acc, int g,
   }
   __asm__ volatile("" ::: "memory");
   FAT_STAMP(7);
-  seg_solve_pf<M, RZ, PF>(st, acc, uL, uR, out, hs);
+  seg_solve_pf<M, RZ, PF>(st, acc, uL, uR, out, hs, keep);
 }
 
-// bits [e0, e0 + 32) of a 128-bit node mask held in two wave-uniform 64-bit halves
-__device__ __forceinline__ unsigned mask_window(unsigned long long lo, unsigned long long hi, int e0) {
+// bits [e0, e0 + 32) of a 128-bit node mask held in two wave-uniform 64-bit halves: the two 32-bit words the window
+// straddles, picked by three compares shared between the masks of a lane (WordPick), then one funnel shift
+struct WordPick {
+  bool q1, q2, q3;
+  unsigned r;
+  __device__ __forceinline__ explicit WordPick(int e0) : q1((e0 >> 5) == 1), q2((e0 >> 5) == 2), q3((e0 >> 5) == 3), r((unsigned)e0 & 31u) {}
+};
+__device__ __forceinline__ unsigned mask_window(unsigned long long lo, unsigned long long hi, const WordPick& w) {
   const unsigned w0 = (unsigned)lo, w1 = (unsigned)(lo >> 32), w2 = (unsigned)hi, w3 = (unsigned)(hi >> 32);
-  const int q = e0 >> 5, r = e0 & 31;
-  const unsigned a = q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : w3;
-  const unsigned b = q == 0 ? w1 : q == 1 ? w2 : q == 2 ? w3 : 0u;
-  return (unsigned)((((unsigned long long)b << 32) | a) >> r);
+  unsigned a = w0, b = w1;
+  a = w.q1 ? w1 : a;  b = w.q1 ? w2 : b;
+  a = w.q2 ? w2 : a;  b = w.q2 ? w3 : b;
+  a = w.q3 ? w3 : a;  b = w.q3 ? 0u : b;
+  return __builtin_amdgcn_alignbit(b, a, w.r);
 }
 
 // FAT  (P = 6): four row sets, one wave per SIMD.      LEAN (P = 16 / 8): two row sets, WPS waves per SIMD.
@@ -243,7 +252,15 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
 #pragma unroll
   for (int k = 0; k < NT; ++k) {
     const unsigned e = lane + 64u * k;
-    if (e < (unsigned)PM) {
+    if (64 * (k + 1) <= Ne) {         // wave-uniform: every element of this round is a real one, nothing to select
+      const double L = tx1[k] - tx0[k];
+      const double rl = fast_rcp(L);
+      const double c2 = 2.0 * tE * rl, pw = 0.5 * tw * L;
+      const double c6 = 3.0 * c2 * rl, c12 = 2.0 * c6 * rl;
+      const double mw = pw * L * (1.0 / 6.0);
+      s_tab[0 * PM + e] = c2;  s_tab[1 * PM + e] = c6;  s_tab[2 * PM + e] = c12;
+      s_tab[3 * PM + e] = rl;  s_tab[4 * PM + e] = pw;  s_tab[5 * PM + e] = mw;
+    } else if (e < (unsigned)PM) {
       const bool real = (int)e < Ne, pad = (int)e > Ne;
       const double L = tx1[k] - tx0[k];
       const double rl0 = fast_rcp(real ? L : 1.0);
@@ -262,9 +279,10 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
   {
     const unsigned long long v0 = __ballot(fb0 & 1), v1 = __ballot(fb1 & 1);
     const unsigned long long r0 = __ballot(fb0 & 2), r1 = __ballot(fb1 & 2);
-    bits.v = mask_window(v0, v1, e0) & ((2u << M) - 1u);
-    bits.t = mask_window(r0, r1, e0) & ((2u << M) - 1u);
     any_rz = (r0 | r1) != 0ull;
+    const WordPick pick(e0);
+    bits.v = mask_window(v0, v1, pick) & ((2u << M) - 1u);
+    bits.t = any_rz ? mask_window(r0, r1, pick) & ((2u << M) - 1u) : 0u;      // wave-uniform
   }
 
   // ---- stage 1b: the rows into LDS.  Padding: I = 1 (unit elements of the padding chain, beams beyond B), Fy = 0

@@ -45,6 +45,13 @@ hipError_t launch_fat_sizing(const BeamParams& p, const SizingArgs& sz, int P, i
 // v_mov_b32 with a row_shr / row_shl modifier (bound_ctrl writes 0 for lanes shifted in from outside
 // the row); no LDS crossbar, no wait.  P = 8 shares its row with a second beam and masks the lanes
 // that would read across the group edge.  P >= 32: ds_bpermute (__shfl).
+// lane SRC of the own 16-lane DPP row, in every lane of the row: ONE move.  row_newbcast is the only DPP control gfx950
+// takes on a 64-bit operand (v_mov_b64_dpp); shifts are 32-bit only.
+template <int SRC>
+__device__ __forceinline__ double row_bcast(double x) {
+  return __builtin_amdgcn_update_dpp(0.0, x, 0x150 + SRC, 0xF, 0xF, true);
+}
+
 template <int P>
 struct Xch {
   template <int S>
@@ -69,6 +76,17 @@ struct Xch {
       return j + S < P ? r : 0.0;
     }
   }
+  // The top reduction level has ONE receiver per direction: row 0 takes row S (top_plus), row S takes row 0 (top_minus).
+  // P = 16: the source is a fixed lane of the DPP row, so the fetch is one 64-bit row_newbcast move per double instead of
+  // two 32-bit shifts (what the other lanes of the row receive is never used).
+  template <int S>
+  static __device__ __forceinline__ double top_plus(double x, int lane, int j) {
+    if constexpr (P == 16) return row_bcast<S>(x); else return from_plus<S>(x, lane, j);
+  }
+  template <int S>
+  static __device__ __forceinline__ double top_minus(double x, int lane, int j) {
+    if constexpr (P == 16) return row_bcast<0>(x); else return from_minus<S>(x, lane, j);
+  }
   template <int S> static __device__ __forceinline__ Sym2 from_minus(const Sym2& s, int l, int j) {
     return Sym2{from_minus<S>(s.a, l, j), from_minus<S>(s.b, l, j), from_minus<S>(s.c, l, j)};
   }
@@ -86,6 +104,15 @@ struct Xch {
   }
   template <int S> static __device__ __forceinline__ Vec2 from_plus(const Vec2& u, int l, int j) {
     return Vec2{from_plus<S>(u.x, l, j), from_plus<S>(u.y, l, j)};
+  }
+  template <int S> static __device__ __forceinline__ Sym2 top_plus(const Sym2& s, int l, int j) {
+    return Sym2{top_plus<S>(s.a, l, j), top_plus<S>(s.b, l, j), top_plus<S>(s.c, l, j)};
+  }
+  template <int S> static __device__ __forceinline__ Vec2 top_plus(const Vec2& u, int l, int j) {
+    return Vec2{top_plus<S>(u.x, l, j), top_plus<S>(u.y, l, j)};
+  }
+  template <int S> static __device__ __forceinline__ Vec2 top_minus(const Vec2& u, int l, int j) {
+    return Vec2{top_minus<S>(u.x, l, j), top_minus<S>(u.y, l, j)};
   }
 };
 
@@ -122,6 +149,9 @@ struct XchPerm {
   template <int S> static __device__ __forceinline__ Vec2 from_plus(const Vec2& u, int l, int j) {
     return Vec2{from_plus<S>(u.x, l, j), from_plus<S>(u.y, l, j)};
   }
+  template <int S> static __device__ __forceinline__ Sym2 top_plus(const Sym2& s, int l, int j) { return from_plus<S>(s, l, j); }
+  template <int S> static __device__ __forceinline__ Vec2 top_plus(const Vec2& u, int l, int j) { return from_plus<S>(u, l, j); }
+  template <int S> static __device__ __forceinline__ Vec2 top_minus(const Vec2& u, int l, int j) { return from_minus<S>(u, l, j); }
 };
 
 // cyclic reduction over the P rows of a beam (beam_math.hpp): levels S = 1, 2, 4, ... < P.  Every lane runs
@@ -134,46 +164,58 @@ __device__ __forceinline__ void cr_forward(IfaceRow& row, int lane, int j, int& 
   if constexpr (S < P) {
     constexpr bool LAST = (2 * S >= P);
     const bool act = cr_active(j, S);
-    if constexpr (EARLY) {
+    if constexpr (LAST) {
+      // The top level.  Active rows are the multiples of 2S below P: row 0 alone, and row 0 has no row at -S.  Its lower
+      // coupling is exactly zero and what it would fetch from there is zeros, so the minus side changes nothing
+      // (x - 0 * 0 == x for every finite x) and is left out: fetch and update.
+      const Sym2 G = inv_spd(row.D, bad);
+      const Sym2 Gp = X::template top_plus<S>(G, lane, j);
+      const Vec2 fp = X::template top_plus<S>(row.f, lane, j);
+      Mat2 Cup = S > 1 ? neg(row.Cup) : row.Cup;     // held negated by the levels below (cr_absorb_held)
+      if (act) cr_absorb<true>(row.D, row.f, Cup, Gp, Mat2{0, 0, 0, 0}, fp);
+    } else if constexpr (EARLY) {
       const Vec2 fm = X::template from_minus<S>(row.f, lane, j);
       const Vec2 fp = X::template from_plus<S>(row.f, lane, j);
-      Mat2 Am{0, 0, 0, 0}, Cp{0, 0, 0, 0};
-      if constexpr (!LAST) {
-        Am = X::template from_minus<S>(row.Alow, lane, j);
-        Cp = X::template from_plus<S>(row.Cup, lane, j);
-      }
+      const Mat2 Am = X::template from_minus<S>(row.Alow, lane, j);
+      const Mat2 Cp = X::template from_plus<S>(row.Cup, lane, j);
       const Sym2 G = inv_spd(row.D, bad);
       const Sym2 Gm = X::template from_minus<S>(G, lane, j);
       const Sym2 Gp = X::template from_plus<S>(G, lane, j);
       if (act) {
-        cr_absorb<LAST>(row.D, row.f, row.Alow, Gm, Am, fm);
-        cr_absorb<LAST>(row.D, row.f, row.Cup, Gp, Cp, fp);
+        cr_absorb_held<(S > 1)>(row.D, row.f, row.Alow, Gm, Am, fm);
+        cr_absorb_held<(S > 1)>(row.D, row.f, row.Cup, Gp, Cp, fp);
       }
     } else {
       const Sym2 G = inv_spd(row.D, bad);
       // the two sides one after the other: half the exchange registers live at a time
       const Sym2 Gm = X::template from_minus<S>(G, lane, j);
       const Vec2 fm = X::template from_minus<S>(row.f, lane, j);
-      Mat2 Am{0, 0, 0, 0};
-      if constexpr (!LAST) Am = X::template from_minus<S>(row.Alow, lane, j);
+      const Mat2 Am = X::template from_minus<S>(row.Alow, lane, j);
       const Vec2 fp = X::template from_plus<S>(row.f, lane, j);      // fetched before the minus side rewrites row.f
-      if (act) cr_absorb<LAST>(row.D, row.f, row.Alow, Gm, Am, fm);
+      if (act) cr_absorb_held<(S > 1)>(row.D, row.f, row.Alow, Gm, Am, fm);
       const Sym2 Gp = X::template from_plus<S>(G, lane, j);
-      Mat2 Cp{0, 0, 0, 0};
-      if constexpr (!LAST) Cp = X::template from_plus<S>(row.Cup, lane, j);
-      if (act) cr_absorb<LAST>(row.D, row.f, row.Cup, Gp, Cp, fp);
+      const Mat2 Cp = X::template from_plus<S>(row.Cup, lane, j);
+      if (act) cr_absorb_held<(S > 1)>(row.D, row.f, row.Cup, Gp, Cp, fp);
     }
     cr_forward<P, 2 * S, X, EARLY>(row, lane, j, bad);
   }
 }
-// back substitution from the top level down: the rows frozen at level S take their neighbours' displacements
+// back substitution from the top level down: the rows frozen at level S take their neighbours' displacements.  A row frozen
+// at a level above the first has its couplings from the level below: held negated (cr_absorb_held).
 template <int P, int S, class X = Xch<P>>
-__device__ __forceinline__ void cr_backward(const IfaceRow& row, const Sym2& G, Vec2& u, int lane, int j) {
+__device__ __forceinline__ void cr_backward(const IfaceRow& held, const Sym2& G, Vec2& u, int lane, int j) {
   if constexpr (S >= 1) {
-    const Vec2 um = X::template from_minus<S>(u, lane, j);
-    const Vec2 up = X::template from_plus<S>(u, lane, j);
-    if (cr_frozen(j, S)) u = cr_back(row, G, um, up);
-    cr_backward<P, S / 2, X>(row, G, u, lane, j);
+    const IfaceRow row{S > 1 ? neg(held.Alow) : held.Alow, S > 1 ? neg(held.Cup) : held.Cup, held.D, held.f};
+    if constexpr (2 * S >= P) {
+      // the top level: row S is the only frozen one and has no row at +S (its u there is 0: x - c * 0 == x, left out)
+      const Vec2 um = X::template top_minus<S>(u, lane, j);
+      if (cr_frozen(j, S)) u = cr_back_low(row, G, um);
+    } else {
+      const Vec2 um = X::template from_minus<S>(u, lane, j);
+      const Vec2 up = X::template from_plus<S>(u, lane, j);
+      if (cr_frozen(j, S)) u = cr_back(row, G, um, up);
+    }
+    cr_backward<P, S / 2, X>(held, G, u, lane, j);
   }
 }
 // the top reduction level of a P-row interface system: the largest power of two below P

@@ -290,6 +290,20 @@ BEAM_HD void cr_absorb(Sym2& D, Vec2& f, Mat2& Aside, const Sym2& G, const Mat2&
   f = sub_mul(f, al, fn);
   if (!LAST) Aside = neg_mul(al, Afar);
 }
+// The same update with the couplings held NEGATED between the levels (cyclic-reduction drivers of beam_io.hpp).  The new
+// coupling is -(al * Afar): negating a RESULT costs an instruction per double, negating an INPUT is an operand modifier.  So a
+// level stores al * Afar as it comes, the next level (NEG: its inputs are such stored values) and the back substitution
+// negate on the way in.  Input negation is exact, so every bit -- the signs of zeros included -- is what cr_absorb gives.
+BEAM_HD Mat2 neg(const Mat2& m) { return Mat2{-m.a, -m.b, -m.c, -m.d}; }
+template <bool NEG>
+BEAM_HD void cr_absorb_held(Sym2& D, Vec2& f, Mat2& held, const Sym2& G, const Mat2& held_far, const Vec2& fn) {
+  const Mat2 Aside = NEG ? neg(held) : held, Afar = NEG ? neg(held_far) : held_far;
+  const Mat2 al = mul(Aside, G);
+  D = sub_mulT(D, al, Aside);
+  f = sub_mul(f, al, fn);
+  held = Mat2{__builtin_fma(al.a, Afar.a, al.b * Afar.c), __builtin_fma(al.a, Afar.b, al.b * Afar.d),
+              __builtin_fma(al.c, Afar.a, al.d * Afar.c), __builtin_fma(al.c, Afar.b, al.d * Afar.d)};   // = -neg_mul(al, Afar)
+}
 template <bool LAST>
 BEAM_HD void cr_eliminate(IfaceRow& r, const Sym2& Gm, const Mat2& Am, const Vec2& fm, const Sym2& Gp,
                           const Mat2& Cp, const Vec2& fp) {
@@ -300,6 +314,11 @@ BEAM_HD void cr_eliminate(IfaceRow& r, const Sym2& Gm, const Mat2& Am, const Vec
 // A frozen row solved from its own equation: u_j = D^-1 (f - Alow u_{j-s} - Cup u_{j+s}); G = D^-1.
 BEAM_HD Vec2 cr_back(const IfaceRow& r, const Sym2& G, const Vec2& um, const Vec2& up) {
   return mul(G, sub_mul(sub_mul(r.f, r.Alow, um), r.Cup, up));
+}
+
+// The same for a row that has no neighbour at +s (the one row frozen at the top level): u_{j+s} = 0 drops out exactly.
+BEAM_HD Vec2 cr_back_low(const IfaceRow& r, const Sym2& G, const Vec2& um) {
+  return mul(G, sub_mul(r.f, r.Alow, um));
 }
 
 // Phase C.  Out receives results by LOCAL index: node(i, v, theta), elem(i, V, Mz), i in [0, M).
@@ -359,9 +378,23 @@ BEAM_HD void seg_solve(const SegState<M>& s, const Acc& acc, const Vec2& uL, con
 // ---------------------------------------------------------------------------------------
 struct ElemIn { double c2, c6, c12, rl, pw, mw, Ie, Fy; };
 
+// Condensation, sweep and back substitution each need element i's kA .. kD.  A kernel with registers to spare keeps kD from
+// the condensation (KeepD: M doubles) and the two later phases form the rest exactly as elem_k does (kA = c12 * Ie and
+// kB = c6 * Ie once more, kC = kD + kD): one multiplication and one table read less per element and phase, same bits.
+// (Keeping kB as well is 2 M doubles: measured on the 16 x 7 rows kernel, 168 VGPRs and 20 bytes of scratch.)
+struct KeepNone {
+  BEAM_HD void put(int, const ElemK&) {}
+  BEAM_HD ElemK get(int, const ElemIn& e) const { return elem_k(e.c2, e.c6, e.c12, e.Ie); }
+};
+template <int M>
+struct KeepD {
+  double kD[M];
+  BEAM_HD void put(int i, const ElemK& k) { kD[i] = k.kD; }
+  BEAM_HD ElemK get(int i, const ElemIn& e) const { return ElemK{e.c12 * e.Ie, e.c6 * e.Ie, kD[i] + kD[i], kD[i]}; }
+};
 
-template <int M, bool RZ, class Acc>
-BEAM_HD void seg_condense_pf(SegState<M>& s, const Acc& acc, int& bad) {
+template <int M, bool RZ, class Acc, class Keep>
+BEAM_HD void seg_condense_pf(SegState<M>& s, const Acc& acc, int& bad, Keep& keep) {
   const auto fb = acc.fixbits();
   ElemIn nx = acc.elem(0);
   {
@@ -369,6 +402,7 @@ BEAM_HD void seg_condense_pf(SegState<M>& s, const Acc& acc, int& bad) {
     if (M > 1) nx = acc.elem(1);
     acc.fence();
     const ElemK k = elem_k(e.c2, e.c6, e.c12, e.Ie);
+    keep.put(0, k);
     s.SLL = Sym2{k.kA, k.kB, k.kC};
     s.SLc = Mat2{-k.kA, k.kB, -k.kB, k.kD};
     s.Scc = Sym2{k.kA, -k.kB, k.kC};
@@ -382,6 +416,7 @@ BEAM_HD void seg_condense_pf(SegState<M>& s, const Acc& acc, int& bad) {
     acc.fence();
     const Flags<RZ> c = node_flags<RZ>(fb, i);
     const ElemK k = elem_k(e.c2, e.c6, e.c12, e.Ie);
+    keep.put(i, k);
     const double pw = e.pw, mw = e.mw;
     const Sym2 G = proj_inv(Sym2{s.Scc.a + k.kA, s.Scc.b + k.kB, s.Scc.c + k.kC}, c, bad);
     const Vec2 gi{s.gc.x + pw + e.Fy, s.gc.y + mw};
@@ -399,12 +434,18 @@ BEAM_HD void seg_condense_pf(SegState<M>& s, const Acc& acc, int& bad) {
   }
 }
 
+template <int M, bool RZ, class Acc>
+BEAM_HD void seg_condense_pf(SegState<M>& s, const Acc& acc, int& bad) {
+  KeepNone keep;
+  seg_condense_pf<M, RZ>(s, acc, bad, keep);
+}
+
 // Hs: where the right-hand-side sweep parks h_i for the back substitution: put(i, h) / get(i) -- registers, or
 // (fat tilings, to stay inside 256 VGPRs) the LDS slots that the back substitution overwrites with its results.
 // PF: how many elements ahead the inputs are requested (an iteration of these two loops is 14 / 24 FP64 instructions,
 // shorter than one LDS round trip).
-template <int M, bool RZ, int PF, class Acc, class Out, class Hs>
-BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, const Vec2& uR, Out& out, Hs& hs) {
+template <int M, bool RZ, int PF, class Acc, class Out, class Hs, class Keep>
+BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, const Vec2& uR, Out& out, Hs& hs, const Keep& keep) {
   static_assert(PF >= 1 && PF <= 4, "prefetch distance");
   {
     ElemIn q[PF];
@@ -413,7 +454,7 @@ BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, 
     const ElemIn e0 = q[0];
     if (PF < M) q[0] = acc.elem(PF);
     acc.fence();
-    const ElemK k0 = elem_k(e0.c2, e0.c6, e0.c12, e0.Ie);
+    const ElemK k0 = keep.get(0, e0);
     Vec2 carry = sub_mulT(Vec2{e0.pw, -e0.mw}, Mat2{-k0.kA, k0.kB, -k0.kB, k0.kD}, uL);
 #pragma unroll
     for (int i = 1; i < M; ++i) {
@@ -424,7 +465,7 @@ BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, 
       const Vec2 hi{carry.x + pw + e.Fy, carry.y + mw};
       hs.put(i, hi);
       if (i + 1 < M) {
-        const ElemK k = elem_k(e.c2, e.c6, e.c12, e.Ie);
+        const ElemK k = keep.get(i, e);
         const Vec2 y = mul(s.Ginv[i], hi);
         carry = sub_mulT(Vec2{pw, -mw}, Mat2{-k.kA, k.kB, -k.kB, k.kD}, y);
       }
@@ -446,7 +487,7 @@ BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, 
     if (i - PF >= 0) q[i % PF] = acc.elem(i - PF);
     if (i - PF >= 1) hq[i % PF] = hs.get(i - PF);
     acc.fence();
-    const ElemK k = elem_k(e.c2, e.c6, e.c12, e.Ie);
+    const ElemK k = keep.get(i, e);
     Vec2 ui;
     if (i > 0) {
       ui = mul(s.Ginv[i], sub_mul(hi, Mat2{-k.kA, k.kB, -k.kB, k.kD}, un));
@@ -464,6 +505,10 @@ BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, 
     out.node(i, ui.x, ui.y);
     un = ui;
   }
+}
+template <int M, bool RZ, int PF, class Acc, class Out, class Hs>
+BEAM_HD void seg_solve_pf(const SegState<M>& s, const Acc& acc, const Vec2& uL, const Vec2& uR, Out& out, Hs& hs) {
+  seg_solve_pf<M, RZ, PF>(s, acc, uL, uR, out, hs, KeepNone{});
 }
 
 // ---------------------------------------------------------------------------------------
