@@ -1,0 +1,82 @@
+// Arithmetic of the exact-gradient frame sizing objective, per node and per element: plain C++ that compiles
+// for the device (csrc/frame_sizing_grad.hip) and with g++ for the host (tests/test_frame_sizing_grad_host.py builds a
+// stand-alone program from this file).  Nothing is restated: the objective's cotangents and its explicit part are the
+// functions of sizing_grad_math.hpp (the beam objective's: sizing_quot, sizing_gM, sizing_gV, sizing_explicit, sizing_defl,
+// sizing_gv), the element stiffness is fa_apply_k of frame_adjoint.hpp.
+//
+//   L(I) = sum_e I_e + aM sum_e M_e^2 / (2 E I_e + bend_eps) + aV sum_e V_e^2 / (G area_coef sqrt(I_e))
+//        + aS sum_n h(|ux_n|, s_lim) + aD sum_n h(|uy_n|, d_lim),      h(a, lim) = (max(0, a - lim) / lim)^2
+//   rhs   r[n,:] = (gv_s(ux_n), gv_d(uy_n), 0) + sum over the elements e at node n of (K_e g_f,e)[end of e at n],
+//         g_f,e = (0, gV_e, gM_e, 0, 0, 0): §9f's fold with g_forces = 0
+//   grad  dL/dI_e = sizing_explicit + (g_f,e - lambda_e) . (K_b,e u_e)
+// The cotangents are formed from (I, V, M) and disp where they are used and live in registers only.
+#pragma once
+
+#include "frame_adjoint.hpp"
+#include "sizing_grad_math.hpp"
+
+namespace opsamd {
+
+// the objective's constants: SizingObj once per hinge -- `sway` carries (aS, s_lim) in (aD, vlim) and is applied to ux, `defl`
+// carries (aD, d_lim) and is applied to uy; the element constants are the same in both
+struct FrameSizingObj { SizingObj sway, defl; };
+
+FA_HD FrameSizingObj frame_sizing_obj(double aM, double aV, double E, double bend_eps, double G, double area_coef, double aS,
+                                      double s_lim, double aD, double d_lim) {
+  const SizingObj s{aM, aV, 2.0 * E, bend_eps, G * area_coef, aS, aS > 0.0 ? s_lim : 1.0};
+  const SizingObj d{aM, aV, 2.0 * E, bend_eps, G * area_coef, aD, aD > 0.0 ? d_lim : 1.0};
+  return FrameSizingObj{s, d};
+}
+
+// the folded cotangent of element row `row` (= frame * Ne + element) from this epoch's forward
+FA_HD void fs_fold(const SizingObj& o, const SizingQuot& q, double gf[6]) {
+  gf[0] = 0.0; gf[1] = sizing_gV(o, q); gf[2] = sizing_gM(o, q);
+  gf[3] = 0.0; gf[4] = 0.0; gf[5] = 0.0;
+}
+
+// The three adjoint loads of node n of frame b (fa_node_rhs with the objective's cotangents in place of arrays; the same fixed
+// order over the node's incident ends).  Returns the node's share of the two hinge terms.  sizing_defl compares, and a
+// comparison drops a NaN: a NaN displacement (a frame whose forward failed) is forwarded to the returned value by hand.
+FA_HD double fs_node_rhs(const FrameSizingObj& o, int n_nodes, int n_elems, const double* elem_geo, const double* elem_EA,
+                         const double* elem_E, const int32_t* node_elem_ptr, const int32_t* node_elem_idx, const double* I,
+                         const double* disp, const double* V, const double* M, long b, int n, double r[3]) {
+  const long node = b * n_nodes + n;
+  const double ux = disp[node * 3], uy = disp[node * 3 + 1];
+  r[0] = sizing_gv(o.sway, ux);
+  r[1] = sizing_gv(o.defl, uy);
+  r[2] = 0.0;
+  for (int p = node_elem_ptr[n]; p < node_elem_ptr[n + 1]; ++p) {
+    const int e = node_elem_idx[p] >> 1, end = node_elem_idx[p] & 1;
+    const long row = b * n_elems + e;
+    double gf[6], y[6];
+    fs_fold(o.sway, sizing_quot(o.sway, I[row], V[row], M[row]), gf);
+    fa_apply_k(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], elem_EA[e], elem_E[e] * I[row], gf, y);
+    for (int k = 0; k < 3; ++k) r[k] += y[3 * end + k];
+  }
+  const double h = sizing_defl(o.sway, ux) + sizing_defl(o.defl, uy);
+  return (ux != ux || uy != uy) ? ux + uy : h;
+}
+
+// dL/dI of element e of frame b from the forward's (I, V, M, disp) and the adjoint's displacements lambda
+FA_HD double fs_elem_grad(const FrameSizingObj& o, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
+                          const int32_t* conn, const double* I, const double* V, const double* M, const double* disp,
+                          const double* lambda, long b, int e) {
+  const long row = b * n_elems + e;
+  const long n1 = b * n_nodes + conn[2 * e], n2 = b * n_nodes + conn[2 * e + 1];
+  const double Ie = I[row], Ve = V[row];
+  const SizingQuot q = sizing_quot(o.sway, Ie, Ve, M[row]);
+  double gf[6], u[6], d[6], y[6];
+  fs_fold(o.sway, q, gf);
+  for (int k = 0; k < 3; ++k) {
+    u[k] = disp[n1 * 3 + k];
+    u[3 + k] = disp[n2 * 3 + k];
+    d[k] = gf[k] - lambda[n1 * 3 + k];
+    d[3 + k] = gf[3 + k] - lambda[n2 * 3 + k];
+  }
+  fa_apply_k(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], 0.0, elem_E[e], u, y);
+  double acc = 0.0;
+  for (int k = 0; k < 6; ++k) acc += d[k] * y[k];
+  return sizing_explicit(o.sway, Ie, Ve, q) + acc;
+}
+
+}  // namespace opsamd

@@ -324,13 +324,122 @@ def differentiable_frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Opti
     return torch_op.frame_solve_autograd(topo, I, loads)
 
 
+GRADIENTS = ("explicit", "total")
+
+
+def _objective(gradient: str, alpha_sway: float, sway_limit: Optional[float], alpha_deflection: float,
+               deflection_limit: Optional[float]) -> tuple:
+    """The checked (gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit) of a frame sizing run (the frame counterpart
+    of `sizing._objective`).  "explicit": the reference's gradient (M and V held fixed), which cannot see a displacement term;
+    "total": the gradient of the loss through the solve.  The limits are penalties, not constraints."""
+    if gradient not in GRADIENTS:
+        raise ValueError(f"gradient must be one of {GRADIENTS}, got {gradient!r}")
+    out = [gradient]
+    for name, alpha, limit in (("sway", alpha_sway, sway_limit), ("deflection", alpha_deflection, deflection_limit)):
+        alpha = float(alpha)
+        if not alpha >= 0.0:
+            raise ValueError(f"alpha_{name} must be >= 0")
+        if alpha > 0.0:
+            if gradient == "explicit":
+                raise ValueError(f'alpha_{name} > 0 needs gradient="total": the {name} term depends on I only through the solve, '
+                                 "the explicit gradient is blind to it")
+            if limit is None or not float(limit) > 0.0:
+                raise ValueError(f"alpha_{name} > 0 needs a {name}_limit > 0")
+        out += [alpha, float(limit) if alpha > 0.0 else 0.0]
+    return tuple(out)
+
+
+def _sizing_params(cfg: FrameConfig, max_epochs: Optional[int] = None) -> "_cabi.SizingParams":
+    """FR:17-44, :155, :170 as the step kernels read them: no scheduler (gamma = 1), `+ 1e-8` in the bending term."""
+    return _cabi.SizingParams(E=cfg.E, G=cfg.G, alpha_moment=cfg.alpha_moment, alpha_shear=cfg.alpha_shear, lr=cfg.lr, gamma=1.0,
+                              beta1=0.9, beta2=0.999, adam_eps=1e-8, clamp_min=1e-8, bend_eps=1e-8, area_coef=cfg.k,
+                              tolerance=cfg.tolerance, patience=cfg.patience,
+                              max_epochs=max_epochs if max_epochs is not None else cfg.num_epochs)
+
+
+class _SizingGradBuffers(NamedTuple):
+    rhs: torch.Tensor                    # [B,Nn,3] the adjoint right-hand side
+    adj: FrameSolution                   # the adjoint solve: disp = lambda
+    grad: torch.Tensor                   # [B,Ne]
+    loss_extra: Optional[torch.Tensor]   # [B], None without a displacement term
+
+
+def _sizing_grad_buffers(topo: FrameTopology, B: int, dev, with_extra: bool) -> _SizingGradBuffers:
+    f64 = dict(dtype=torch.float64, device=dev)
+    return _SizingGradBuffers(torch.empty((B, topo.Nn, 3), **f64), _empty_solution(topo, B, dev), torch.empty((B, topo.Ne), **f64),
+                              torch.zeros((B,), **f64) if with_extra else None)
+
+
+def _sizing_grad_launches(topo: FrameTopology, I: torch.Tensor, sol: FrameSolution, hp, obj, active: Optional[torch.Tensor],
+                          buf: _SizingGradBuffers) -> None:
+    """The three launches of dL/dI on the current stream (csrc/frame_sizing_grad.hip around the adjoint solve of §9f); no checks, no
+    allocation beyond what `_run_solve` keeps per stream."""
+    lib = _cabi.load()
+    dev, B = I.device, I.shape[0]
+    adj = _adjoint_tables(topo)
+    act = active.data_ptr() if active is not None else None
+    extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.ops_frame_sizing_rhs_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+                                          adj.ptr.data_ptr(), adj.idx.data_ptr(), I.data_ptr(), sol.disp.data_ptr(), sol.V.data_ptr(),
+                                          sol.M.data_ptr(), ctypes.byref(hp), ctypes.byref(obj), act, buf.rhs.data_ptr(), extra, stream)
+    _cabi.check(rc, "ops_frame_sizing_rhs_f64")
+    _run_solve(topo, I, buf.rhs, topo.Nn * 3, buf.adj, adj.zero_w, "_ws_adjoint")
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_sizing_grad_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(),
+                                           I.data_ptr(), sol.disp.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(),
+                                           buf.adj.disp.data_ptr(), ctypes.byref(hp), act, sol.status.data_ptr(),
+                                           buf.adj.status.data_ptr(), buf.grad.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_sizing_grad_f64")
+
+
+def frame_sizing_gradient(topo: FrameTopology, I: torch.Tensor, sol: FrameSolution, hp, *, alpha_sway: float = 0.0,
+                          sway_limit: Optional[float] = None, alpha_deflection: float = 0.0,
+                          deflection_limit: Optional[float] = None, active: Optional[torch.Tensor] = None):
+    """dL/dI [B,Ne] of the frame sizing objective (float64, with M, V and the nodal displacements as functions of I)
+    from the forward solution `sol` of `frame_solve(topo, I)`: three launches on the current stream -- the adjoint right-hand side,
+    the adjoint solve, the gradient (csrc/frame_sizing_grad.hip).  `hp`: a `FrameConfig` or an `ops_sizing_params`.  The objective may
+    add `alpha_sway * sum_n (max(0, |ux_n| - sway_limit) / sway_limit)^2` and the same in uy with `alpha_deflection`,
+    `deflection_limit`: penalties, not constraints.  Returns (grad, loss_extra, status): loss_extra [B] is the value of the two
+    displacement terms (None when both alphas are 0), status [B] the adjoint solve's (non-zero: the frame's row is NaN, as it is for
+    a frame with sol.status != 0).  Rows of frames with active[b] == 0 are not written."""
+    if not torch.is_tensor(I) or not I.is_cuda:
+        raise RuntimeError("frame_sizing_gradient needs GPU tensors: openpystruct_amd has no CPU fallback")
+    if I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne or not I.is_contiguous():
+        raise ValueError(f"I must be a contiguous float64 tensor of shape [B, {topo.Ne}]")
+    B, dev = I.shape[0], I.device
+    _, aS, s_lim, aD, d_lim = _objective("total", alpha_sway, sway_limit, alpha_deflection, deflection_limit)
+    hp = _sizing_params(hp) if isinstance(hp, FrameConfig) else hp
+    for name, t, shape in (("sol.disp", sol.disp, (B, topo.Nn, 3)), ("sol.V", sol.V, (B, topo.Ne)), ("sol.M", sol.M, (B, topo.Ne))):
+        if tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {dev}")
+    if tuple(sol.status.shape) != (B,) or sol.status.dtype != torch.int32 or sol.status.device != dev:
+        raise ValueError(f"sol.status must be an int32 tensor of shape {(B,)} on {dev}")
+    if active is not None and (tuple(active.shape) != (B,) or active.dtype != torch.uint8 or active.device != dev):
+        raise ValueError(f"active must be a uint8 tensor of shape {(B,)} on {dev}")
+    buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
+    if B:
+        obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
+        _sizing_grad_launches(topo, I, sol, hp, obj, active, buf)
+    return buf.grad, buf.loss_extra, buf.adj.status
+
+
 def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
-                    max_epochs: Optional[int] = None, poll_every: int = 25, loss_history: Optional[list] = None):
+                    max_epochs: Optional[int] = None, poll_every: int = 25, loss_history: Optional[list] = None,
+                    gradient: str = "explicit", alpha_sway: float = 0.0, sway_limit: Optional[float] = None,
+                    alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
     """FR:163-206 for B frames at once (same topology; `I0` [B,Ne] lets them start from different designs).
     Adam(lr) with NO scheduler (gamma = 1), loss with `+1e-8` in the bending term (FR:155), early stop
     tolerance 1e-3 / patience 10.  Returns (I float32 [B,Ne], solution of the last solve, epochs_run).
-    `loss_history`: a list that receives every epoch's `total_loss` [B] (FR:190; a stopped frame repeats its last value)."""
+    `loss_history`: a list that receives every epoch's `total_loss` [B] (FR:190; a stopped frame repeats its last value).
+    `gradient`: "explicit" steps on the reference's gradient (M and V held fixed: its loop); "total" on the exact gradient of the
+    loss through the solve (five launches per epoch, two factorisations) and may add the penalties
+    `alpha_sway * sum_n (max(0, |ux_n| - sway_limit) / sway_limit)^2` and, in uy, `alpha_deflection` / `deflection_limit` to the loss."""
     cfg = cfg or FrameConfig()
+    _, aS, s_lim, aD, d_lim = _objective(gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit)
+    if gradient == "total" and topo.Ne > 512:
+        raise ValueError(f'gradient="total" serves up to 512 elements per frame (the optimiser step kernel), got {topo.Ne}')
     lib = _cabi.load()
     dev = topo.device
     Ne = topo.Ne
@@ -345,18 +454,31 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
     last = torch.zeros((B,), **f32)
     V32, M32 = torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32)
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
-    hp = _cabi.SizingParams(E=cfg.E, G=cfg.G, alpha_moment=cfg.alpha_moment, alpha_shear=cfg.alpha_shear, lr=cfg.lr, gamma=1.0,
-                            beta1=0.9, beta2=0.999, adam_eps=1e-8, clamp_min=1e-8, bend_eps=1e-8, area_coef=cfg.k,
-                            tolerance=cfg.tolerance, patience=cfg.patience, max_epochs=n_max)
+    hp = _sizing_params(cfg, n_max)
     sol = None
+    if gradient == "total":      # every buffer of the loop, before it
+        sol = _empty_solution(topo, B, dev)
+        buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
+        obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
+        extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
     for e in range(n_max):
         sol = frame_solve(topo, I64, out=sol)
-        with torch.cuda.device(dev):
-            rc = lib.ops_beam_sizing_step_f32(B, Ne, I.data_ptr(), I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), ea.data_ptr(),
-                                              es.data_ptr(), best.data_ptr(), cnt.data_ptr(), ep.data_ptr(), active.data_ptr(),
-                                              last.data_ptr(), V32.data_ptr(), M32.data_ptr(), ctypes.byref(hp),
-                                              torch.cuda.current_stream(dev).cuda_stream)
-        _cabi.check(rc, "ops_beam_sizing_step_f32")
+        if gradient == "total":
+            _sizing_grad_launches(topo, I64, sol, hp, obj, active, buf)
+            with torch.cuda.device(dev):
+                rc = lib.ops_beam_sizing_step_grad_f32(B, Ne, I.data_ptr(), I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(),
+                                                       buf.grad.data_ptr(), extra, ea.data_ptr(), es.data_ptr(), best.data_ptr(),
+                                                       cnt.data_ptr(), ep.data_ptr(), active.data_ptr(), last.data_ptr(),
+                                                       V32.data_ptr(), M32.data_ptr(), ctypes.byref(hp), None,
+                                                       torch.cuda.current_stream(dev).cuda_stream)
+            _cabi.check(rc, "ops_beam_sizing_step_grad_f32")
+        else:
+            with torch.cuda.device(dev):
+                rc = lib.ops_beam_sizing_step_f32(B, Ne, I.data_ptr(), I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), ea.data_ptr(),
+                                                  es.data_ptr(), best.data_ptr(), cnt.data_ptr(), ep.data_ptr(), active.data_ptr(),
+                                                  last.data_ptr(), V32.data_ptr(), M32.data_ptr(), ctypes.byref(hp),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+            _cabi.check(rc, "ops_beam_sizing_step_f32")
         if loss_history is not None:
             loss_history.append(last.clone())
         if (e + 1) % poll_every == 0 and not bool(active.any()):
