@@ -15,9 +15,11 @@ import types
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd.h")
 # additions to the C ABI that change no declaration of HEADER_PATH (and so not OPS_AMD_ABI_VERSION) have headers of their own
-# (the beam sizing header stays the last entry: tests/test_sizing_grad_emulation.py reads it as EXTENSION_HEADER_PATHS[-1])
+# (the beam sizing header stays the last entry: tests/test_sizing_grad_emulation.py reads it as EXTENSION_HEADER_PATHS[-1]; the frame
+# sizing header stays entry 1)
 EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_vjp.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_sizing.h"),
+                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_loads.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_grad.h"))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
@@ -152,7 +154,7 @@ TfdFrontArgs = _struct("ops_tfd_front_args")
 TfdFrontBwdArgs = _struct("ops_tfd_front_bwd_args")
 BayesLayer = _struct("ops_bayes_layer")
 BayesMcArgs = _struct("ops_bayes_mc_args")
-SizingObjective = _extensions[EXTENSION_HEADER_PATHS[2]].structs["ops_sizing_objective"]
+SizingObjective = _extensions[EXTENSION_HEADER_PATHS[-1]].structs["ops_sizing_objective"]
 FrameSizingObjective = _extensions[EXTENSION_HEADER_PATHS[1]].structs["ops_frame_sizing_objective"]
 # every OPS_AMD_X / OPS_X of the header as X: OK, ERR_*, FIX_*, ABI_VERSION, FRAME_REUSE_PLAN, MLP_*, BAYES_*, WGRAD_MAX_GROUP, ADAM_*, ...
 for _name, _value in _abi.defines.items():

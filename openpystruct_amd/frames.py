@@ -179,7 +179,10 @@ class FrameSolution(NamedTuple):
 
 
 def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tensor] = None,
-                out: Optional[FrameSolution] = None) -> FrameSolution:
+                out: Optional[FrameSolution] = None, element_loads: Optional[torch.Tensor] = None) -> FrameSolution:
+    """`element_loads`: float64 [Ne,2] or [B,Ne,2] (wy, wx) REPLACES the topology's `wy` / `wx` for this call, per frame when it has
+    a batch dimension (three launches -- the right-hand side with the consistent loads, the solve without element
+    loads on a workspace of its own, the correction of the forces); None: the topology's element loads, one launch."""
     lib = _cabi.load()
     if not torch.is_tensor(I) or not I.is_cuda:
         raise RuntimeError("frame_solve needs GPU tensors: openpystruct_amd has no CPU fallback")
@@ -193,10 +196,50 @@ def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tens
     else:
         loads = loads.to(torch.float64).contiguous()
         lbs = topo.Nn * 3 if loads.dim() == 3 else 0
+    if element_loads is not None:
+        w, wbs = _checked_element_loads(topo, element_loads, B, dev)
+        _check_nodal_loads(topo, loads, B, dev)
     if out is None:
         out = _empty_solution(topo, B, dev)
+    if element_loads is not None:
+        _element_load_launches(topo, I, loads, lbs, w, wbs, torch.empty((B, topo.Nn, 3), dtype=torch.float64, device=dev), out)
+        return out
     _run_solve(topo, I, loads, lbs, out, topo.d_w, "_ws")
     return out
+
+
+def _checked_element_loads(topo: FrameTopology, w, B: int, dev) -> tuple:
+    """(contiguous element loads, their batch stride) of an `element_loads` argument for B frames on `dev`."""
+    if not torch.is_tensor(w) or not w.is_cuda:
+        raise RuntimeError("element_loads must be a GPU tensor: openpystruct_amd has no CPU fallback")
+    if w.dtype != torch.float64 or w.device != dev or tuple(w.shape) not in ((topo.Ne, 2), (B, topo.Ne, 2)):
+        raise ValueError(f"element_loads must be float64 [{topo.Ne}, 2] or [{B}, {topo.Ne}, 2] (wy, wx) on {dev}")
+    return w.contiguous(), (2 * topo.Ne if w.dim() == 3 else 0)
+
+
+def _check_nodal_loads(topo: FrameTopology, loads: torch.Tensor, B: int, dev) -> None:
+    if loads.device != dev or tuple(loads.shape) not in ((topo.Nn, 3), (B, topo.Nn, 3)):
+        raise ValueError(f"loads must be [{topo.Nn}, 3] or [{B}, {topo.Nn}, 3] on {dev}")
+
+
+def _element_load_launches(topo: FrameTopology, I: torch.Tensor, loads: torch.Tensor, lbs: int, w: torch.Tensor, wbs: int,
+                           rhs: torch.Tensor, out: FrameSolution) -> None:
+    """The three launches of a solve under element loads `w` on the current stream (csrc/frame_loads.hip around the solve without
+    element loads); no checks, no allocation beyond what `_run_solve` keeps per stream.  The workspaces are this
+    path's own (`_ws_loads`): a cached plan holds the consistent loads of the element loads it was built with."""
+    lib = _cabi.load()
+    dev, B = I.device, I.shape[0]
+    adj = _adjoint_tables(topo)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.ops_frame_load_rhs_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(),
+                                        loads.data_ptr(), lbs, w.data_ptr(), wbs, rhs.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_load_rhs_f64")
+    _run_solve(topo, I, rhs, topo.Nn * 3, out, adj.zero_w, "_ws_loads")
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_load_forces_f64(B, topo.Ne, topo.d_geo.data_ptr(), w.data_ptr(), wbs, out.status.data_ptr(),
+                                           out.forces.data_ptr(), out.V.data_ptr(), out.M.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_load_forces_f64")
 
 
 def _empty_solution(topo: FrameTopology, B: int, dev) -> FrameSolution:
@@ -317,11 +360,57 @@ def frame_solve_vjp(topo: FrameTopology, I: torch.Tensor, disp: torch.Tensor, g_
     return gI, sol.disp, sol.status
 
 
-def differentiable_frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tensor] = None) -> FrameSolution:
+def frame_element_load_vjp(topo: FrameTopology, lam: torch.Tensor, g_forces: Optional[torch.Tensor] = None,
+                           gV: Optional[torch.Tensor] = None, gM: Optional[torch.Tensor] = None,
+                           status: Optional[torch.Tensor] = None, status_adj: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of a loss with respect to per-frame element loads: g_w [B,Ne,2] (wy, wx) from `lam` [B,Nn,3], the
+    `g_loads` that `frame_solve_vjp` returns for the same cotangents, and the cotangents of forces [B,Ne,6], V and M [B,Ne] (None =
+    zero).  One launch on the current stream (csrc/frame_loads.hip).  `status` / `status_adj` [B] int32: the forward's and the
+    adjoint solve's; a frame with a non-zero one gets a NaN row.  Element loads shared by the batch take the sum over the frames."""
+    lib = _cabi.load()
+    if not torch.is_tensor(lam) or not lam.is_cuda:
+        raise RuntimeError("frame_element_load_vjp needs GPU tensors: openpystruct_amd has no CPU fallback")
+    if lam.dtype != torch.float64 or lam.dim() != 3 or tuple(lam.shape[1:]) != (topo.Nn, 3):
+        raise ValueError(f"lam must be float64 [B, {topo.Nn}, 3]")
+    lam = lam.contiguous()
+    B, dev = lam.shape[0], lam.device
+    shapes = dict(g_forces=(B, topo.Ne, 6), gV=(B, topo.Ne), gM=(B, topo.Ne))
+
+    def dense(name, t):
+        if t is None:
+            return None
+        if t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != shapes[name]:
+            raise ValueError(f"{name} must be float64 {list(shapes[name])} on {dev}")
+        return t.contiguous()
+
+    def flags(name, t):
+        if t is None:
+            return None
+        if t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != (B,):
+            raise ValueError(f"{name} must be int32 [{B}] on {dev}")
+        return t.contiguous()
+
+    g_forces, gV, gM = (dense(k, v) for k, v in (("g_forces", g_forces), ("gV", gV), ("gM", gM)))
+    status, status_adj = flags("status", status), flags("status_adj", status_adj)
+    adj = _adjoint_tables(topo)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    g_w = torch.empty((B, topo.Ne, 2), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_load_vjp_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.conn.data_ptr(), lam.data_ptr(), ptr(g_forces),
+                                        ptr(gV), ptr(gM), ptr(status), ptr(status_adj), g_w.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream)
+    _cabi.check(rc, "ops_frame_load_vjp_f64")
+    return g_w
+
+
+def differentiable_frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tensor] = None,
+                               element_loads: Optional[torch.Tensor] = None) -> FrameSolution:
     """`frame_solve` through the registered operator `openpystruct_amd::frame_solve` (torch_op.py): gradients reach I and, when
-    given, loads ([Nn,3] shared or [B,Nn,3]); status is not differentiable.  The graph keeps `topo` alive until it is freed."""
+    given, loads ([Nn,3] shared or [B,Nn,3]); status is not differentiable.  The graph keeps `topo` alive until it is freed.
+    With `element_loads` ([Ne,2] shared or [B,Ne,2]) it is the operator `openpystruct_amd::frame_solve_loads`, whose gradients reach
+    the element loads too; a shared input receives the sum over the frames."""
     from . import torch_op
-    return torch_op.frame_solve_autograd(topo, I, loads)
+    return torch_op.frame_solve_autograd(topo, I, loads, element_loads)
 
 
 GRADIENTS = ("explicit", "total")
@@ -428,8 +517,11 @@ def frame_sizing_gradient(topo: FrameTopology, I: torch.Tensor, sol: FrameSoluti
 def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
                     max_epochs: Optional[int] = None, poll_every: int = 25, loss_history: Optional[list] = None,
                     gradient: str = "explicit", alpha_sway: float = 0.0, sway_limit: Optional[float] = None,
-                    alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
+                    alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None, loads: Optional[torch.Tensor] = None,
+                    element_loads: Optional[torch.Tensor] = None):
     """FR:163-206 for B frames at once (same topology; `I0` [B,Ne] lets them start from different designs).
+    `loads` ([Nn,3] or [B,Nn,3]) and `element_loads` (float64 [Ne,2] or [B,Ne,2]: wy, wx) replace the topology's nodal and element
+    loads, per frame when they have a batch dimension; only the forward solve of an epoch changes.
     Adam(lr) with NO scheduler (gamma = 1), loss with `+1e-8` in the bending term (FR:155), early stop
     tolerance 1e-3 / patience 10.  Returns (I float32 [B,Ne], solution of the last solve, epochs_run).
     `loss_history`: a list that receives every epoch's `total_loss` [B] (FR:190; a stopped frame repeats its last value).
@@ -456,13 +548,29 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
     hp = _sizing_params(cfg, n_max)
     sol = None
-    if gradient == "total":      # every buffer of the loop, before it
+    if loads is not None:
+        if not torch.is_tensor(loads) or not loads.is_cuda:
+            raise RuntimeError("loads must be a GPU tensor: openpystruct_amd has no CPU fallback")
+        loads = loads.to(torch.float64).contiguous()
+        _check_nodal_loads(topo, loads, B, I.device)
+    if element_loads is not None:      # every buffer of the three-launch forward, before the loop
+        w, wbs = _checked_element_loads(topo, element_loads, B, I.device)
+        fwd_loads = topo.d_loads if loads is None else loads
+        lbs = topo.Nn * 3 if fwd_loads.dim() == 3 else 0
         sol = _empty_solution(topo, B, dev)
+        fwd_rhs = torch.empty((B, topo.Nn, 3), dtype=torch.float64, device=dev)
+    if gradient == "total":      # every buffer of the loop, before it
+        sol = sol if sol is not None else _empty_solution(topo, B, dev)
         buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
         obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
         extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
     for e in range(n_max):
-        sol = frame_solve(topo, I64, out=sol)
+        if element_loads is not None:
+            _element_load_launches(topo, I64, fwd_loads, lbs, w, wbs, fwd_rhs, sol)
+        elif loads is not None:
+            sol = frame_solve(topo, I64, loads, out=sol)
+        else:
+            sol = frame_solve(topo, I64, out=sol)
         if gradient == "total":
             _sizing_grad_launches(topo, I64, sol, hp, obj, active, buf)
             with torch.cuda.device(dev):
@@ -485,3 +593,48 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
             break
     torch.cuda.synchronize(dev)
     return I, sol, ep
+
+
+def grid_load_cases(topo: FrameTopology, lateral, vertical):
+    """The reference's load pattern (FR:120-131) with per-frame magnitudes: `lateral` [B] and `vertical` [B] (array-likes or
+    tensors) -> (loads [B,Nn,3], element_loads [B,Ne,2]) float64 on `topo.device`: (lateral_b, 0, 0) on the nodes of the left column
+    line that are not fully fixed, beamUniform(vertical_b, vertical_b) on the horizontal elements.  With a `FrameConfig`'s two
+    scalars it is `grid_frame`'s own `nodal_loads`, `wy` and `wx`."""
+    f64 = dict(dtype=torch.float64, device=topo.device)
+    lateral, vertical = torch.as_tensor(lateral, **f64).reshape(-1), torch.as_tensor(vertical, **f64).reshape(-1)
+    if lateral.shape != vertical.shape:
+        raise ValueError("lateral and vertical must have one value per frame each")
+    left = (topo.coords[:, 0] == topo.coords[:, 0].min()) & ~topo.fix3.all(axis=1)
+    horizontal = topo.coords[topo.conn[:, 0], 1] == topo.coords[topo.conn[:, 1], 1]
+    loads = torch.zeros((lateral.shape[0], topo.Nn, 3), **f64)
+    loads[:, torch.as_tensor(np.nonzero(left)[0], device=topo.device), 0] = lateral[:, None]
+    w = torch.zeros((lateral.shape[0], topo.Ne, 2), **f64)
+    w[:, torch.as_tensor(np.nonzero(horizontal)[0], device=topo.device), :] = vertical[:, None, None]
+    return loads, w
+
+
+def frame_dataset_draws(n_cases: int, lateral_range=(0.5e4, 2e4), vertical_range=(-2e4, -0.5e4), seed: int = 0):
+    """The load magnitudes of `generate_frame_dataset`: (lateral [n_cases], vertical [n_cases]) float64 numpy, uniform over the two
+    ranges from `np.random.default_rng(seed)` -- all lateral values first, then all vertical ones."""
+    if n_cases < 0:
+        raise ValueError("n_cases must be >= 0")
+    rng = np.random.default_rng(seed)
+    lateral = rng.uniform(lateral_range[0], lateral_range[1], size=n_cases)
+    vertical = rng.uniform(vertical_range[0], vertical_range[1], size=n_cases)
+    return lateral, vertical
+
+
+def generate_frame_dataset(num_bays: int, num_stories: int, n_cases: int, cfg: Optional[FrameConfig] = None,
+                           lateral_range=(0.5e4, 2e4), vertical_range=(-2e4, -0.5e4), seed: int = 0, gradient: str = "explicit",
+                           max_epochs: Optional[int] = None, **objective) -> dict:
+    """`n_cases` sized designs of the reference's num_bays x num_stories frame, each under its own wind and gravity load
+    (`frame_dataset_draws`, `grid_load_cases`), sized in one batch by `optimize_frames` (`objective`: its penalty keywords).
+    Returns CPU tensors: I [n,Ne] float32, lateral, vertical [n] float64, V, M [n,Ne] and disp [n,Nn,3] float64 (the last solve's),
+    epochs [n] int32, status [n] int32."""
+    cfg = cfg or FrameConfig()
+    topo = grid_frame(num_bays, num_stories, cfg)
+    lateral, vertical = frame_dataset_draws(n_cases, lateral_range, vertical_range, seed)
+    loads, w = grid_load_cases(topo, lateral, vertical)
+    I, sol, ep = optimize_frames(topo, n_cases, cfg, max_epochs=max_epochs, gradient=gradient, loads=loads, element_loads=w, **objective)
+    return dict(I=I.cpu(), lateral=torch.as_tensor(lateral), vertical=torch.as_tensor(vertical), V=sol.V.cpu(), M=sol.M.cpu(),
+                disp=sol.disp.cpu(), epochs=ep.cpu(), status=sol.status.cpu())

@@ -15,7 +15,10 @@ requiring one is an error rather than a silent None.
 csrc/frame_vjp.hip).  Operator arguments are tensors and ints: the inertias, the loads and the
 integer under which the `FrameTopology` -- whose arrays and per-stream workspaces the solve uses -- is registered here, and
 its node count (the output shapes of the fake implementation); `frame_solve_autograd` (= `frames.differentiable_frame_solve`) fills them
-in.  Gradients reach I and loads; status is not differentiable."""
+in.  Gradients reach I and loads; status is not differentiable.
+
+`torch.ops.openpystruct_amd.frame_solve_loads` / `frame_solve_loads_vjp` are that pair with the element loads as one more tensor
+argument ([Ne,2] shared or [B,Ne,2]: DESIGN.md §9i, csrc/frame_loads.hip); gradients reach them too."""
 from __future__ import annotations
 
 import itertools
@@ -147,7 +150,65 @@ def _frame_backward(ctx, g_disp, g_forces, gV, gM, gstatus):
 frame_solve_op.register_autograd(_frame_backward, setup_context=_frame_setup_context)
 
 
-def frame_solve_autograd(topo: frames.FrameTopology, I: T, loads: Optional[T] = None) -> frames.FrameSolution:
+# ---- the frame solve under per-call element loads ----
+@torch.library.custom_op("openpystruct_amd::frame_solve_loads", mutates_args=(), device_types="cuda")
+def frame_solve_loads_op(I: T, loads: T, element_loads: T, n_nodes: int, topology: int) -> Tuple[T, T, T, T, T]:
+    topo = _topology(topology)
+    if n_nodes != topo.Nn:
+        raise ValueError(f"openpystruct_amd::frame_solve_loads: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
+    s = frames.frame_solve(topo, I, loads, element_loads=element_loads)
+    return s.disp, s.forces, s.V, s.M, s.status
+
+
+@frame_solve_loads_op.register_fake
+def _(I, loads, element_loads, n_nodes, topology):
+    B, Ne = I.shape
+    return (I.new_empty((B, n_nodes, 3)), I.new_empty((B, Ne, 6)), I.new_empty((B, Ne)), I.new_empty((B, Ne)),
+            I.new_empty((B,), dtype=torch.int32))
+
+
+@torch.library.custom_op("openpystruct_amd::frame_solve_loads_vjp", mutates_args=(), device_types="cuda")
+def frame_solve_loads_vjp_op(I: T, disp: T, status: Optional[T], g_disp: Optional[T], g_forces: Optional[T], gV: Optional[T],
+                             gM: Optional[T], topology: int) -> Tuple[T, T, T, T]:
+    """(gI, g_loads per frame, g_w per frame, the adjoint solve's status): `frame_solve_vjp` -- neither gI nor g_loads depends on the
+    element loads -- and one more launch for g_w."""
+    topo = _topology(topology)
+    gI, lam, st = frames.frame_solve_vjp(topo, I, disp, g_disp, g_forces, gV, gM, status)
+    return gI, lam, frames.frame_element_load_vjp(topo, lam, g_forces, gV, gM, status, st), st
+
+
+@frame_solve_loads_vjp_op.register_fake
+def _(I, disp, status, g_disp, g_forces, gV, gM, topology):
+    B, Ne = I.shape
+    return I.new_empty(I.shape), disp.new_empty(disp.shape), I.new_empty((B, Ne, 2)), I.new_empty((B,), dtype=torch.int32)
+
+
+def _frame_loads_setup_context(ctx, inputs, output):
+    I, loads, element_loads, n_nodes, topology = inputs
+    ctx.mark_non_differentiable(output[4])
+    ctx.save_for_backward(I, output[0], output[4])
+    ctx.topo, ctx.topology = _topologies.get(topology), topology
+    ctx.loads_shared, ctx.w_shared = loads.dim() == 2, element_loads.dim() == 2
+
+
+def _frame_loads_backward(ctx, g_disp, g_forces, gV, gM, gstatus):
+    I, disp, status = ctx.saved_tensors
+    gI, g_loads, g_w, _ = torch.ops.openpystruct_amd.frame_solve_loads_vjp(I, disp, status, g_disp, g_forces, gV, gM, ctx.topology)
+    if ctx.needs_input_grad[1] and ctx.loads_shared:       # one load set for the batch: the sum over the frames
+        g_loads = g_loads.sum(0)
+    if ctx.needs_input_grad[2] and ctx.w_shared:
+        g_w = g_w.sum(0)
+    return (gI if ctx.needs_input_grad[0] else None, g_loads if ctx.needs_input_grad[1] else None,
+            g_w if ctx.needs_input_grad[2] else None, None, None)
+
+
+frame_solve_loads_op.register_autograd(_frame_loads_backward, setup_context=_frame_loads_setup_context)
+
+
+def frame_solve_autograd(topo: frames.FrameTopology, I: T, loads: Optional[T] = None,
+                         element_loads: Optional[T] = None) -> frames.FrameSolution:
     if loads is None:
         loads = topo.d_loads
+    if element_loads is not None:
+        return frames.FrameSolution(*torch.ops.openpystruct_amd.frame_solve_loads(I, loads, element_loads, topo.Nn, _topology_id(topo)))
     return frames.FrameSolution(*torch.ops.openpystruct_amd.frame_solve(I, loads, topo.Nn, _topology_id(topo)))
