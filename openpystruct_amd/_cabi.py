@@ -15,8 +15,6 @@ import types
 _PKG = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd.h")
 # additions to the C ABI that change no declaration of HEADER_PATH (and so not OPS_AMD_ABI_VERSION) have headers of their own
-# (the beam sizing header stays the last entry: tests/test_sizing_grad_emulation.py reads it as EXTENSION_HEADER_PATHS[-1]; the frame
-# sizing header stays entry 1)
 EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_vjp.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_sizing.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_loads.h"),
@@ -154,8 +152,9 @@ TfdFrontArgs = _struct("ops_tfd_front_args")
 TfdFrontBwdArgs = _struct("ops_tfd_front_bwd_args")
 BayesLayer = _struct("ops_bayes_layer")
 BayesMcArgs = _struct("ops_bayes_mc_args")
-SizingObjective = _extensions[EXTENSION_HEADER_PATHS[-1]].structs["ops_sizing_objective"]
-FrameSizingObjective = _extensions[EXTENSION_HEADER_PATHS[1]].structs["ops_frame_sizing_objective"]
+_extension_structs = {name: cls for _ext in _extensions.values() for name, cls in _ext.structs.items()}
+SizingObjective = _extension_structs["ops_sizing_objective"]
+FrameSizingObjective = _extension_structs["ops_frame_sizing_objective"]
 # every OPS_AMD_X / OPS_X of the header as X: OK, ERR_*, FIX_*, ABI_VERSION, FRAME_REUSE_PLAN, MLP_*, BAYES_*, WGRAD_MAX_GROUP, ADAM_*, ...
 for _name, _value in _abi.defines.items():
     _short = _name[len("OPS_AMD_"):] if _name.startswith("OPS_AMD_") else _name[len("OPS_"):]

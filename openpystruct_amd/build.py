@@ -29,7 +29,7 @@ HEADERS = [os.path.join(CSRC, "lane_common.hpp"), os.path.join(CSRC, "library.hp
            os.path.join(ROOT, "include", "openpystruct_amd_frame_vjp.h"), os.path.join(CSRC, "sizing_grad_math.hpp"),
            os.path.join(ROOT, "include", "openpystruct_amd_sizing_grad.h"), os.path.join(CSRC, "frame_sizing_math.hpp"),
            os.path.join(ROOT, "include", "openpystruct_amd_frame_sizing.h"), os.path.join(CSRC, "frame_loads.hpp"),
-           os.path.join(ROOT, "include", "openpystruct_amd_frame_loads.h")]
+           os.path.join(ROOT, "include", "openpystruct_amd_frame_loads.h"), os.path.join(CSRC, "frame_stream.hpp")]
 ARCH = "gfx950"
 
 

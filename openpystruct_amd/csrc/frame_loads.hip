@@ -3,25 +3,16 @@
 //
 // The solve is linear in the element loads, so the band kernels stay as they are: the caller runs
 // ops_frame_solve_batched_f64_ex between the first two kernels (loads = rhs, per frame; elem_w = zeros).  All three kernels
-// are one thread per output row -- (frame, node) or (frame, element), the frame slowest, so a wave's stores are one
-// contiguous run -- over a grid-stride loop; no LDS, no atomics: every output is one thread's sum in a fixed order, the
-// same bits for every batch size and every position of a frame in the batch.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// are one thread per output row, (frame, node) or (frame, element), by frame_stream.hpp's row loop and launch: the same bits
+// for every batch size and every position of a frame in the batch.
+#include "frame_stream.hpp"
 
-#include "../../include/openpystruct_amd.h"
 #include "../../include/openpystruct_amd_frame_loads.h"
 #include "frame_loads.hpp"
-#include "library.hpp"
 
 namespace opsamd {
 
-struct FrameLoadParams {
-  int B, Nn, Ne;
-  const double* elem_geo;          // [Ne,3]  L, cos, sin
-  const int32_t* conn;             // [Ne,2]
-  const int32_t* node_elem_ptr;    // [Nn+1]
-  const int32_t* node_elem_idx;    // [2 Ne]  2 * element + end
+struct FrameLoadParams : FrameStreamTopo {
   const double* loads;             // [Nn,3] or [B,Nn,3]
   const double* elem_w;            // [Ne,2] or [B,Ne,2]  wy, wx
   long loads_bstride, w_bstride;
@@ -35,32 +26,18 @@ struct FrameLoadParams {
   double* g_w;                     // [B,Ne,2]
 };
 
-constexpr int FL_BLOCK = 256;
-constexpr long FL_MAX_GRID = 2048;     // memory-bound: a few workgroups per CU, the rest of the rows by grid stride
-
-// frame of row i, `per` rows to a frame: a 32-bit division wherever the row count allows (csrc/frame_vjp.hip row_frame)
-__device__ __forceinline__ long fl_row_frame(long i, int per, bool small) {
-  return small ? (long)((unsigned)i / (unsigned)per) : i / per;
-}
-
-__global__ __launch_bounds__(FL_BLOCK) void frame_load_rhs_kernel(const FrameLoadParams p) {
-  const long total = (long)p.B * p.Nn, stride = (long)gridDim.x * FL_BLOCK;
-  for (long i = (long)blockIdx.x * FL_BLOCK + threadIdx.x; i < total; i += stride) {
-    const long b = fl_row_frame(i, p.Nn, total <= 0x7fffffffL);
-    const int n = (int)(i - b * p.Nn);
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_load_rhs_kernel(const FrameLoadParams p) {
+  frame_stream_rows(p.B, p.Nn, [&](long i, long b, int n) {
     double r[3];
     fl_node_rhs(p.Nn, p.elem_geo, p.node_elem_ptr, p.node_elem_idx, p.loads, p.loads_bstride, p.elem_w, p.w_bstride, b, n, r);
     double* o = p.rhs + i * 3;
     o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
-  }
+  });
 }
 
-__global__ __launch_bounds__(FL_BLOCK) void frame_load_forces_kernel(const FrameLoadParams p) {
-  const long total = (long)p.B * p.Ne, stride = (long)gridDim.x * FL_BLOCK;
-  for (long i = (long)blockIdx.x * FL_BLOCK + threadIdx.x; i < total; i += stride) {
-    const long b = fl_row_frame(i, p.Ne, total <= 0x7fffffffL);
-    const int e = (int)(i - b * p.Ne);
-    if (p.status && p.status[b] != 0) continue;       // a failed frame keeps the solve's NaN rows
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_load_forces_kernel(const FrameLoadParams p) {
+  frame_stream_rows(p.B, p.Ne, [&](long i, long b, int e) {
+    if (p.status && p.status[b] != 0) return;         // a failed frame keeps the solve's NaN rows
     double* fo = p.forces + i * 6;
     double f[6];
     for (int k = 0; k < 6; ++k) f[k] = fo[k];
@@ -68,32 +45,17 @@ __global__ __launch_bounds__(FL_BLOCK) void frame_load_forces_kernel(const Frame
     for (int k = 0; k < 6; ++k) fo[k] = f[k];
     p.V[i] = f[1];
     p.M[i] = f[2];
-  }
+  });
 }
 
-__global__ __launch_bounds__(FL_BLOCK) void frame_load_vjp_kernel(const FrameLoadParams p) {
-  const long total = (long)p.B * p.Ne, stride = (long)gridDim.x * FL_BLOCK;
-  for (long i = (long)blockIdx.x * FL_BLOCK + threadIdx.x; i < total; i += stride) {
-    const long b = fl_row_frame(i, p.Ne, total <= 0x7fffffffL);
-    const int e = (int)(i - b * p.Ne);
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_load_vjp_kernel(const FrameLoadParams p) {
+  frame_stream_rows(p.B, p.Ne, [&](long i, long b, int e) {
     const bool bad = (p.status && p.status[b] != 0) || (p.status_adj && p.status_adj[b] != 0);
     double gw[2];
     fl_elem_gw(p.Nn, p.Ne, p.elem_geo, p.conn, p.lambda, p.g_forces, p.gV, p.gM, b, e, gw);
     p.g_w[2 * i] = bad ? __builtin_nan("") : gw[0];
     p.g_w[2 * i + 1] = bad ? __builtin_nan("") : gw[1];
-  }
-}
-
-static int launch(void (*kernel)(const FrameLoadParams), const FrameLoadParams& p, long rows, void* stream) {
-  const long need = (rows + FL_BLOCK - 1) / FL_BLOCK;
-  const unsigned grid = (unsigned)(need < FL_MAX_GRID ? need : FL_MAX_GRID);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(FL_BLOCK), 0, (hipStream_t)stream, p);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  });
 }
 
 static bool stride_ok(long stride, long full) { return stride == 0 || stride == full; }
@@ -113,7 +75,7 @@ extern "C" int ops_frame_load_rhs_f64(int B, int n_nodes, int n_elems, const dou
   p.B = B; p.Nn = n_nodes; p.Ne = n_elems;
   p.elem_geo = elem_geo; p.node_elem_ptr = node_elem_ptr; p.node_elem_idx = node_elem_idx;
   p.loads = loads; p.loads_bstride = loads_bstride; p.elem_w = elem_w; p.w_bstride = w_bstride; p.rhs = rhs;
-  return launch(frame_load_rhs_kernel, p, (long)B * n_nodes, stream);
+  return frame_stream_launch(frame_load_rhs_kernel, p, (long)B * n_nodes, stream);
 }
 
 extern "C" int ops_frame_load_forces_f64(int B, int n_elems, const double* elem_geo, const double* elem_w, long w_bstride,
@@ -126,7 +88,7 @@ extern "C" int ops_frame_load_forces_f64(int B, int n_elems, const double* elem_
   p.B = B; p.Ne = n_elems;
   p.elem_geo = elem_geo; p.elem_w = elem_w; p.w_bstride = w_bstride; p.status = status;
   p.forces = forces; p.V = V; p.M = M;
-  return launch(frame_load_forces_kernel, p, (long)B * n_elems, stream);
+  return frame_stream_launch(frame_load_forces_kernel, p, (long)B * n_elems, stream);
 }
 
 extern "C" int ops_frame_load_vjp_f64(int B, int n_nodes, int n_elems, const double* elem_geo, const int32_t* conn,
@@ -139,5 +101,5 @@ extern "C" int ops_frame_load_vjp_f64(int B, int n_nodes, int n_elems, const dou
   p.B = B; p.Nn = n_nodes; p.Ne = n_elems;
   p.elem_geo = elem_geo; p.conn = conn; p.lambda = lambda; p.g_forces = g_forces; p.gV = gV; p.gM = gM;
   p.status = status_fwd; p.status_adj = status_adj; p.g_w = g_w;
-  return launch(frame_load_vjp_kernel, p, (long)B * n_elems, stream);
+  return frame_stream_launch(frame_load_vjp_kernel, p, (long)B * n_elems, stream);
 }

@@ -26,21 +26,18 @@ FA_HD void fl_pg(double L, double c, double s, double wy, double wx, double pg[6
   pg[5] = pl[5];
 }
 
-// the three loads of node n of frame b: its own nodal load plus the consistent loads of its incident element ends, walked
-// as node_elem_idx[node_elem_ptr[n] .. node_elem_ptr[n + 1]) (2 * element + end) in that one fixed order.  loads_bstride:
-// 0 (one [Nn,3] for the batch) or 3 Nn; w_bstride: 0 (one [Ne,2]) or 2 Ne
+// the three loads of node n of frame b: its own nodal load plus the consistent loads of its incident element ends, in the one
+// fixed order of fa_walk (frame_adjoint.hpp).  loads_bstride: 0 (one [Nn,3] for the batch) or 3 Nn; w_bstride: 0 (one [Ne,2])
+// or 2 Ne
 FA_HD void fl_node_rhs(int n_nodes, const double* elem_geo, const int32_t* node_elem_ptr, const int32_t* node_elem_idx,
                        const double* loads, long loads_bstride, const double* elem_w, long w_bstride, long b, int n,
                        double r[3]) {
   const double* ld = loads + b * loads_bstride + 3 * (long)n;
   const double* w = elem_w + b * w_bstride;
   for (int k = 0; k < 3; ++k) r[k] = ld[k];
-  for (int p = node_elem_ptr[n]; p < node_elem_ptr[n + 1]; ++p) {
-    const int e = node_elem_idx[p] >> 1, end = node_elem_idx[p] & 1;
-    double pg[6];
+  fa_walk(node_elem_ptr, node_elem_idx, n, r, [&](int e, double pg[6]) {
     fl_pg(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], w[2 * e], w[2 * e + 1], pg);
-    for (int k = 0; k < 3; ++k) r[k] += pg[3 * end + k];
-  }
+  });
 }
 
 // f (the six global end forces of element e of frame b, solved without element loads) -= pg_e
@@ -52,16 +49,14 @@ FA_HD void fl_elem_forces(const double* elem_geo, const double* elem_w, long w_b
 }
 
 // (g_wy, g_wx) of element e of frame b from the adjoint displacements (lambda: zero on constrained DOFs) and the folded
-// cotangent of the forces; pg is linear in (wy, wx), so its derivatives are pg of the unit loads
+// cotangent of the forces; pg is linear in (wy, wx), so its derivatives are pg of the unit loads.  The difference is lambda - g_f,
+// the negative of fa_contract's: the sign of a zero sum depends on it, so the contraction is this function's own
 FA_HD void fl_elem_gw(int n_nodes, int n_elems, const double* elem_geo, const int32_t* conn, const double* lambda,
                       const double* g_forces, const double* gV, const double* gM, long b, int e, double gw[2]) {
-  const long n1 = b * n_nodes + conn[2 * e], n2 = b * n_nodes + conn[2 * e + 1];
   double gf[6], d[6], dy[6], dx[6];
+  fa_gather(n_nodes, conn, lambda, b, e, d);      // (before the fold: fewer live registers on the device)
   fa_fold(g_forces, gV, gM, b * n_elems + e, gf);
-  for (int k = 0; k < 3; ++k) {
-    d[k] = lambda[n1 * 3 + k] - gf[k];
-    d[3 + k] = lambda[n2 * 3 + k] - gf[3 + k];
-  }
+  for (int k = 0; k < 6; ++k) d[k] -= gf[k];
   fl_pg(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], 1.0, 0.0, dy);
   fl_pg(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], 0.0, 1.0, dx);
   double ay = 0.0, ax = 0.0;

@@ -12,24 +12,16 @@
 // partial sums.  The order of every addition is a function of Nn alone: loss_extra does not depend on B, on the frame's place in
 // the batch or on the grid.  Frames are dealt to wavefronts in order, so a wavefront stores one contiguous run of rhs rows per
 // pass (with idle lanes where Nn < G).  No LDS, no atomics.
-// grad kernel: one thread per (frame, element), as frame_grad_contract_kernel.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// grad kernel: one thread per (frame, element), as frame_grad_contract_kernel (frame_stream.hpp's row loop; both kernels go
+// through its launch).
+#include "frame_stream.hpp"
 
 #include "../../include/openpystruct_amd_frame_sizing.h"
 #include "frame_sizing_math.hpp"
-#include "library.hpp"
 
 namespace opsamd {
 
-struct FrameSizingParams {
-  int B, Nn, Ne;
-  const double* elem_geo;          // [Ne,3]  L, cos, sin
-  const double* elem_EA;           // [Ne]
-  const double* elem_E;            // [Ne]
-  const int32_t* conn;             // [Ne,2]
-  const int32_t* node_elem_ptr;    // [Nn+1]
-  const int32_t* node_elem_idx;    // [2 Ne]  2 * element + end
+struct FrameSizingParams : FrameStreamTopo {
   const double* I;                 // [B,Ne]
   const double* disp;              // [B,Nn,3]  this epoch's forward
   const double* V; const double* M;   // [B,Ne]
@@ -42,15 +34,12 @@ struct FrameSizingParams {
   double* grad;                    // [B,Ne]
 };
 
-constexpr int FS_BLOCK = 256;
-constexpr long FS_MAX_GRID = 2048;     // memory-bound: a few workgroups per CU, the rest by grid stride
-
 template <int G>
-__global__ __launch_bounds__(FS_BLOCK) void frame_sizing_rhs_kernel(const FrameSizingParams p) {
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_sizing_rhs_kernel(const FrameSizingParams p) {
   constexpr int FPW = 64 / G;           // frames per wavefront
   const int lane = threadIdx.x & 63, g = lane / G, j = lane - g * G;
   const long groups = ((long)p.B + FPW - 1) / FPW;
-  const long wave = (long)blockIdx.x * (FS_BLOCK / 64) + (threadIdx.x >> 6), waves = (long)gridDim.x * (FS_BLOCK / 64);
+  const long wave = (long)blockIdx.x * (FRAME_STREAM_BLOCK / 64) + (threadIdx.x >> 6), waves = (long)gridDim.x * (FRAME_STREAM_BLOCK / 64);
   for (long w = wave; w < groups; w += waves) {      // wave-uniform trip count: every lane reaches the butterfly
     const long b = w * FPW + g;
     const bool inb = b < p.B;
@@ -74,39 +63,20 @@ __global__ __launch_bounds__(FS_BLOCK) void frame_sizing_rhs_kernel(const FrameS
   }
 }
 
-// frame of row i of `total` rows, `per` rows to a frame (frame_vjp.hip: the 64-bit division is a long instruction sequence)
-__device__ __forceinline__ long fs_row_frame(long i, int per, bool small) {
-  return small ? (long)((unsigned)i / (unsigned)per) : i / per;
-}
-
-__global__ __launch_bounds__(FS_BLOCK) void frame_sizing_grad_kernel(const FrameSizingParams p) {
-  const long total = (long)p.B * p.Ne, stride = (long)gridDim.x * FS_BLOCK;
-  for (long i = (long)blockIdx.x * FS_BLOCK + threadIdx.x; i < total; i += stride) {
-    const long b = fs_row_frame(i, p.Ne, total <= 0x7fffffffL);
-    if (p.active && !p.active[b]) continue;
-    const int e = (int)(i - b * p.Ne);
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_sizing_grad_kernel(const FrameSizingParams p) {
+  frame_stream_rows(p.B, p.Ne, [&](long i, long b, int e) {
+    if (p.active && !p.active[b]) return;
     const bool bad = (p.status_fwd && p.status_fwd[b] != 0) || (p.status_adj && p.status_adj[b] != 0);
     const double g = fs_elem_grad(p.o, p.Nn, p.Ne, p.elem_geo, p.elem_E, p.conn, p.I, p.V, p.M, p.disp, p.lambda, b, e);
     p.grad[i] = bad ? __builtin_nan("") : g;
-  }
+  });
 }
 
+// a wavefront (64 threads) per 64 / G frames: frame_stream_launch's one thread per row with 64 rows to a group of frames
 template <int G>
-static hipError_t launch_rhs(const FrameSizingParams& p, hipStream_t stream) {
+static int launch_rhs(const FrameSizingParams& p, void* stream) {
   constexpr int FPW = 64 / G;
-  const long groups = ((long)p.B + FPW - 1) / FPW, per_block = FS_BLOCK / 64;
-  const long need = (groups + per_block - 1) / per_block;
-  const unsigned grid = (unsigned)(need < FS_MAX_GRID ? need : FS_MAX_GRID);
-  hipLaunchKernelGGL((frame_sizing_rhs_kernel<G>), dim3(grid), dim3(FS_BLOCK), 0, stream, p);
-  return hipGetLastError();
-}
-
-static int launched(hipError_t err) {
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return frame_stream_launch(frame_sizing_rhs_kernel<G>, p, (((long)p.B + FPW - 1) / FPW) * 64, stream);
 }
 
 static FrameSizingObj objective(const ops_sizing_params* hp, double aS, double s_lim, double aD, double d_lim) {
@@ -137,12 +107,11 @@ extern "C" int ops_frame_sizing_rhs_f64(int B, int n_nodes, int n_elems, const d
   p.I = I; p.disp = disp; p.V = V; p.M = M;
   p.o = objective(hp, obj->alpha_sway, obj->sway_limit, obj->alpha_deflection, obj->deflection_limit);
   p.active = active; p.rhs = rhs; p.loss_extra = loss_extra;
-  hipStream_t s = (hipStream_t)stream;
-  if (n_nodes <= 4) return launched(launch_rhs<4>(p, s));
-  if (n_nodes <= 8) return launched(launch_rhs<8>(p, s));
-  if (n_nodes <= 16) return launched(launch_rhs<16>(p, s));
-  if (n_nodes <= 32) return launched(launch_rhs<32>(p, s));
-  return launched(launch_rhs<64>(p, s));
+  if (n_nodes <= 4) return launch_rhs<4>(p, stream);
+  if (n_nodes <= 8) return launch_rhs<8>(p, stream);
+  if (n_nodes <= 16) return launch_rhs<16>(p, stream);
+  if (n_nodes <= 32) return launch_rhs<32>(p, stream);
+  return launch_rhs<64>(p, stream);
 }
 
 extern "C" int ops_frame_sizing_grad_f64(int B, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
@@ -159,8 +128,5 @@ extern "C" int ops_frame_sizing_grad_f64(int B, int n_nodes, int n_elems, const 
   p.I = I; p.disp = disp; p.V = V; p.M = M; p.lambda = lambda;
   p.o = objective(hp, 0.0, 0.0, 0.0, 0.0);      // the hinges reach the gradient through lambda alone
   p.active = active; p.status_fwd = status_fwd; p.status_adj = status_adj; p.grad = grad;
-  const long need = ((long)B * n_elems + FS_BLOCK - 1) / FS_BLOCK;
-  const unsigned grid = (unsigned)(need < FS_MAX_GRID ? need : FS_MAX_GRID);
-  hipLaunchKernelGGL(frame_sizing_grad_kernel, dim3(grid), dim3(FS_BLOCK), 0, (hipStream_t)stream, p);
-  return launched(hipGetLastError());
+  return frame_stream_launch(frame_sizing_grad_kernel, p, (long)B * n_elems, stream);
 }

@@ -2,7 +2,8 @@
 // for the device (csrc/frame_sizing_grad.hip) and with g++ for the host (tests/test_frame_sizing_grad_host.py builds a
 // stand-alone program from this file).  Nothing is restated: the objective's cotangents and its explicit part are the
 // functions of sizing_grad_math.hpp (the beam objective's: sizing_quot, sizing_gM, sizing_gV, sizing_explicit, sizing_defl,
-// sizing_gv), the element stiffness is fa_apply_k of frame_adjoint.hpp.
+// sizing_gv); the element stiffness, the node walk and the end-node contraction are fa_apply_k, fa_scatter_k and fa_contract
+// of frame_adjoint.hpp.
 //
 //   L(I) = sum_e I_e + aM sum_e M_e^2 / (2 E I_e + bend_eps) + aV sum_e V_e^2 / (G area_coef sqrt(I_e))
 //        + aS sum_n h(|ux_n|, s_lim) + aD sum_n h(|uy_n|, d_lim),      h(a, lim) = (max(0, a - lim) / lim)^2
@@ -34,9 +35,9 @@ FA_HD void fs_fold(const SizingObj& o, const SizingQuot& q, double gf[6]) {
   gf[3] = 0.0; gf[4] = 0.0; gf[5] = 0.0;
 }
 
-// The three adjoint loads of node n of frame b (fa_node_rhs with the objective's cotangents in place of arrays; the same fixed
-// order over the node's incident ends).  Returns the node's share of the two hinge terms.  sizing_defl compares, and a
-// comparison drops a NaN: a NaN displacement (a frame whose forward failed) is forwarded to the returned value by hand.
+// The three adjoint loads of node n of frame b (fa_node_rhs with the objective's cotangents in place of arrays: the same walk,
+// fa_scatter_k).  Returns the node's share of the two hinge terms.  sizing_defl compares, and a comparison drops a NaN: a NaN
+// displacement (a frame whose forward failed) is forwarded to the returned value by hand.
 FA_HD double fs_node_rhs(const FrameSizingObj& o, int n_nodes, int n_elems, const double* elem_geo, const double* elem_EA,
                          const double* elem_E, const int32_t* node_elem_ptr, const int32_t* node_elem_idx, const double* I,
                          const double* disp, const double* V, const double* M, long b, int n, double r[3]) {
@@ -45,38 +46,23 @@ FA_HD double fs_node_rhs(const FrameSizingObj& o, int n_nodes, int n_elems, cons
   r[0] = sizing_gv(o.sway, ux);
   r[1] = sizing_gv(o.defl, uy);
   r[2] = 0.0;
-  for (int p = node_elem_ptr[n]; p < node_elem_ptr[n + 1]; ++p) {
-    const int e = node_elem_idx[p] >> 1, end = node_elem_idx[p] & 1;
-    const long row = b * n_elems + e;
-    double gf[6], y[6];
-    fs_fold(o.sway, sizing_quot(o.sway, I[row], V[row], M[row]), gf);
-    fa_apply_k(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], elem_EA[e], elem_E[e] * I[row], gf, y);
-    for (int k = 0; k < 3; ++k) r[k] += y[3 * end + k];
-  }
+  fa_scatter_k(n_elems, elem_geo, elem_EA, elem_E, node_elem_ptr, node_elem_idx, I, b, n, r,
+               [&](long row, double gf[6]) { fs_fold(o.sway, sizing_quot(o.sway, I[row], V[row], M[row]), gf); });
   const double h = sizing_defl(o.sway, ux) + sizing_defl(o.defl, uy);
   return (ux != ux || uy != uy) ? ux + uy : h;
 }
 
-// dL/dI of element e of frame b from the forward's (I, V, M, disp) and the adjoint's displacements lambda
+// dL/dI of element e of frame b from the forward's (I, V, M, disp) and the adjoint's displacements lambda: the explicit part plus
+// fa_contract of the objective's cotangents
 FA_HD double fs_elem_grad(const FrameSizingObj& o, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
                           const int32_t* conn, const double* I, const double* V, const double* M, const double* disp,
                           const double* lambda, long b, int e) {
   const long row = b * n_elems + e;
-  const long n1 = b * n_nodes + conn[2 * e], n2 = b * n_nodes + conn[2 * e + 1];
   const double Ie = I[row], Ve = V[row];
   const SizingQuot q = sizing_quot(o.sway, Ie, Ve, M[row]);
-  double gf[6], u[6], d[6], y[6];
+  double gf[6];
   fs_fold(o.sway, q, gf);
-  for (int k = 0; k < 3; ++k) {
-    u[k] = disp[n1 * 3 + k];
-    u[3 + k] = disp[n2 * 3 + k];
-    d[k] = gf[k] - lambda[n1 * 3 + k];
-    d[3 + k] = gf[3 + k] - lambda[n2 * 3 + k];
-  }
-  fa_apply_k(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], 0.0, elem_E[e], u, y);
-  double acc = 0.0;
-  for (int k = 0; k < 6; ++k) acc += d[k] * y[k];
-  return sizing_explicit(o.sway, Ie, Ve, q) + acc;
+  return sizing_explicit(o.sway, Ie, Ve, q) + fa_contract(n_nodes, elem_geo, elem_E, conn, disp, lambda, gf, b, e);
 }
 
 }  // namespace opsamd

@@ -4,27 +4,16 @@
 //
 // The stiffness matrix is symmetric, so the adjoint system is the forward system with another right-hand side: the caller
 // runs ops_frame_solve_batched_f64_ex between the two kernels (loads = rhs, per frame; elem_w = zeros) and the band kernels
-// stay as they are.  Both kernels are one thread per output row -- (frame, node) and (frame, element), the frame slowest,
-// so a wave's stores are one contiguous run and its loads of I, the cotangents and the displacements are runs of
-// neighbouring rows -- over a grid-stride loop; no LDS, no atomics: every output is one thread's sum in a fixed order.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// stay as they are.  Both kernels are one thread per output row, (frame, node) and (frame, element): the row loop and the
+// launch are frame_stream.hpp's.
+#include "frame_stream.hpp"
 
-#include "../../include/openpystruct_amd.h"
 #include "../../include/openpystruct_amd_frame_vjp.h"
 #include "frame_adjoint.hpp"
-#include "library.hpp"
 
 namespace opsamd {
 
-struct FrameVjpParams {
-  int B, Nn, Ne;
-  const double* elem_geo;          // [Ne,3]  L, cos, sin
-  const double* elem_EA;           // [Ne]
-  const double* elem_E;            // [Ne]
-  const int32_t* conn;             // [Ne,2]
-  const int32_t* node_elem_ptr;    // [Nn+1]
-  const int32_t* node_elem_idx;    // [2 Ne]  2 * element + end
+struct FrameVjpParams : FrameStreamTopo {
   const double* I;                 // [B,Ne]
   const double* disp;              // [B,Nn,3]
   const double* lambda;            // [B,Nn,3]
@@ -36,49 +25,22 @@ struct FrameVjpParams {
   double* gI;                      // [B,Ne]
 };
 
-constexpr int FV_BLOCK = 256;
-constexpr long FV_MAX_GRID = 2048;     // memory-bound: a few workgroups per CU, the rest of the rows by grid stride
-
-// frame of row i of `total` rows, `per` rows to a frame: a 32-bit division wherever the row count allows (the 64-bit one is a
-// long instruction sequence on this target); `small` is uniform over the launch
-__device__ __forceinline__ long row_frame(long i, int per, bool small) {
-  return small ? (long)((unsigned)i / (unsigned)per) : i / per;
-}
-
-__global__ __launch_bounds__(FV_BLOCK) void frame_adjoint_rhs_kernel(const FrameVjpParams p) {
-  const long total = (long)p.B * p.Nn, stride = (long)gridDim.x * FV_BLOCK;
-  for (long i = (long)blockIdx.x * FV_BLOCK + threadIdx.x; i < total; i += stride) {
-    const long b = row_frame(i, p.Nn, total <= 0x7fffffffL);
-    const int n = (int)(i - b * p.Nn);
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_adjoint_rhs_kernel(const FrameVjpParams p) {
+  frame_stream_rows(p.B, p.Nn, [&](long i, long b, int n) {
     double r[3];
     fa_node_rhs(p.Nn, p.Ne, p.elem_geo, p.elem_EA, p.elem_E, p.node_elem_ptr, p.node_elem_idx, p.I, p.g_disp, p.g_forces,
                 p.gV, p.gM, b, n, r);
     double* o = p.rhs + i * 3;
     o[0] = r[0]; o[1] = r[1]; o[2] = r[2];
-  }
+  });
 }
 
-__global__ __launch_bounds__(FV_BLOCK) void frame_grad_contract_kernel(const FrameVjpParams p) {
-  const long total = (long)p.B * p.Ne, stride = (long)gridDim.x * FV_BLOCK;
-  for (long i = (long)blockIdx.x * FV_BLOCK + threadIdx.x; i < total; i += stride) {
-    const long b = row_frame(i, p.Ne, total <= 0x7fffffffL);
-    const int e = (int)(i - b * p.Ne);
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_grad_contract_kernel(const FrameVjpParams p) {
+  frame_stream_rows(p.B, p.Ne, [&](long i, long b, int e) {
     const bool bad = (p.status_fwd && p.status_fwd[b] != 0) || (p.status_adj && p.status_adj[b] != 0);
     const double g = fa_elem_gI(p.Nn, p.Ne, p.elem_geo, p.elem_E, p.conn, p.disp, p.lambda, p.g_forces, p.gV, p.gM, b, e);
     p.gI[i] = bad ? __builtin_nan("") : g;
-  }
-}
-
-static int launch(void (*kernel)(const FrameVjpParams), const FrameVjpParams& p, long rows, void* stream) {
-  const long need = (rows + FV_BLOCK - 1) / FV_BLOCK;
-  const unsigned grid = (unsigned)(need < FV_MAX_GRID ? need : FV_MAX_GRID);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(FV_BLOCK), 0, (hipStream_t)stream, p);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  });
 }
 
 }  // namespace opsamd
@@ -98,7 +60,7 @@ extern "C" int ops_frame_adjoint_rhs_f64(int B, int n_nodes, int n_elems, const 
   p.elem_geo = elem_geo; p.elem_EA = elem_EA; p.elem_E = elem_E;
   p.conn = conn; p.node_elem_ptr = node_elem_ptr; p.node_elem_idx = node_elem_idx;
   p.I = I; p.g_disp = g_disp; p.g_forces = g_forces; p.gV = gV; p.gM = gM; p.rhs = rhs;
-  return launch(frame_adjoint_rhs_kernel, p, (long)B * n_nodes, stream);
+  return frame_stream_launch(frame_adjoint_rhs_kernel, p, (long)B * n_nodes, stream);
 }
 
 extern "C" int ops_frame_grad_contract_f64(int B, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
@@ -113,5 +75,5 @@ extern "C" int ops_frame_grad_contract_f64(int B, int n_nodes, int n_elems, cons
   p.elem_geo = elem_geo; p.elem_E = elem_E; p.conn = conn;
   p.disp = disp; p.lambda = lambda; p.g_forces = g_forces; p.gV = gV; p.gM = gM;
   p.status_fwd = status_fwd; p.status_adj = status_adj; p.gI = gI;
-  return launch(frame_grad_contract_kernel, p, (long)B * n_elems, stream);
+  return frame_stream_launch(frame_grad_contract_kernel, p, (long)B * n_elems, stream);
 }

@@ -178,17 +178,27 @@ class FrameSolution(NamedTuple):
     status: torch.Tensor    # [B] int32
 
 
+def _checked(name: str, t, dtype, shape: tuple, dev=None, *, gpu_for: str = "", optional: bool = False, in_place: bool = False):
+    """The one tensor check of this module: `t`, contiguous, if it is a `dtype` tensor of `shape` (None: any batch size) on `dev` (None:
+    wherever it is), else ValueError.  `gpu_for`: the entry's name -- anything but a GPU tensor is a RuntimeError.  `optional`: None
+    passes as None.  `in_place`: the caller uses `t`'s own memory, so a tensor that is not contiguous is refused rather than copied."""
+    if t is None and optional:
+        return None
+    if gpu_for and (not torch.is_tensor(t) or not t.is_cuda):
+        raise RuntimeError(f"{gpu_for} needs GPU tensors: openpystruct_amd has no CPU fallback")
+    fits = t.dim() == len(shape) and all(want is None or want == have for want, have in zip(shape, t.shape))
+    if t.dtype != dtype or (dev is not None and t.device != dev) or not fits or (in_place and not t.is_contiguous()):
+        what = f"{str(dtype).split('.')[-1]} [{', '.join('B' if n is None else str(n) for n in shape)}]"
+        raise ValueError(f"{name} must be {'contiguous ' if in_place else ''}{what}" + (f" on {dev}" if dev is not None else ""))
+    return t.contiguous()
+
+
 def frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tensor] = None,
                 out: Optional[FrameSolution] = None, element_loads: Optional[torch.Tensor] = None) -> FrameSolution:
     """`element_loads`: float64 [Ne,2] or [B,Ne,2] (wy, wx) REPLACES the topology's `wy` / `wx` for this call, per frame when it has
     a batch dimension (three launches -- the right-hand side with the consistent loads, the solve without element
     loads on a workspace of its own, the correction of the forces); None: the topology's element loads, one launch."""
-    lib = _cabi.load()
-    if not torch.is_tensor(I) or not I.is_cuda:
-        raise RuntimeError("frame_solve needs GPU tensors: openpystruct_amd has no CPU fallback")
-    if I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne:
-        raise ValueError(f"I must be float64 [B, {topo.Ne}]")
-    I = I.contiguous()
+    I = _checked("I", I, torch.float64, (None, topo.Ne), gpu_for="frame_solve")
     B = I.shape[0]
     dev = I.device
     if loads is None:
@@ -316,28 +326,13 @@ def frame_solve_vjp(topo: FrameTopology, I: torch.Tensor, disp: torch.Tensor, g_
     element loads), the per-element contraction (csrc/frame_vjp.hip).  A frame whose factorisation fails has status != 0 and NaN rows;
     `status` [B] int32: the forward's status, when given a frame that failed there gets a NaN gI row whatever its `disp` holds."""
     lib = _cabi.load()
-    if not torch.is_tensor(I) or not I.is_cuda:
-        raise RuntimeError("frame_solve_vjp needs GPU tensors: openpystruct_amd has no CPU fallback")
-    if I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne:
-        raise ValueError(f"I must be float64 [B, {topo.Ne}]")
-    I = I.contiguous()
+    I = _checked("I", I, torch.float64, (None, topo.Ne), gpu_for="frame_solve_vjp")
     B, dev = I.shape[0], I.device
-    shapes = dict(disp=(B, topo.Nn, 3), g_disp=(B, topo.Nn, 3), g_forces=(B, topo.Ne, 6), gV=(B, topo.Ne), gM=(B, topo.Ne))
-
-    def dense(name, t):
-        if t is None:
-            return None
-        if t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != shapes[name]:
-            raise ValueError(f"{name} must be float64 {list(shapes[name])} on {dev}")
-        return t.contiguous()
-
-    disp, g_disp, g_forces, gV, gM = (dense(k, v) for k, v in (("disp", disp), ("g_disp", g_disp), ("g_forces", g_forces), ("gV", gV), ("gM", gM)))
     if disp is None:
         raise ValueError("disp: the forward's displacements are needed")
-    if status is not None:
-        if status.dtype != torch.int32 or status.device != dev or tuple(status.shape) != (B,):
-            raise ValueError(f"status must be int32 [{B}] on {dev}")
-        status = status.contiguous()
+    disp, g_disp = (_checked(k, v, torch.float64, (B, topo.Nn, 3), dev, optional=True) for k, v in (("disp", disp), ("g_disp", g_disp)))
+    g_forces, gV, gM = _checked_cotangents(topo, B, dev, g_forces, gV, gM)
+    status = _checked("status", status, torch.int32, (B,), dev, optional=True)
     adj = _adjoint_tables(topo)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     rhs = torch.empty((B, topo.Nn, 3), dtype=torch.float64, device=dev)
@@ -360,6 +355,13 @@ def frame_solve_vjp(topo: FrameTopology, I: torch.Tensor, disp: torch.Tensor, g_
     return gI, sol.disp, sol.status
 
 
+def _checked_cotangents(topo: FrameTopology, B: int, dev, g_forces, gV, gM) -> tuple:
+    """The optional cotangents of the element results: forces [B,Ne,6], V and M [B,Ne]."""
+    return (_checked("g_forces", g_forces, torch.float64, (B, topo.Ne, 6), dev, optional=True),
+            _checked("gV", gV, torch.float64, (B, topo.Ne), dev, optional=True),
+            _checked("gM", gM, torch.float64, (B, topo.Ne), dev, optional=True))
+
+
 def frame_element_load_vjp(topo: FrameTopology, lam: torch.Tensor, g_forces: Optional[torch.Tensor] = None,
                            gV: Optional[torch.Tensor] = None, gM: Optional[torch.Tensor] = None,
                            status: Optional[torch.Tensor] = None, status_adj: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -368,30 +370,10 @@ def frame_element_load_vjp(topo: FrameTopology, lam: torch.Tensor, g_forces: Opt
     zero).  One launch on the current stream (csrc/frame_loads.hip).  `status` / `status_adj` [B] int32: the forward's and the
     adjoint solve's; a frame with a non-zero one gets a NaN row.  Element loads shared by the batch take the sum over the frames."""
     lib = _cabi.load()
-    if not torch.is_tensor(lam) or not lam.is_cuda:
-        raise RuntimeError("frame_element_load_vjp needs GPU tensors: openpystruct_amd has no CPU fallback")
-    if lam.dtype != torch.float64 or lam.dim() != 3 or tuple(lam.shape[1:]) != (topo.Nn, 3):
-        raise ValueError(f"lam must be float64 [B, {topo.Nn}, 3]")
-    lam = lam.contiguous()
+    lam = _checked("lam", lam, torch.float64, (None, topo.Nn, 3), gpu_for="frame_element_load_vjp")
     B, dev = lam.shape[0], lam.device
-    shapes = dict(g_forces=(B, topo.Ne, 6), gV=(B, topo.Ne), gM=(B, topo.Ne))
-
-    def dense(name, t):
-        if t is None:
-            return None
-        if t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != shapes[name]:
-            raise ValueError(f"{name} must be float64 {list(shapes[name])} on {dev}")
-        return t.contiguous()
-
-    def flags(name, t):
-        if t is None:
-            return None
-        if t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != (B,):
-            raise ValueError(f"{name} must be int32 [{B}] on {dev}")
-        return t.contiguous()
-
-    g_forces, gV, gM = (dense(k, v) for k, v in (("g_forces", g_forces), ("gV", gV), ("gM", gM)))
-    status, status_adj = flags("status", status), flags("status_adj", status_adj)
+    g_forces, gV, gM = _checked_cotangents(topo, B, dev, g_forces, gV, gM)
+    status, status_adj = (_checked(k, v, torch.int32, (B,), dev, optional=True) for k, v in (("status", status), ("status_adj", status_adj)))
     adj = _adjoint_tables(topo)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     g_w = torch.empty((B, topo.Ne, 2), dtype=torch.float64, device=dev)
@@ -493,25 +475,53 @@ def frame_sizing_gradient(topo: FrameTopology, I: torch.Tensor, sol: FrameSoluti
     `deflection_limit`: penalties, not constraints.  Returns (grad, loss_extra, status): loss_extra [B] is the value of the two
     displacement terms (None when both alphas are 0), status [B] the adjoint solve's (non-zero: the frame's row is NaN, as it is for
     a frame with sol.status != 0).  Rows of frames with active[b] == 0 are not written."""
-    if not torch.is_tensor(I) or not I.is_cuda:
-        raise RuntimeError("frame_sizing_gradient needs GPU tensors: openpystruct_amd has no CPU fallback")
-    if I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne or not I.is_contiguous():
-        raise ValueError(f"I must be a contiguous float64 tensor of shape [B, {topo.Ne}]")
+    I = _checked("I", I, torch.float64, (None, topo.Ne), gpu_for="frame_sizing_gradient", in_place=True)
     B, dev = I.shape[0], I.device
     _, aS, s_lim, aD, d_lim = _objective("total", alpha_sway, sway_limit, alpha_deflection, deflection_limit)
     hp = _sizing_params(hp) if isinstance(hp, FrameConfig) else hp
     for name, t, shape in (("sol.disp", sol.disp, (B, topo.Nn, 3)), ("sol.V", sol.V, (B, topo.Ne)), ("sol.M", sol.M, (B, topo.Ne))):
-        if tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous float64 tensor of shape {shape} on {dev}")
-    if tuple(sol.status.shape) != (B,) or sol.status.dtype != torch.int32 or sol.status.device != dev:
-        raise ValueError(f"sol.status must be an int32 tensor of shape {(B,)} on {dev}")
-    if active is not None and (tuple(active.shape) != (B,) or active.dtype != torch.uint8 or active.device != dev):
-        raise ValueError(f"active must be a uint8 tensor of shape {(B,)} on {dev}")
+        _checked(name, t, torch.float64, shape, dev, in_place=True)
+    sol = sol._replace(status=_checked("sol.status", sol.status, torch.int32, (B,), dev))
+    active = _checked("active", active, torch.uint8, (B,), dev, optional=True)
     buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
     if B:
         obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
         _sizing_grad_launches(topo, I, sol, hp, obj, active, buf)
     return buf.grad, buf.loss_extra, buf.adj.status
+
+
+class _StepState(NamedTuple):
+    """The tensors the optimiser step kernels update in place, one row per frame."""
+    I: torch.Tensor              # [B,Ne] float32: the design
+    I64: torch.Tensor            # [B,Ne] float64: the design as the solve reads it
+    exp_avg: torch.Tensor        # [B,Ne] float32 (Adam)
+    exp_avg_sq: torch.Tensor     # [B,Ne] float32
+    best: torch.Tensor           # [B] float32: early stopping
+    patience_cnt: torch.Tensor   # [B] int32
+    epochs: torch.Tensor         # [B] int32
+    active: torch.Tensor         # [B] uint8
+    last: torch.Tensor           # [B] float32: the epoch's total_loss
+    V32: torch.Tensor            # [B,Ne] float32
+    M32: torch.Tensor            # [B,Ne] float32
+
+
+def _sizing_step(st: _StepState, sol: FrameSolution, hp, buf: Optional[_SizingGradBuffers]) -> None:
+    """One optimiser step with the early-stop bookkeeping, on the current stream: on the explicit gradient formed from (V, M) where
+    `buf` is None, else on the gradient (and the loss's displacement terms) that `_sizing_grad_launches` left in `buf`."""
+    lib = _cabi.load()
+    B, Ne = st.I.shape
+    dev = st.I.device
+    design = (B, Ne, st.I.data_ptr(), st.I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr())
+    state = tuple(t.data_ptr() for t in st[2:])
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if buf is None:
+            name, rc = "ops_beam_sizing_step_f32", lib.ops_beam_sizing_step_f32(*design, *state, ctypes.byref(hp), stream)
+        else:
+            extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
+            name, rc = "ops_beam_sizing_step_grad_f32", lib.ops_beam_sizing_step_grad_f32(*design, buf.grad.data_ptr(), extra, *state,
+                                                                                          ctypes.byref(hp), None, stream)
+    _cabi.check(rc, name)
 
 
 def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
@@ -532,67 +542,48 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
     _, aS, s_lim, aD, d_lim = _objective(gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit)
     if gradient == "total" and topo.Ne > 512:
         raise ValueError(f'gradient="total" serves up to 512 elements per frame (the optimiser step kernel), got {topo.Ne}')
-    lib = _cabi.load()
-    dev = topo.device
-    Ne = topo.Ne
-    f32 = dict(dtype=torch.float32, device=dev)
+    dev, Ne = topo.device, topo.Ne
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
     I = (I0.to(**f32).clone() if I0 is not None else torch.full((B, Ne), cfg.I0, **f32))
-    I64 = I.double()
-    ea, es = torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32)
-    best = torch.full((B,), float("inf"), **f32)
-    cnt = torch.zeros((B,), dtype=torch.int32, device=dev)
-    ep = torch.zeros((B,), dtype=torch.int32, device=dev)
-    active = torch.ones((B,), dtype=torch.uint8, device=dev)
-    last = torch.zeros((B,), **f32)
-    V32, M32 = torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32)
+    st = _StepState(I, I.double(), torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32), torch.full((B,), float("inf"), **f32),
+                    torch.zeros((B,), **i32), torch.zeros((B,), **i32), torch.ones((B,), dtype=torch.uint8, device=dev),
+                    torch.zeros((B,), **f32), torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32))
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
     hp = _sizing_params(cfg, n_max)
-    sol = None
     if loads is not None:
         if not torch.is_tensor(loads) or not loads.is_cuda:
             raise RuntimeError("loads must be a GPU tensor: openpystruct_amd has no CPU fallback")
         loads = loads.to(torch.float64).contiguous()
         _check_nodal_loads(topo, loads, B, I.device)
-    if element_loads is not None:      # every buffer of the three-launch forward, before the loop
+    # every buffer of the loop, before it (the one-launch forward with the explicit step allocates its solution in the first epoch);
+    # the forward is one callable that fills and returns its solution
+    sol = _empty_solution(topo, B, dev) if element_loads is not None or gradient == "total" else None
+    if element_loads is not None:      # the three-launch forward
         w, wbs = _checked_element_loads(topo, element_loads, B, I.device)
         fwd_loads = topo.d_loads if loads is None else loads
         lbs = topo.Nn * 3 if fwd_loads.dim() == 3 else 0
-        sol = _empty_solution(topo, B, dev)
         fwd_rhs = torch.empty((B, topo.Nn, 3), dtype=torch.float64, device=dev)
-    if gradient == "total":      # every buffer of the loop, before it
-        sol = sol if sol is not None else _empty_solution(topo, B, dev)
+
+        def forward(out):
+            _element_load_launches(topo, st.I64, fwd_loads, lbs, w, wbs, fwd_rhs, out)
+            return out
+    else:
+        forward = lambda out: frame_solve(topo, st.I64, loads, out=out)  # noqa: E731
+    buf = None
+    if gradient == "total":
         buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
         obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
-        extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
     for e in range(n_max):
-        if element_loads is not None:
-            _element_load_launches(topo, I64, fwd_loads, lbs, w, wbs, fwd_rhs, sol)
-        elif loads is not None:
-            sol = frame_solve(topo, I64, loads, out=sol)
-        else:
-            sol = frame_solve(topo, I64, out=sol)
-        if gradient == "total":
-            _sizing_grad_launches(topo, I64, sol, hp, obj, active, buf)
-            with torch.cuda.device(dev):
-                rc = lib.ops_beam_sizing_step_grad_f32(B, Ne, I.data_ptr(), I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(),
-                                                       buf.grad.data_ptr(), extra, ea.data_ptr(), es.data_ptr(), best.data_ptr(),
-                                                       cnt.data_ptr(), ep.data_ptr(), active.data_ptr(), last.data_ptr(),
-                                                       V32.data_ptr(), M32.data_ptr(), ctypes.byref(hp), None,
-                                                       torch.cuda.current_stream(dev).cuda_stream)
-            _cabi.check(rc, "ops_beam_sizing_step_grad_f32")
-        else:
-            with torch.cuda.device(dev):
-                rc = lib.ops_beam_sizing_step_f32(B, Ne, I.data_ptr(), I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), ea.data_ptr(),
-                                                  es.data_ptr(), best.data_ptr(), cnt.data_ptr(), ep.data_ptr(), active.data_ptr(),
-                                                  last.data_ptr(), V32.data_ptr(), M32.data_ptr(), ctypes.byref(hp),
-                                                  torch.cuda.current_stream(dev).cuda_stream)
-            _cabi.check(rc, "ops_beam_sizing_step_f32")
+        sol = forward(sol)
+        if buf is not None:
+            _sizing_grad_launches(topo, st.I64, sol, hp, obj, st.active, buf)
+        _sizing_step(st, sol, hp, buf)
         if loss_history is not None:
-            loss_history.append(last.clone())
-        if (e + 1) % poll_every == 0 and not bool(active.any()):
+            loss_history.append(st.last.clone())
+        if (e + 1) % poll_every == 0 and not bool(st.active.any()):
             break
     torch.cuda.synchronize(dev)
-    return I, sol, ep
+    return I, sol, st.epochs
 
 
 def grid_load_cases(topo: FrameTopology, lateral, vertical):

@@ -104,20 +104,41 @@ def _topology(tid: int) -> frames.FrameTopology:
     return topo
 
 
-@torch.library.custom_op("openpystruct_amd::frame_solve", mutates_args=(), device_types="cuda")
-def frame_solve_op(I: T, loads: T, n_nodes: int, topology: int) -> Tuple[T, T, T, T, T]:
+# The two forward operators (with and without the element loads as an argument) share their body, their fake implementation,
+# their context setup and the core of their backward; their arguments end in (n_nodes, topology).
+def _frame_solve(name: str, I: T, loads: T, element_loads: Optional[T], n_nodes: int, topology: int) -> Tuple[T, T, T, T, T]:
     topo = _topology(topology)
     if n_nodes != topo.Nn:
-        raise ValueError(f"openpystruct_amd::frame_solve: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
-    s = frames.frame_solve(topo, I, loads)
+        raise ValueError(f"openpystruct_amd::{name}: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
+    s = frames.frame_solve(topo, I, loads, element_loads=element_loads)
     return s.disp, s.forces, s.V, s.M, s.status
 
 
-@frame_solve_op.register_fake
-def _(I, loads, n_nodes, topology):
+def _frame_solve_fake(I, *args):
     B, Ne = I.shape
-    return (I.new_empty((B, n_nodes, 3)), I.new_empty((B, Ne, 6)), I.new_empty((B, Ne)), I.new_empty((B, Ne)),
+    return (I.new_empty((B, args[-2], 3)), I.new_empty((B, Ne, 6)), I.new_empty((B, Ne)), I.new_empty((B, Ne)),
             I.new_empty((B,), dtype=torch.int32))
+
+
+def _frame_setup_context(ctx, inputs, output):
+    ctx.mark_non_differentiable(output[4])
+    ctx.save_for_backward(inputs[0], output[0], output[4])
+    # the operators name the topology by an integer that is valid while the object lives: the graph keeps it alive
+    ctx.topo, ctx.topology = _topologies.get(inputs[-1]), inputs[-1]
+    ctx.shared = [False] + [t.dim() == 2 for t in inputs[1:-2]]      # per tensor input: one load set for the batch
+
+
+def _frame_backward(ctx, vjp_op, g_disp, g_forces, gV, gM, gstatus):
+    """The VJP operator returns (gI, g_loads[, g_w], status), the load gradients per frame: a shared input receives the sum over the frames."""
+    I, disp, status = ctx.saved_tensors
+    grads = vjp_op(I, disp, status, g_disp, g_forces, gV, gM, ctx.topology)[:-1]
+    return tuple((g.sum(0) if shared else g) if need else None
+                 for g, shared, need in zip(grads, ctx.shared, ctx.needs_input_grad)) + (None, None)
+
+
+@torch.library.custom_op("openpystruct_amd::frame_solve", mutates_args=(), device_types="cuda")
+def frame_solve_op(I: T, loads: T, n_nodes: int, topology: int) -> Tuple[T, T, T, T, T]:
+    return _frame_solve("frame_solve", I, loads, None, n_nodes, topology)
 
 
 @torch.library.custom_op("openpystruct_amd::frame_solve_vjp", mutates_args=(), device_types="cuda")
@@ -131,40 +152,10 @@ def _(I, disp, status, g_disp, g_forces, gV, gM, topology):
     return I.new_empty(I.shape), disp.new_empty(disp.shape), I.new_empty((I.shape[0],), dtype=torch.int32)
 
 
-def _frame_setup_context(ctx, inputs, output):
-    I, loads, n_nodes, topology = inputs
-    ctx.mark_non_differentiable(output[4])
-    ctx.save_for_backward(I, output[0], output[4])
-    # the operators name the topology by an integer that is valid while the object lives: the graph keeps it alive
-    ctx.topo, ctx.topology, ctx.loads_shared = _topologies.get(topology), topology, loads.dim() == 2
-
-
-def _frame_backward(ctx, g_disp, g_forces, gV, gM, gstatus):
-    I, disp, status = ctx.saved_tensors
-    gI, g_loads, _ = torch.ops.openpystruct_amd.frame_solve_vjp(I, disp, status, g_disp, g_forces, gV, gM, ctx.topology)
-    if ctx.needs_input_grad[1] and ctx.loads_shared:       # one [Nn,3] load set for the batch: the sum over the frames
-        g_loads = g_loads.sum(0)
-    return (gI if ctx.needs_input_grad[0] else None, g_loads if ctx.needs_input_grad[1] else None, None, None)
-
-
-frame_solve_op.register_autograd(_frame_backward, setup_context=_frame_setup_context)
-
-
 # ---- the frame solve under per-call element loads ----
 @torch.library.custom_op("openpystruct_amd::frame_solve_loads", mutates_args=(), device_types="cuda")
 def frame_solve_loads_op(I: T, loads: T, element_loads: T, n_nodes: int, topology: int) -> Tuple[T, T, T, T, T]:
-    topo = _topology(topology)
-    if n_nodes != topo.Nn:
-        raise ValueError(f"openpystruct_amd::frame_solve_loads: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
-    s = frames.frame_solve(topo, I, loads, element_loads=element_loads)
-    return s.disp, s.forces, s.V, s.M, s.status
-
-
-@frame_solve_loads_op.register_fake
-def _(I, loads, element_loads, n_nodes, topology):
-    B, Ne = I.shape
-    return (I.new_empty((B, n_nodes, 3)), I.new_empty((B, Ne, 6)), I.new_empty((B, Ne)), I.new_empty((B, Ne)),
-            I.new_empty((B,), dtype=torch.int32))
+    return _frame_solve("frame_solve_loads", I, loads, element_loads, n_nodes, topology)
 
 
 @torch.library.custom_op("openpystruct_amd::frame_solve_loads_vjp", mutates_args=(), device_types="cuda")
@@ -183,26 +174,10 @@ def _(I, disp, status, g_disp, g_forces, gV, gM, topology):
     return I.new_empty(I.shape), disp.new_empty(disp.shape), I.new_empty((B, Ne, 2)), I.new_empty((B,), dtype=torch.int32)
 
 
-def _frame_loads_setup_context(ctx, inputs, output):
-    I, loads, element_loads, n_nodes, topology = inputs
-    ctx.mark_non_differentiable(output[4])
-    ctx.save_for_backward(I, output[0], output[4])
-    ctx.topo, ctx.topology = _topologies.get(topology), topology
-    ctx.loads_shared, ctx.w_shared = loads.dim() == 2, element_loads.dim() == 2
-
-
-def _frame_loads_backward(ctx, g_disp, g_forces, gV, gM, gstatus):
-    I, disp, status = ctx.saved_tensors
-    gI, g_loads, g_w, _ = torch.ops.openpystruct_amd.frame_solve_loads_vjp(I, disp, status, g_disp, g_forces, gV, gM, ctx.topology)
-    if ctx.needs_input_grad[1] and ctx.loads_shared:       # one load set for the batch: the sum over the frames
-        g_loads = g_loads.sum(0)
-    if ctx.needs_input_grad[2] and ctx.w_shared:
-        g_w = g_w.sum(0)
-    return (gI if ctx.needs_input_grad[0] else None, g_loads if ctx.needs_input_grad[1] else None,
-            g_w if ctx.needs_input_grad[2] else None, None, None)
-
-
-frame_solve_loads_op.register_autograd(_frame_loads_backward, setup_context=_frame_loads_setup_context)
+for _op, _vjp in ((frame_solve_op, "frame_solve_vjp"), (frame_solve_loads_op, "frame_solve_loads_vjp")):
+    _op.register_fake(_frame_solve_fake)
+    _op.register_autograd(lambda ctx, *g, _vjp=_vjp: _frame_backward(ctx, getattr(torch.ops.openpystruct_amd, _vjp), *g),
+                          setup_context=_frame_setup_context)
 
 
 def frame_solve_autograd(topo: frames.FrameTopology, I: T, loads: Optional[T] = None,

@@ -224,7 +224,7 @@ def test_new_entry_points_are_declared_by_an_extension_header():
     assert {"ops_beam_sizing_grad_f64", "ops_beam_sizing_step_grad_f32"} <= set(_cabi.EXTENSION_EXPORTS)
     assert [n for n, _ in _cabi.SizingObjective._fields_] == ["alpha_deflection", "deflection_limit"]
     assert ctypes.sizeof(_cabi.SizingObjective) == 16
-    header = _cabi._extensions[_cabi.EXTENSION_HEADER_PATHS[-1]]
+    header, = (ext for path, ext in _cabi._extensions.items() if os.path.basename(path) == "openpystruct_amd_sizing_grad.h")
     restype, argtypes = header.functions["ops_beam_sizing_grad_f64"]
     assert restype is ctypes.c_int
     assert argtypes[16] == ctypes.POINTER(_cabi.SizingParams) and argtypes[17] == ctypes.POINTER(_cabi.SizingObjective)
