@@ -48,7 +48,8 @@ extern "C" {
  * 2*Ne eleResponse calls (:189-190) + 2*N nodeDisp calls (:224-232).
  *
  * Batch strides are in ELEMENTS of the array's type; a stride of 0 means "one value /
- * one row shared by every beam".
+ * one row shared by every beam".  I_bstride and Fy_bstride are below 2^31 (else
+ * OPS_AMD_ERR_INVALID_ARG).
  *
  *   x      [N] (x_bstride 0) or [B,N]     node coordinates along the beam   (`ops.node`)
  *   E      scalar (E_bstride 0) or [B,Ne] Young's modulus per element       (`ops.element` arg E)

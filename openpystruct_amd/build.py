@@ -31,6 +31,10 @@ HEADERS = [os.path.join(CSRC, "lane_common.hpp"), os.path.join(CSRC, "library.hp
            os.path.join(ROOT, "include", "openpystruct_amd_frame_sizing.h"), os.path.join(CSRC, "frame_loads.hpp"),
            os.path.join(ROOT, "include", "openpystruct_amd_frame_loads.h"), os.path.join(CSRC, "frame_stream.hpp")]
 ARCH = "gfx950"
+# Per-file flags.  beam_fat.hip: its kernels take their leading arguments as plain scalars and pointers (beam_io.hpp, RowsHead)
+# so that the hardware can hand them to every wave in SGPRs at launch; the compiler does that for up to 14 dwords when asked.
+# The code keeps a load prologue in front for firmware without the feature.
+FILE_FLAGS = {"beam_fat.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"]}
 
 
 def hipcc_path() -> str:
@@ -56,9 +60,17 @@ def _deps(path: str, seen=None) -> set:
     return seen
 
 
+def _file_flags(src: str) -> list:
+    return FILE_FLAGS.get(os.path.basename(src), [])
+
+
 def _flags() -> list:
     return ([f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-fast-math", "-ffp-contract=off", "-Wall",
              "-Wno-unused-command-line-argument"] + os.environ.get("OPS_AMD_EXTRA_HIPCC_FLAGS", "").split())   # e.g. -DOPS_AMD_TRACE (diagnostic build)
+
+
+def _flags_stamp() -> str:
+    return " ".join(_flags()) + "".join(f"\n{k}: {' '.join(v)}" for k, v in sorted(FILE_FLAGS.items()))
 
 
 def _obj(src: str) -> str:
@@ -68,7 +80,7 @@ def _obj(src: str) -> str:
 def _stale_objects(force: bool) -> list:
     """Sources whose object is older than the source, one of its headers, this file, or was built with other flags."""
     stamp = os.path.join(os.path.dirname(LIB), "obj", "flags.txt")
-    same_flags = os.path.exists(stamp) and open(stamp).read() == " ".join(_flags())
+    same_flags = os.path.exists(stamp) and open(stamp).read() == _flags_stamp()
     out = []
     for src in SOURCES:
         o = _obj(src)
@@ -103,7 +115,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
         flags = ["-Rpass-analysis=kernel-resource-usage"] + flags
 
     def compile_one(src):
-        subprocess.check_call([hipcc] + flags + ["-c", "-o", _obj(src) + ".tmp", src])
+        subprocess.check_call([hipcc] + flags + _file_flags(src) + ["-c", "-o", _obj(src) + ".tmp", src])
         os.replace(_obj(src) + ".tmp", _obj(src))
 
     jobs = jobs or int(os.environ.get("OPS_AMD_BUILD_JOBS", "0")) or min(len(todo) or 1, max(1, (os.cpu_count() or 2) - 1))
@@ -112,7 +124,7 @@ def build(force: bool = False, verbose: bool = False, jobs: int = 0) -> str:
     with ThreadPoolExecutor(max_workers=jobs) as ex:
         list(ex.map(compile_one, todo))
     with open(os.path.join(os.path.dirname(LIB), "obj", "flags.txt"), "w") as f:
-        f.write(" ".join(_flags()))
+        f.write(_flags_stamp())
     subprocess.check_call([hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", LIB + ".tmp"] + [_obj(s) for s in SOURCES])
     os.replace(LIB + ".tmp", LIB)
     return LIB

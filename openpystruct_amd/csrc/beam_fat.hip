@@ -78,7 +78,8 @@ struct ParkH {
 };
 
 #ifdef OPS_AMD_TRACE
-#define FAT_STAMP(k) stamps[k] = __builtin_amdgcn_s_memrealtime()
+// (between two scheduling barriers: a stamp is taken where it is written, not behind the next wait)
+#define FAT_STAMP(k) (__builtin_amdgcn_sched_barrier(0), stamps[k] = __builtin_amdgcn_s_memrealtime(), __builtin_amdgcn_sched_barrier(0))
 #else
 #define FAT_STAMP(k) ((void)0)
 #endif
@@ -159,7 +160,7 @@ __device__ __forceinline__ unsigned mask_window(unsigned long long lo, unsigned 
 // its cases on the shears / moments it holds in LDS (sizing_math.hpp) instead of storing them: the generator's fused
 // solve + step (SingleCore.py:174-219), as beam_solve.hip's beam_sizing_epoch_kernel.
 template <int P, int M, int WPS, bool FAT, bool SIZING>
-__device__ __forceinline__ void beam_rows_body(const BeamParams& p, const SizingArgs* sz) {
+__device__ __forceinline__ void beam_rows_body(const RowsHead& p, const RowsTail& t, const SizingArgs* sz) {
   constexpr int BPW = 64 / P;       // beams per wavefront
   constexpr int LIVE = BPW * P;     // lanes that own a segment
   constexpr int PM = P * M;         // padded nodes per beam (>= N); a row is one wave instruction of 16-byte lanes
@@ -171,7 +172,7 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
 #ifdef OPS_AMD_ST
   constexpr int ST = OPS_AMD_ST;
 #else
-  constexpr int ST = 16;            // sc1 (write-through); p.stream_out selects nt
+  constexpr int ST = 16;            // sc1 (write-through); t.stream_out selects nt
 #endif
   __shared__ double s_tab[6 * PM];
   __shared__ __attribute__((aligned(16))) double s_a[ROWS];   // I                  -> theta
@@ -186,18 +187,23 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
   const unsigned lane = threadIdx.x;
   unsigned long long stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // diagnostic builds (-DOPS_AMD_TRACE) only
   FAT_STAMP(0);
+  // ---- stage 1a: every global load is issued before anything waits; cache-resident ones first.  What the loads need
+  //      (RowsHead) is in SGPRs when the wave starts: the geometry, the rows, E[0] and wy[0] go out one after the other, none
+  //      of them behind a load of the arguments (the compiler places the two scalar loads behind the rows: same round trip).
   const int Ne = p.Ne, N = p.Ne + 1;
+  const long I_bs = p.I_bs, Fy_bs = p.Fy_bs;
   const long beam0 = (long)blockIdx.x * BPW;
   const int nb = (p.B - beam0 < BPW) ? (int)(p.B - beam0) : BPW;   // live beams of this wave
-  if (p.active) {                   // wave-uniform: finished cases of a sizing run cost one scalar load each
+  // (a test of the pointer at run time, as before: with the loop unconditional the compiler loads all of SizingArgs here and
+  //  spills it, v_readlane 82 -> 359 in the fused epoch, generate_s + 3.5 %)
+  if (SIZING && t.active) {         // wave-uniform: finished cases of a sizing run cost one scalar load each; the plain solve has no mask
     unsigned any = 0;
-    for (int b = 0; b < nb; ++b) any |= p.active[beam0 + b];
+    for (int b = 0; b < nb; ++b) any |= t.active[beam0 + b];
     if (!any) return;
   }
-
-  // ---- stage 1a: every global load is issued before anything waits; cache-resident ones first ----
-  double tx0[NT], tx1[NT];
   const double tE = p.E[0], tw = p.wy[0];
+  __builtin_amdgcn_sched_barrier(0);          // RowsTail's argument load stays the first instruction (else: behind the row loads)
+  double tx0[NT], tx1[NT];
   {
     const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, (unsigned)N * 8u);
 #pragma unroll
@@ -210,44 +216,45 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
   const int g_raw = lane / P, j = lane - g_raw * P, e0 = j * M;
   const bool live = (int)lane < LIVE;
   const int g = live ? g_raw : BPW - 1;          // idle lanes shadow the last group's low lanes; they write to s_dummy
-  // constraint bytes (one mask for all beams, host-checked): nodes `lane` and `lane + 64`; the wave ballots them
-  unsigned char fb0, fb1;
-  {
-    const __amdgpu_buffer_rsrc_t rf = make_rsrc(p.fix, (unsigned)N);
-    fb0 = __builtin_amdgcn_raw_buffer_load_b8(rf, (int)lane, 0, 0);            // nodes >= N: out of range -> 0 = free
-    fb1 = __builtin_amdgcn_raw_buffer_load_b8(rf, (int)(lane + 64u), 0, 0);
-  }
   // the wave's rows: lane l moves doubles 2l, 2l + 1 of every row (16 bytes), the last double of an odd row apart
   const int hE = Ne >> 1, hN = N >> 1;
   double2 rI[BPW], rF[BPW];
   double tI = 0.0, tF = 0.0;
   {
-    const __amdgpu_buffer_rsrc_t rsF = make_rsrc(p.Fy + beam0 * p.Fy_bs, (unsigned)(((long)(nb - 1) * p.Fy_bs + N) * 8));
+    const __amdgpu_buffer_rsrc_t rsF = make_rsrc(p.Fy + beam0 * Fy_bs, (unsigned)(((long)(nb - 1) * Fy_bs + N) * 8));
     const unsigned oobF = (int)lane < hN ? lane * 16u : 0x40000000u;
     const unsigned tb = lane < (unsigned)nb ? lane : 0u;               // lane b fetches the odd tail of row b
     if constexpr (SIZING) {          // float32 inertias (the reference's I_tensor, dense rows): 8-byte pairs, widened in registers
-      const __amdgpu_buffer_rsrc_t rsI = make_rsrc(p.I32 + beam0 * Ne, (unsigned)(nb * Ne) * 4u);
+      const __amdgpu_buffer_rsrc_t rsI = make_rsrc(static_cast<const float*>(p.I) + beam0 * Ne, (unsigned)(nb * Ne) * 4u);
       const unsigned oobI = (int)lane < hE ? lane * 8u : 0x40000000u;
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
         const float2 f = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rsI, (int)((unsigned)(b * Ne) * 4u + oobI), 0, 0));
         rI[b] = make_double2((double)f.x, (double)f.y);
-        rF[b] = buf_load_d2(rsF, (unsigned)(b * p.Fy_bs * 8) + oobF);
+        rF[b] = buf_load_d2(rsF, (unsigned)(b * Fy_bs * 8) + oobF);
       }
       if (Ne & 1) tI = (double)__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsI, (int)((tb * Ne + Ne - 1) * 4u), 0, 0));
     } else {
-      const __amdgpu_buffer_rsrc_t rsI = make_rsrc(p.I + beam0 * p.I_bs, (unsigned)(((long)(nb - 1) * p.I_bs + Ne) * 8));
+      const __amdgpu_buffer_rsrc_t rsI = make_rsrc(static_cast<const double*>(p.I) + beam0 * I_bs, (unsigned)(((long)(nb - 1) * I_bs + Ne) * 8));
       const unsigned oobI = (int)lane < hE ? lane * 16u : 0x40000000u;
 #pragma unroll
       for (int b = 0; b < BPW; ++b) {
-        rI[b] = buf_load_d2(rsI, (unsigned)(b * p.I_bs * 8) + oobI);     // rows of beams beyond B, lanes beyond the row: 0
-        rF[b] = buf_load_d2(rsF, (unsigned)(b * p.Fy_bs * 8) + oobF);
+        rI[b] = buf_load_d2(rsI, (unsigned)(b * I_bs * 8) + oobI);     // rows of beams beyond B, lanes beyond the row: 0
+        rF[b] = buf_load_d2(rsF, (unsigned)(b * Fy_bs * 8) + oobF);
       }
-      if (Ne & 1) tI = buf_load_d(rsI, (unsigned)((tb * p.I_bs + Ne - 1) * 8));
+      if (Ne & 1) tI = buf_load_d(rsI, (unsigned)((tb * I_bs + Ne - 1) * 8));
     }
-    if (N & 1) tF = buf_load_d(rsF, (unsigned)((tb * p.Fy_bs + N - 1) * 8));
+    if (N & 1) tF = buf_load_d(rsF, (unsigned)((tb * Fy_bs + N - 1) * 8));
   }
-  FAT_STAMP(5);
+  FAT_STAMP(5);                    // geometry and rows are on their way
+  // constraint bytes (one mask for all beams, host-checked): nodes `lane` and `lane + 64`; the wave ballots them.
+  // The mask's pointer is the first thing taken from RowsTail: these two loads go out when it has arrived, behind the rows
+  unsigned char fb0, fb1;
+  {
+    const __amdgpu_buffer_rsrc_t rf = make_rsrc(t.fix, (unsigned)N);
+    fb0 = __builtin_amdgcn_raw_buffer_load_b8(rf, (int)lane, 0, 0);            // nodes >= N: out of range -> 0 = free
+    fb1 = __builtin_amdgcn_raw_buffer_load_b8(rf, (int)(lane + 64u), 0, 0);
+  }
   // ---- stage 0: element table (unit-inertia stiffness tile entries, 1/L, UDL loads); padding as in beam_solve.hip ----
 #pragma unroll
   for (int k = 0; k < NT; ++k) {
@@ -334,8 +341,8 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
       if constexpr (FAT) out.sv[i] = qnan; else out.vr[i] = qnan;
     }
   }
-  if (j == 0 && live && g < nb && p.status)
-    __hip_atomic_store(&p.status[beam0 + g], gbad ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (j == 0 && live && g < nb && t.status)
+    __hip_atomic_store(&t.status[beam0 + g], gbad ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   double* const sth = live ? &s_a[g * PM + e0] : s_dummy;
   if constexpr (FAT) {                            // rotations: from registers into the dead inertia rows
 #pragma unroll
@@ -365,7 +372,7 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
   // ---- stage 5: rows out, one 16-byte store per lane and row.  All rows of an array are read from LDS before the
   //      first of them is stored (a store behind every read would pay one LDS round trip per row), and the next
   //      array's reads are issued before this array's stores.
-  const bool two = p.v != nullptr;                // wave-uniform: forces-only calls store two arrays
+  const bool two = t.v != nullptr;                // wave-uniform: forces-only calls store two arrays
   auto read_rows = [&](double2 (&r)[BPW], double& tail, const double* s, int n_) {
     const unsigned lrow = (int)lane < (n_ >> 1) ? lane : 0u;
 #pragma unroll
@@ -387,13 +394,13 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
     read_rows(ra, ta, s_b, Ne);
     read_rows(rb, tb, FAT ? s_m : s_a, Ne);
     if constexpr (FAT) {
-      store_rows(aux, p.V, ra, ta, Ne);
+      store_rows(aux, t.V, ra, ta, Ne);
       if (two) read_rows(ra, ta, s_v, N);
-      store_rows(aux, p.M, rb, tb, Ne);
+      store_rows(aux, t.M, rb, tb, Ne);
       if (two) {
         read_rows(rb, tb, s_a, N);
-        store_rows(aux, p.v, ra, ta, N);
-        store_rows(aux, p.theta, rb, tb, N);
+        store_rows(aux, t.v, ra, ta, N);
+        store_rows(aux, t.theta, rb, tb, N);
       }
     } else {
       if (two) {                                  // the row sets are in registers now: deflections / rotations take their place
@@ -402,24 +409,24 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
 #pragma unroll
         for (int i = 0; i < M; ++i) { svv[i] = out.vr[i]; sth[i] = out.th[i]; }
       }
-      store_rows(aux, p.V, ra, ta, Ne);
-      store_rows(aux, p.M, rb, tb, Ne);
+      store_rows(aux, t.V, ra, ta, Ne);
+      store_rows(aux, t.M, rb, tb, Ne);
       if (two) {
         wave_lds_fence();
         read_rows(ra, ta, s_b, N);
         read_rows(rb, tb, s_a, N);
-        store_rows(aux, p.v, ra, ta, N);
-        store_rows(aux, p.theta, rb, tb, N);
+        store_rows(aux, t.v, ra, ta, N);
+        store_rows(aux, t.theta, rb, tb, N);
       }
     }
   };
-  if (p.stream_out) all_rows(std::integral_constant<int, 2>{});   // wave-uniform
+  if (t.stream_out) all_rows(std::integral_constant<int, 2>{});   // wave-uniform
   else              all_rows(std::integral_constant<int, ST>{});
 #ifdef OPS_AMD_TRACE
-  if (p.trace && lane == 0) {   // per-wave phase stamps (100 MHz clock) + hardware id, for scripts/trace_run.py
+  if (t.trace && lane == 0) {   // per-wave phase stamps (100 MHz clock) + hardware id, for scripts/trace_run.py
     FAT_STAMP(3);
     stamps[4] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | ((16 - 1) << 11));
-    unsigned long long* q = p.trace + 8 * (unsigned long long)blockIdx.x;
+    unsigned long long* q = t.trace + 8 * (unsigned long long)blockIdx.x;
 #pragma unroll
     for (int k = 0; k < 8; ++k) q[k] = stamps[k];
   }
@@ -427,12 +434,15 @@ __device__ __forceinline__ void beam_rows_body(const BeamParams& p, const Sizing
 }
 
 template <int P, int M, int WPS, bool FAT>
-__global__ __launch_bounds__(64, WPS) void beam_rows_kernel(const BeamParams p) {
-  beam_rows_body<P, M, WPS, FAT, false>(p, nullptr);
+__global__ __launch_bounds__(64, WPS) void beam_rows_kernel(int Ne, int B, const void* I, const double* Fy, unsigned I_bs, unsigned Fy_bs,
+                                                           const double* x, const double* E, const double* wy, const RowsTail t) {
+  beam_rows_body<P, M, WPS, FAT, false>(RowsHead{Ne, B, I, Fy, I_bs, Fy_bs, x, E, wy}, t, nullptr);
 }
 template <int P, int M, int WPS>
-__global__ __launch_bounds__(64, WPS) void beam_rows_sizing_kernel(const BeamParams p, const SizingArgs sz) {
-  beam_rows_body<P, M, WPS, false, true>(p, &sz);
+// The fused epoch takes RowsHead as a struct, i.e. not preloaded: its wave reads `active` through RowsTail before anything else,
+// so nothing of it would start sooner.
+__global__ __launch_bounds__(64, WPS) void beam_rows_sizing_kernel(const RowsHead h, const RowsTail t, const SizingArgs sz) {
+  beam_rows_body<P, M, WPS, false, true>(h, t, &sz);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -445,9 +455,19 @@ const FatTiling kFatTilings[] = {
 };
 const int kNumFatTilings = sizeof(kFatTilings) / sizeof(kFatTilings[0]);
 
+// BeamParams as the row kernels take it: leading scalars (RowsHead's members, preloaded) and the trailing struct.  The
+// strides are below 2^31 and the wave's 32-bit row offsets hold (beam_solve.hip, solve_impl).
+static RowsHead rows_head(const BeamParams& p, const void* I) { return RowsHead{p.Ne, p.B, I, p.Fy, (unsigned)p.I_bs, (unsigned)p.Fy_bs, p.x, p.E, p.wy}; }
+static RowsTail rows_tail(const BeamParams& p) { return RowsTail{p.fix, p.v, p.theta, p.V, p.M, p.status, p.active, p.stream_out, p.trace}; }
+static void launch_rows(void (*kernel)(int, int, const void*, const double*, unsigned, unsigned, const double*, const double*, const double*, RowsTail),
+                        unsigned grid, hipStream_t stream, const BeamParams& p) {
+  const RowsHead h = rows_head(p, p.I);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), 0, stream, h.Ne, h.B, h.I, h.Fy, h.I_bs, h.Fy_bs, h.x, h.E, h.wy, rows_tail(p));
+}
+
 hipError_t launch_fat_sizing(const BeamParams& p, const SizingArgs& sz, int P, int M, hipStream_t stream) {
   const unsigned grid = (unsigned)((p.B + 64 / P - 1) / (64 / P));
-  if (P == 16 && M == 7) hipLaunchKernelGGL((beam_rows_sizing_kernel<16, 7, 3>), dim3(grid), dim3(64), 0, stream, p, sz);
+  if (P == 16 && M == 7) hipLaunchKernelGGL((beam_rows_sizing_kernel<16, 7, 3>), dim3(grid), dim3(64), 0, stream, rows_head(p, p.I32), rows_tail(p), sz);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
@@ -455,9 +475,9 @@ hipError_t launch_fat_sizing(const BeamParams& p, const SizingArgs& sz, int P, i
 hipError_t launch_fat(const BeamParams& p, int P, int M, hipStream_t stream) {
   const int bpw = 64 / P;
   const unsigned grid = (unsigned)((p.B + bpw - 1) / bpw);
-  if (P == 6 && M == 17) hipLaunchKernelGGL((beam_rows_kernel<6, 17, 1, true>), dim3(grid), dim3(64), 0, stream, p);
-  else if (P == 16 && M == 7) hipLaunchKernelGGL((beam_rows_kernel<16, 7, 3, false>), dim3(grid), dim3(64), 0, stream, p);
-  else if (P == 8 && M == 13) hipLaunchKernelGGL((beam_rows_kernel<8, 13, 2, false>), dim3(grid), dim3(64), 0, stream, p);
+  if (P == 6 && M == 17) launch_rows(beam_rows_kernel<6, 17, 1, true>, grid, stream, p);
+  else if (P == 16 && M == 7) launch_rows(beam_rows_kernel<16, 7, 3, false>, grid, stream, p);
+  else if (P == 8 && M == 13) launch_rows(beam_rows_kernel<8, 13, 2, false>, grid, stream, p);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }

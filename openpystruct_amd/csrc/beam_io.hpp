@@ -32,6 +32,30 @@ struct BeamParams {
   unsigned magic_ne, magic_n;
 };
 
+// The row kernels of beam_fat.hip do not take BeamParams by value: a wave of a by-value struct starts with a scalar load of
+// it from a cold scalar cache, and nothing of the prologue can issue before that round trip is over.  Leading parameters
+// that are plain scalars and pointers are delivered in SGPRs at wave launch instead (kernarg preloading, on for that file:
+// build.py); 14 dwords fit beside the argument pointer.  They are the members of RowsHead, in its order: what the wave needs
+// to issue its geometry and row loads, the row strides as 32-bit values (host-checked).  The constraint mask would be dwords
+// 15-16: it is the one input whose load may go out late (it is needed after the element table, and is a cached byte load), so
+// it travels in RowsTail with everything that is used after the row loads are in flight.  RowsTail is loaded as before (a
+// scalar load, requested by the wave's first instruction); its round trip runs under those loads.
+struct RowsHead {
+  int Ne, B;
+  const void* I;               // double rows, stride I_bs; sizing epochs: float rows, dense
+  const double* Fy;
+  unsigned I_bs, Fy_bs;
+  const double* x; const double* E; const double* wy;
+};
+struct RowsTail {
+  const uint8_t* fix;
+  double* v; double* theta; double* V; double* M;
+  int32_t* status;
+  const uint8_t* active;       // sizing epochs only
+  int stream_out;
+  unsigned long long* trace;   // diagnostic builds (-DOPS_AMD_TRACE) only
+};
+
 // fat-wave tilings (beam_fat.hip): shared geometry and constraint mask only; a tiling serves Ne with Ne + 1 <= P * M
 struct FatTiling { int P, M; const char* name; };
 extern const FatTiling kFatTilings[];

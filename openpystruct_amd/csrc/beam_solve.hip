@@ -591,6 +591,7 @@ static int solve_impl(int B, int Ne, const double* x, long x_bstride, const doub
   if (B == 0) return OPS_AMD_OK;
   if (!x || !E || (!I && !sz) || !fix || !Fy || !wy || ((!V || !M) && !sz) || ((v == nullptr) != (theta == nullptr))) return OPS_AMD_ERR_INVALID_ARG;
   if (I_bstride < Ne || Fy_bstride < Ne + 1) return OPS_AMD_ERR_INVALID_ARG;
+  if (I_bstride >= (1l << 31) || Fy_bstride >= (1l << 31)) return OPS_AMD_ERR_INVALID_ARG;   // the row kernels take them as 32-bit values
   if ((x_bstride != 0 && x_bstride < Ne + 1) || (fix_bstride != 0 && fix_bstride < Ne + 1) ||
       (E_bstride != 0 && E_bstride < Ne) || (wy_bstride != 0 && wy_bstride < Ne))
     return OPS_AMD_ERR_INVALID_ARG;
@@ -611,7 +612,9 @@ static int solve_impl(int B, int Ne, const double* x, long x_bstride, const doub
     // (the fused sizing epoch: 16-lane rows kernel only; an `active` mask is the sizing epoch's, nobody else's)
     const bool fat_ok = shared && fix_bstride == 0 && !f32_forces && (sz ? true : !active);
     const FatTiling* f = choose_fat(B, Ne, tiling);
-    if (f && fat_ok && (!sz || f->P == 16)) fat = f;
+    // a wave of the row kernels addresses its 64 / P rows with 32-bit byte offsets from its first row
+    const bool rows_fit = f && (unsigned long long)(64 / f->P - 1) * (unsigned long long)(I_bstride > Fy_bstride ? I_bstride : Fy_bstride) + Ne + 1 < (1ull << 29);
+    if (f && fat_ok && rows_fit && (!sz || f->P == 16)) fat = f;
     else if (is_fat_tiling(tiling)) return f ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
   }
   const Tiling* t = fat ? nullptr : choose_tiling(B, Ne, tiling & ~OPS_AMD_TILING_ROWS);

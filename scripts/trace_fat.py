@@ -24,7 +24,8 @@ prev = None
 for nm, k in names:
     c = col(k)
     d = "" if prev is None else "  (+%.2f med since previous)" % np.median(c - prev)
-    print("%-15s min %.2f p10 %.2f med %.2f p90 %.2f max %.2f us%s" % (nm, c.min(), np.percentile(c, 10), np.median(c), np.percentile(c, 90), c.max(), d))
+    print("%-15s min %.2f p10 %.2f p25 %.2f med %.2f p75 %.2f p90 %.2f max %.2f us%s"
+          % (nm, c.min(), *np.percentile(c, [10, 25, 50, 75, 90]), c.max(), d))
     prev = c
 hw = t[:, 4]; wid = hw & 15
 import collections
