@@ -481,6 +481,29 @@ def _layer_ok(layer: nn.Module) -> bool:
             and type(layer.norm2) is nn.LayerNorm and layer.norm1.elementwise_affine and layer.norm2.elementwise_affine)
 
 
+def attention_support(S: int, H: int, dh: int):
+    """(forward, backward): whether ops_seq_attention_fwd / _bwd (csrc/seq_block.hip) take sequences of S tokens, H heads of width dh --
+    the host checks of the two entry points, which size their LDS differently: one sample's q|k|v image forward, plus the dO rows and
+    two [H, S, S] float32 tables backward, each within 64 KB.  (d = 256, H = 64, S = 8: 49 152 bytes forward, 98 304 backward.)"""
+    if S < 1 or H < 1 or dh < 1 or S > 8 or S * H > 512 or dh > 32 or (3 * H * dh) % 8:
+        return False, False
+    dhp = 16 if dh <= 16 else 32
+    fwd = S * 3 * H * dhp * 2 <= 64 * 1024
+    bwd = (H * dh) % 8 == 0 and S * 4 * H * dhp * 2 + 2 * H * S * S * 4 <= 64 * 1024
+    return fwd, bwd
+
+
+def _attention_ok(enc: nn.TransformerEncoder, S: int, training: bool) -> bool:
+    """Every layer's attention of S tokens can run: the forward kernel, and in training mode the backward one as well (a layer whose
+    backward would be refused inside autograd, one step into training, must never start on the forward kernel)."""
+    key = tuple((layer.self_attn.num_heads, layer.self_attn.embed_dim) for layer in enc.layers) + (S, training)
+    seen = enc.__dict__.setdefault("_ops_attention_ok", {})
+    if key not in seen:
+        both = [attention_support(S, H, d // H) for H, d in key[:-2]]
+        seen[key] = all(fwd and (bwd or not training) for fwd, bwd in both)
+    return seen[key]
+
+
 def encoder_forward(enc: nn.TransformerEncoder, src: torch.Tensor, st: _State) -> torch.Tensor:
     """The fast path proper: src [B, S, d] float32 -> [B, S, d] float32 (training mode, S <= 8)."""
     global _PENDING_LAYER, _PENDING_BWD
@@ -976,7 +999,7 @@ def patch_encoder(enc: nn.TransformerEncoder, seed: int, direct_param_grads: boo
         eval_pass = st0 is not None and not st0.train_mode and not self.training and not torch.is_grad_enabled()    # (set by the model's patched forward)
         fast = ((self.training or eval_pass) and src.is_cuda and src.dim() == 3 and src.shape[1] <= 8 and mask is None and src_key_padding_mask is None
                 and not is_causal and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
-                and src.dtype == torch.float32)
+                and src.dtype == torch.float32 and _attention_ok(self, src.shape[1], self.training))
         if not fast:
             return nn.TransformerEncoder.forward(self, src, mask=mask, src_key_padding_mask=src_key_padding_mask, is_causal=is_causal)
         st = state.get(src.device)
@@ -997,5 +1020,6 @@ def unpatch_encoder(enc: nn.Module) -> None:
     enc.__dict__.pop("_ops_tile_entries", None)
     enc.__dict__.pop("_ops_extra_tiles", None)
     enc.__dict__.pop("_ops_step_counter", None)
+    enc.__dict__.pop("_ops_attention_ok", None)
     for layer in getattr(enc, "layers", []):
         layer.__dict__.pop("_ops_tiles", None)
