@@ -71,6 +71,12 @@ def _check_inputs(fn, x, E, I, fix, wy, Fy=None):
     return dev, B, Ne, x, E, I, fix, wy, Fy
 
 
+def _rows(t, cols):
+    """(pointer, batch stride) of a `_check_inputs` argument as the C ABI takes it: `cols` for one row per beam (x, fix [B,N]; E, wy
+    [B,Ne]), 0 for one row (x, fix [N]) or one element (E, wy) shared by the batch."""
+    return t.data_ptr(), cols if t.dim() == 2 and t.numel() != 1 else 0
+
+
 def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolution] = None, stream_out: bool = False) -> BeamSolution:
     """Solve B straight Euler-Bernoulli beams (Ne elements, N = Ne + 1 nodes) on the GPU.
 
@@ -103,12 +109,7 @@ def beam_solve(x, E, I, fix, Fy, wy, *, tiling: int = 0, out: Optional[BeamSolut
         stream = torch.cuda.current_stream(dev).cuda_stream
         rc = lib.ops_beam_solve_batched_f64(
             B, Ne,
-            x.data_ptr(), N if x.dim() == 2 else 0,
-            E.data_ptr(), Ne if E.numel() != 1 else 0,
-            I.data_ptr(), Ne,
-            fix.data_ptr(), N if fix.dim() == 2 else 0,
-            Fy.data_ptr(), N,
-            wy.data_ptr(), Ne if wy.numel() != 1 else 0,
+            *_rows(x, N), *_rows(E, Ne), I.data_ptr(), Ne, *_rows(fix, N), Fy.data_ptr(), N, *_rows(wy, Ne),
             out.v.data_ptr(), out.theta.data_ptr(), out.V.data_ptr(), out.M.data_ptr(),
             out.status.data_ptr(), int(tiling) | (TILING_STREAM_OUT if stream_out else 0), stream,
         )
@@ -152,11 +153,7 @@ def beam_solve_vjp(x, E, I, fix, wy, v, theta, gv=None, gt=None, gV=None, gM=Non
         stream = torch.cuda.current_stream(dev).cuda_stream
         rc = lib.ops_beam_solve_vjp_f64(
             B, Ne,
-            x.data_ptr(), N if x.dim() == 2 else 0,
-            E.data_ptr(), Ne if E.numel() != 1 else 0,
-            I.data_ptr(), Ne,
-            fix.data_ptr(), N if fix.dim() == 2 else 0,
-            wy.data_ptr(), Ne if wy.numel() != 1 else 0,
+            *_rows(x, N), *_rows(E, Ne), I.data_ptr(), Ne, *_rows(fix, N), *_rows(wy, Ne),
             v.data_ptr(), theta.data_ptr(), ptr(gv), ptr(gt), ptr(gV), ptr(gM),
             gI.data_ptr(), gFy.data_ptr(), gwy.data_ptr(), status.data_ptr(), stream,
         )

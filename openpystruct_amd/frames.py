@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from .sizing_common import GRADIENTS, _ptr, _sizing_step, _StepState, checked_objective, run_epochs  # noqa: F401  (GRADIENTS: public here)
 
 
 @dataclass
@@ -395,29 +396,12 @@ def differentiable_frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Opti
     return torch_op.frame_solve_autograd(topo, I, loads, element_loads)
 
 
-GRADIENTS = ("explicit", "total")
-
-
 def _objective(gradient: str, alpha_sway: float, sway_limit: Optional[float], alpha_deflection: float,
                deflection_limit: Optional[float]) -> tuple:
-    """The checked (gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit) of a frame sizing run (the frame counterpart
-    of `sizing._objective`).  "explicit": the reference's gradient (M and V held fixed), which cannot see a displacement term;
-    "total": the gradient of the loss through the solve.  The limits are penalties, not constraints."""
-    if gradient not in GRADIENTS:
-        raise ValueError(f"gradient must be one of {GRADIENTS}, got {gradient!r}")
-    out = [gradient]
-    for name, alpha, limit in (("sway", alpha_sway, sway_limit), ("deflection", alpha_deflection, deflection_limit)):
-        alpha = float(alpha)
-        if not alpha >= 0.0:
-            raise ValueError(f"alpha_{name} must be >= 0")
-        if alpha > 0.0:
-            if gradient == "explicit":
-                raise ValueError(f'alpha_{name} > 0 needs gradient="total": the {name} term depends on I only through the solve, '
-                                 "the explicit gradient is blind to it")
-            if limit is None or not float(limit) > 0.0:
-                raise ValueError(f"alpha_{name} > 0 needs a {name}_limit > 0")
-        out += [alpha, float(limit) if alpha > 0.0 else 0.0]
-    return tuple(out)
+    """The checked (gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit) of a frame sizing run.  "explicit": the
+    reference's gradient (M and V held fixed), which cannot see a displacement term; "total": the gradient of the loss through the
+    solve.  The limits are penalties, not constraints."""
+    return checked_objective(gradient, (("sway", alpha_sway, sway_limit), ("deflection", alpha_deflection, deflection_limit)))
 
 
 def _sizing_params(cfg: FrameConfig, max_epochs: Optional[int] = None) -> "_cabi.SizingParams":
@@ -448,8 +432,7 @@ def _sizing_grad_launches(topo: FrameTopology, I: torch.Tensor, sol: FrameSoluti
     lib = _cabi.load()
     dev, B = I.device, I.shape[0]
     adj = _adjoint_tables(topo)
-    act = active.data_ptr() if active is not None else None
-    extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
+    act, extra = _ptr(active), _ptr(buf.loss_extra)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         rc = lib.ops_frame_sizing_rhs_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
@@ -488,40 +471,6 @@ def frame_sizing_gradient(topo: FrameTopology, I: torch.Tensor, sol: FrameSoluti
         obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
         _sizing_grad_launches(topo, I, sol, hp, obj, active, buf)
     return buf.grad, buf.loss_extra, buf.adj.status
-
-
-class _StepState(NamedTuple):
-    """The tensors the optimiser step kernels update in place, one row per frame."""
-    I: torch.Tensor              # [B,Ne] float32: the design
-    I64: torch.Tensor            # [B,Ne] float64: the design as the solve reads it
-    exp_avg: torch.Tensor        # [B,Ne] float32 (Adam)
-    exp_avg_sq: torch.Tensor     # [B,Ne] float32
-    best: torch.Tensor           # [B] float32: early stopping
-    patience_cnt: torch.Tensor   # [B] int32
-    epochs: torch.Tensor         # [B] int32
-    active: torch.Tensor         # [B] uint8
-    last: torch.Tensor           # [B] float32: the epoch's total_loss
-    V32: torch.Tensor            # [B,Ne] float32
-    M32: torch.Tensor            # [B,Ne] float32
-
-
-def _sizing_step(st: _StepState, sol: FrameSolution, hp, buf: Optional[_SizingGradBuffers]) -> None:
-    """One optimiser step with the early-stop bookkeeping, on the current stream: on the explicit gradient formed from (V, M) where
-    `buf` is None, else on the gradient (and the loss's displacement terms) that `_sizing_grad_launches` left in `buf`."""
-    lib = _cabi.load()
-    B, Ne = st.I.shape
-    dev = st.I.device
-    design = (B, Ne, st.I.data_ptr(), st.I64.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr())
-    state = tuple(t.data_ptr() for t in st[2:])
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if buf is None:
-            name, rc = "ops_beam_sizing_step_f32", lib.ops_beam_sizing_step_f32(*design, *state, ctypes.byref(hp), stream)
-        else:
-            extra = buf.loss_extra.data_ptr() if buf.loss_extra is not None else None
-            name, rc = "ops_beam_sizing_step_grad_f32", lib.ops_beam_sizing_step_grad_f32(*design, buf.grad.data_ptr(), extra, *state,
-                                                                                          ctypes.byref(hp), None, stream)
-    _cabi.check(rc, name)
 
 
 def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
@@ -569,19 +518,20 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
             return out
     else:
         forward = lambda out: frame_solve(topo, st.I64, loads, out=out)  # noqa: E731
-    buf = None
+    buf = grad = loss_extra = None      # the explicit step forms its gradient from (V, M)
     if gradient == "total":
         buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
         obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
-    for e in range(n_max):
+        grad, loss_extra = buf.grad, buf.loss_extra
+
+    def epoch():
+        nonlocal sol
         sol = forward(sol)
         if buf is not None:
             _sizing_grad_launches(topo, st.I64, sol, hp, obj, st.active, buf)
-        _sizing_step(st, sol, hp, buf)
-        if loss_history is not None:
-            loss_history.append(st.last.clone())
-        if (e + 1) % poll_every == 0 and not bool(st.active.any()):
-            break
+        _sizing_step(st, sol.V, sol.M, hp, grad, loss_extra)
+
+    run_epochs(epoch, n_max, poll_every, st.active, (lambda: loss_history.append(st.last.clone())) if loss_history is not None else None)
     torch.cuda.synchronize(dev)
     return I, sol, st.epochs
 

@@ -16,7 +16,7 @@ from __future__ import annotations
 import torch
 
 from . import _cabi
-from .beam import _check_inputs
+from .beam import _check_inputs, _rows
 
 
 def _f64(t, dev):
@@ -44,9 +44,8 @@ class _FEResidual(torch.autograd.Function):
         rv, rt = torch.empty_like(v), torch.empty_like(theta)
         with torch.cuda.device(dev):                  # the launch goes to I's device, whatever the current one is
             s = torch.cuda.current_stream(dev).cuda_stream
-            rc = lib.ops_beam_residual_f64(B, Ne, x.data_ptr(), N if x.dim() == 2 else 0, E.data_ptr(), Ne if E.numel() != 1 else 0,
-                                           I.data_ptr(), fix.data_ptr(), N if fix.dim() == 2 else 0, Fy.data_ptr(), wy.data_ptr(),
-                                           Ne if wy.numel() != 1 else 0, v.data_ptr(), theta.data_ptr(), rv.data_ptr(), rt.data_ptr(), s)
+            rc = lib.ops_beam_residual_f64(B, Ne, *_rows(x, N), *_rows(E, Ne), I.data_ptr(), *_rows(fix, N), Fy.data_ptr(), *_rows(wy, Ne),
+                                           v.data_ptr(), theta.data_ptr(), rv.data_ptr(), rt.data_ptr(), s)
         _cabi.check(rc, "ops_beam_residual_f64")
         ctx.save_for_backward(I, v, theta, x, E, fix)
         return rv, rt
@@ -63,8 +62,7 @@ class _FEResidual(torch.autograd.Function):
         dv, dt, dI = torch.empty_like(v), torch.empty_like(v), torch.empty_like(I)
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream(dev).cuda_stream
-            rc = lib.ops_beam_residual_vjp_f64(B, Ne, x.data_ptr(), N if x.dim() == 2 else 0, E.data_ptr(), Ne if E.numel() != 1 else 0,
-                                               I.data_ptr(), fix.data_ptr(), N if fix.dim() == 2 else 0, v.data_ptr(), theta.data_ptr(),
+            rc = lib.ops_beam_residual_vjp_f64(B, Ne, *_rows(x, N), *_rows(E, Ne), I.data_ptr(), *_rows(fix, N), v.data_ptr(), theta.data_ptr(),
                                                gv.data_ptr(), gt.data_ptr(), sv.data_ptr(), st_.data_ptr(), dv.data_ptr(), dt.data_ptr(),
                                                dI.data_ptr(), s)
         _cabi.check(rc, "ops_beam_residual_vjp_f64")

@@ -3,15 +3,19 @@
 Mirrors /root/reference/OpenPyStruct_BeamOpt_training_SingleCore.py (and _MultiCore.py):
   * module-level parameters                 :20-49   -> `SizingConfig` (same names, same defaults)
   * case randomisation                      :133-160 -> `make_cases`
-  * per-epoch FE solve                      :176-190 -> `beam_solve`            (HIP kernel, csrc/beam_solve.hip)
-  * loss / backward / Adam / clamp / stop   :195-219 -> `ops_beam_sizing_step_f32` (HIP kernel, csrc/sizing_step.hip)
+  * per-epoch FE solve                      :176-190 \\ `SizingState.epoch`: by default ONE launch per epoch,
+  * loss / backward / Adam / clamp / stop   :195-219 /  `ops_beam_sizing_epoch_f32` (HIP kernels, csrc/beam_solve.hip)
   * record assembly                         :221-249 -> `generate_dataset` / `records_to_reference_json`
 
-All cases of a shard advance one epoch per (solve, step) pair; finished cases are frozen by the step
-kernel (their solver input is no longer refreshed), so no host round trip is needed per epoch.  The host
-only polls `active.any()` every `poll_every` epochs.  Multi-GPU: cases are independent, every rank owns a
-contiguous slice of the globally seeded case list and nothing is exchanged (MultiCore.py:258 does the
-same with processes).
+The epoch takes one of three paths, fixed when the state is built:
+  * fused (the default): solve and optimiser step in one launch, for the explicit gradient up to 128 elements per beam;
+  * separate: `ops_beam_solve_forces_f32` then the step (`sizing_common._sizing_step`), two launches -- larger meshes, or
+    `OPS_AMD_SIZING_FUSED=0`;
+  * total (`gradient="total"`): the float64 `beam_solve`, dL/dI through it (`_beam_sizing_grad_launch`), the gradient-fed step.
+All cases of a shard advance one epoch per call; finished cases are frozen by the step (their solver input is
+no longer refreshed), so no host round trip is needed per epoch.  The host only polls `active.any()` every
+`poll_every` epochs.  Multi-GPU: cases are independent, every rank owns a contiguous slice of the globally
+seeded case list and nothing is exchanged (MultiCore.py:258 does the same with processes).
 """
 from __future__ import annotations
 
@@ -26,7 +30,8 @@ import numpy as np
 import torch
 
 from . import _cabi
-from .beam import BeamSolution, beam_solve
+from .beam import BeamSolution, _check_inputs, _rows, beam_solve
+from .sizing_common import GRADIENTS, _ptr, _sizing_step, _StepState, checked_objective, run_epochs  # noqa: F401  (GRADIENTS: public here)
 
 
 @dataclass
@@ -324,24 +329,23 @@ def sizing_tiling(n_nodes: int, shared_geometry: bool = False) -> int:
     return 16 | TILING_ROWS if shared_geometry else 16
 
 
-GRADIENTS = ("explicit", "total")
-
-
 def _objective(gradient: str, alpha_deflection: float, deflection_limit: Optional[float]) -> tuple:
     """The checked (gradient, alpha_deflection, deflection_limit) of a sizing run.  "explicit": the reference's gradient (M and V
     held fixed), which cannot see a deflection term; "total": the gradient of the loss through the solve."""
-    if gradient not in GRADIENTS:
-        raise ValueError(f"gradient must be one of {GRADIENTS}, got {gradient!r}")
-    alpha_deflection = float(alpha_deflection)
-    if not alpha_deflection >= 0.0:
-        raise ValueError("alpha_deflection must be >= 0")
-    if alpha_deflection > 0.0:
-        if gradient == "explicit":
-            raise ValueError('alpha_deflection > 0 needs gradient="total": the deflection term depends on I only through the solve, '
-                             "the explicit gradient is blind to it")
-        if deflection_limit is None or not float(deflection_limit) > 0.0:
-            raise ValueError("alpha_deflection > 0 needs a deflection_limit > 0")
-    return gradient, alpha_deflection, float(deflection_limit) if alpha_deflection > 0.0 else 0.0
+    return checked_objective(gradient, (("deflection", alpha_deflection, deflection_limit),))
+
+
+def _beam_sizing_grad_launch(x, E, I, fix, wy, sol: BeamSolution, hp, obj, active: Optional[torch.Tensor], grad: torch.Tensor,
+                             loss_extra: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """The one launch of dL/dI on the current stream (csrc/sizing_grad.hip); no checks, no allocation."""
+    B, Ne = I.shape
+    N = Ne + 1
+    with torch.cuda.device(I.device):
+        rc = _cabi.load().ops_beam_sizing_grad_f64(
+            B, Ne, *_rows(x, N), *_rows(E, Ne), I.data_ptr(), Ne, *_rows(fix, N), *_rows(wy, Ne), sol.v.data_ptr(),
+            sol.theta.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), ctypes.byref(hp), ctypes.byref(obj), _ptr(active),
+            grad.data_ptr(), _ptr(loss_extra), status.data_ptr(), torch.cuda.current_stream(I.device).cuda_stream)
+    _cabi.check(rc, "ops_beam_sizing_grad_f64")
 
 
 def beam_sizing_gradient(x, E, I, fix, wy, sol: BeamSolution, hp, alpha_deflection: float = 0.0,
@@ -352,7 +356,6 @@ def beam_sizing_gradient(x, E, I, fix, wy, sol: BeamSolution, hp, alpha_deflecti
     Returns (grad, loss_extra, status): loss_extra [B] is the value of the deflection term (None when alpha_deflection == 0),
     status [B] non-zero for a beam whose factorisation failed (its row is NaN).  Rows of cases with active[b] == 0 are not
     written (`out` supplies the buffers to keep).  Asynchronous on the current stream."""
-    from .beam import _check_inputs
     dev, B, Ne, x, E, I, fix, wy, _ = _check_inputs("beam_sizing_gradient", x, E, I, fix, wy)
     N = Ne + 1
     _, aD, vlim = _objective("total", alpha_deflection, deflection_limit)
@@ -368,19 +371,18 @@ def beam_sizing_gradient(x, E, I, fix, wy, sol: BeamSolution, hp, alpha_deflecti
                torch.empty((B,), dtype=torch.int32, device=dev))
     grad, extra, status = out
     obj = _cabi.SizingObjective(alpha_deflection=aD, deflection_limit=vlim)
-    with torch.cuda.device(dev):
-        rc = _cabi.load().ops_beam_sizing_grad_f64(
-            B, Ne, x.data_ptr(), N if x.dim() == 2 else 0, E.data_ptr(), Ne if E.numel() != 1 else 0, I.data_ptr(), Ne,
-            fix.data_ptr(), N if fix.dim() == 2 else 0, wy.data_ptr(), Ne if wy.numel() != 1 else 0, sol.v.data_ptr(),
-            sol.theta.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), ctypes.byref(hp), ctypes.byref(obj),
-            active.data_ptr() if active is not None else None, grad.data_ptr(), extra.data_ptr() if extra is not None else None,
-            status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _cabi.check(rc, "ops_beam_sizing_grad_f64")
+    _beam_sizing_grad_launch(x, E, I, fix, wy, sol, hp, obj, active, grad, extra, status)
     return grad, extra, status
 
 
+def _shared_rows(cases: Cases) -> Tuple[bool, bool]:
+    """(one geometry, one set of supports) for all cases: each is then stored as one shared row (the kernels' shared-table fast path)."""
+    return (bool((cases.node_positions == cases.node_positions[:1]).all()), bool((cases.fix == cases.fix[:1]).all()))
+
+
 class SizingState:
-    """Device-resident optimiser state of a shard (what the reference keeps per sample in Python objects)."""
+    """Device-resident optimiser state of a shard (what the reference keeps per sample in Python objects).  Which of the three
+    epoch paths (module docstring) it takes, and the tiling of every solve, are fixed when the state is built."""
 
     def __init__(self, cases: Cases, cfg: SizingConfig, device: torch.device, gradient: str = "explicit",
                  alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
@@ -392,42 +394,64 @@ class SizingState:
             raise ValueError(f'gradient="total" serves up to 512 elements per beam (the optimiser step kernel), got {Ne}')
         f64 = dict(dtype=torch.float64, device=device)
         f32 = dict(dtype=torch.float32, device=device)
-        self.B, self.N, self.Ne, self.cfg, self.device = B, N, Ne, cfg, device
-        # one shared row when every case has the same geometry / supports (the kernel's shared-table fast path)
-        shared_geom = bool((cases.node_positions == cases.node_positions[:1]).all())
-        shared_fix = bool((cases.fix == cases.fix[:1]).all())
-        self.x = (cases.node_positions[0] if shared_geom else cases.node_positions).to(**f64).contiguous()
-        self.fix = (cases.fix[0] if shared_fix else cases.fix).to(dtype=torch.uint8, device=device).contiguous()
-        self.Fy = cases.Fy.to(**f64).contiguous()
-        self.E = torch.tensor(cfg.E, **f64)
-        self.wy = torch.tensor(cfg.uniform_udl, **f64)
-        self.I = torch.full((B, Ne), cfg.I_0, **f32)                    # I_tensor, :163
-        # fused epochs keep no widened copy: the kernel records, once per case, the float32 inertias of its last solve
+        i32 = dict(dtype=torch.int32, device=device)
+        self.B, self.N, self.Ne, self.device = B, N, Ne, device
+        shared_geom, shared_fix = _shared_rows(cases)
         self._fused = _FUSED_EPOCH and Ne <= 128 and not self._total
-        self.I_last = torch.full((B, Ne), cfg.I_0, **f32) if self._fused else None
-        self.I64 = None if self._fused else self.I.double()      # separate solve + step launches: the solver's input
-        self.exp_avg = torch.zeros((B, Ne), **f32)
-        self.exp_avg_sq = torch.zeros((B, Ne), **f32)
-        self.best_loss = torch.full((B,), float("inf"), **f32)          # :170
-        self.patience_cnt = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.epochs_run = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.active = torch.ones((B,), dtype=torch.uint8, device=device)
-        self.last_loss = torch.zeros((B,), **f32)
-        self.V32: Optional[torch.Tensor] = None      # set by finalize()
-        self.M32: Optional[torch.Tensor] = None
-        self.sol: Optional[BeamSolution] = None
+        # one tiling for the epochs' solves and finalize's, whatever the shard size: the records do not depend on how many GPUs
+        # share the cases.  The fused kernel is row-staged when geometry and supports are shared.
+        self._solve_tiling = sizing_tiling(N, shared_geometry=self._fused and shared_geom and shared_fix)
+        # the buffers: `_arm` writes the initial state into them, and captured epoch graphs point at them
+        self.x = torch.empty((N,) if shared_geom else (B, N), **f64)
+        self.fix = torch.empty((N,) if shared_fix else (B, N), dtype=torch.uint8, device=device)
+        self.Fy = torch.empty((B, N), **f64)
+        self.E, self.wy = torch.empty((), **f64), torch.empty((), **f64)
+        self.I = torch.empty((B, Ne), **f32)                             # I_tensor, :163
+        # fused epochs keep no widened copy: the kernel records, once per case, the float32 inertias of its last solve
+        self.I_last = torch.empty((B, Ne), **f32) if self._fused else None
+        self.I64 = None if self._fused else torch.empty((B, Ne), **f64)     # separate launches: the solver's input
+        self.exp_avg, self.exp_avg_sq = torch.empty((B, Ne), **f32), torch.empty((B, Ne), **f32)
+        self.best_loss, self.last_loss = torch.empty((B,), **f32), torch.empty((B,), **f32)          # :170
+        self.patience_cnt, self.epochs_run, self._status = torch.empty((B,), **i32), torch.empty((B,), **i32), torch.empty((B,), **i32)
+        self.active = torch.empty((B,), dtype=torch.uint8, device=device)
+        self.sol: Optional[BeamSolution] = None      # V32, M32 (set by `_arm`) and sol: filled by finalize()
+        # what each epoch overwrites before it is read
         self._V = torch.empty((B, Ne), **f32)         # element end forces of the epoch's solve, rounded like :189-190
         self._M = torch.empty((B, Ne), **f32)
         if self._total:      # the exact gradient of this epoch's loss and the value of its deflection term (csrc/sizing_grad.hip)
             self._grad = torch.empty((B, Ne), **f64)
             self._loss_extra = torch.zeros((B,), **f64) if self.objective[1] > 0.0 else None
             self._obj = _cabi.SizingObjective(alpha_deflection=self.objective[1], deflection_limit=self.objective[2])
-            self._grad_status = torch.zeros((B,), dtype=torch.int32, device=device)
-        self._status = torch.zeros((B,), dtype=torch.int32, device=device)
+            self._grad_status = torch.zeros((B,), **i32)
+        if not self._fused:
+            self._step = _StepState(self.I, self.I64, self.exp_avg, self.exp_avg_sq, self.best_loss, self.patience_cnt,
+                                    self.epochs_run, self.active, self.last_loss, None, None)     # aliases; V32 / M32: finalize rounds them
         self._hp = cfg.c_params()
         sched = np.zeros((max(int(cfg.max_e), 1), 2), dtype=np.float32)          # per-epoch step size / bias correction
         _cabi.load().ops_sizing_schedule_f32(ctypes.byref(self._hp), sched.ctypes.data)
         self._schedule = torch.as_tensor(sched, device=device)
+        self._arm(cases, cfg)
+
+    def _arm(self, cases: Cases, cfg: SizingConfig) -> None:
+        """The state before the first epoch of a run on `cases`, written IN PLACE: the one statement of it, for a new state and
+        for a re-armed one."""
+        self.cfg = cfg
+        # E and the line load are device scalars the launches read: c_params() carries neither the load nor (exactly) E
+        self.E.fill_(cfg.E)
+        self.wy.fill_(cfg.uniform_udl)
+        self.x.copy_(cases.node_positions[0] if self.x.dim() == 1 else cases.node_positions)
+        self.fix.copy_(cases.fix[0] if self.fix.dim() == 1 else cases.fix)
+        self.Fy.copy_(cases.Fy)
+        self.I.fill_(cfg.I_0)
+        if self._fused:
+            self.I_last.fill_(cfg.I_0)
+        else:
+            self.I64.fill_(float(np.float32(cfg.I_0)))
+        for t in (self.exp_avg, self.exp_avg_sq, self.patience_cnt, self.epochs_run, self.last_loss, self._status):
+            t.zero_()
+        self.best_loss.fill_(float("inf"))
+        self.active.fill_(1)
+        self.V32 = self.M32 = None
 
     def reset(self, cases: Cases, cfg: SizingConfig, gradient: str = "explicit", alpha_deflection: float = 0.0,
               deflection_limit: Optional[float] = None) -> bool:
@@ -438,90 +462,54 @@ class SizingState:
             return False
         if tuple(cases.Fy.shape) != (self.B, self.N) or bytes(cfg.c_params()) != bytes(self._hp) or int(cfg.max_e) != int(self.cfg.max_e):
             return False
-        shared_geom = bool((cases.node_positions == cases.node_positions[:1]).all())
-        shared_fix = bool((cases.fix == cases.fix[:1]).all())
-        if shared_geom != (self.x.dim() == 1) or shared_fix != (self.fix.dim() == 1):
+        if _shared_rows(cases) != (self.x.dim() == 1, self.fix.dim() == 1):
             return False
-        self.cfg = cfg
-        # E and the line load are device scalars the captured launches read: c_params() carries neither the load nor (exactly) E
-        self.E.fill_(cfg.E)
-        self.wy.fill_(cfg.uniform_udl)
-        self.x.copy_(cases.node_positions[0] if shared_geom else cases.node_positions)
-        self.fix.copy_(cases.fix[0] if shared_fix else cases.fix)
-        self.Fy.copy_(cases.Fy)
-        self.I.fill_(cfg.I_0)
-        if self.I_last is not None:
-            self.I_last.fill_(cfg.I_0)
-        else:
-            self.I64.fill_(float(np.float32(cfg.I_0)))
-        self.exp_avg.zero_(); self.exp_avg_sq.zero_()
-        self.best_loss.fill_(float("inf"))
-        self.patience_cnt.zero_(); self.epochs_run.zero_(); self.active.fill_(1); self.last_loss.zero_(); self._status.zero_()
-        self.V32 = self.M32 = None
+        self._arm(cases, cfg)
         return True
 
     def epoch(self) -> None:
-        """One epoch for every case of the shard: FE solve (:176-190) then optimiser step (:195-219).  Inside the loop
-        the reference reads only eleResponse: the solve writes forces only and skips wavefronts of finished cases."""
-        lib = _cabi.load()
-        N, Ne = self.N, self.Ne
-        if self._fused:
-            # solve + optimiser step in ONE launch: the wavefront that solved a case steps it on the forces it still holds in LDS
-            with torch.cuda.device(self.device):
-                rc = lib.ops_beam_sizing_epoch_f32(
-                    self.B, Ne, self.x.data_ptr(), N if self.x.dim() == 2 else 0, self.E.data_ptr(), 0,
-                    self.fix.data_ptr(), N if self.fix.dim() == 2 else 0, self.Fy.data_ptr(), N, self.wy.data_ptr(), 0,
-                    self.I.data_ptr(), self.I_last.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                    self.best_loss.data_ptr(), self.patience_cnt.data_ptr(), self.epochs_run.data_ptr(), self.active.data_ptr(),
-                    self.last_loss.data_ptr(), ctypes.byref(self._hp), self._schedule.data_ptr(), self._status.data_ptr(), self._tiling(),
-                    torch.cuda.current_stream(self.device).cuda_stream)
-            _cabi.check(rc, "ops_beam_sizing_epoch_f32")
-            return
-        if self._total:
-            # three launches: the float64 solve on I64, dL/dI through it (explicit part + adjoint solve), the gradient-fed step
-            self.sol = beam_solve(self.x, self.E, self.I64, self.fix, self.Fy, self.wy, tiling=sizing_tiling(N), out=self.sol)
-            with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                extra = self._loss_extra.data_ptr() if self._loss_extra is not None else None
-                rc = lib.ops_beam_sizing_grad_f64(
-                    self.B, Ne, self.x.data_ptr(), N if self.x.dim() == 2 else 0, self.E.data_ptr(), 0, self.I64.data_ptr(), Ne,
-                    self.fix.data_ptr(), N if self.fix.dim() == 2 else 0, self.wy.data_ptr(), 0, self.sol.v.data_ptr(),
-                    self.sol.theta.data_ptr(), self.sol.V.data_ptr(), self.sol.M.data_ptr(), ctypes.byref(self._hp),
-                    ctypes.byref(self._obj), self.active.data_ptr(), self._grad.data_ptr(), extra, self._grad_status.data_ptr(), stream)
-                _cabi.check(rc, "ops_beam_sizing_grad_f64")
-                rc = lib.ops_beam_sizing_step_grad_f32(
-                    self.B, Ne, self.I.data_ptr(), self.I64.data_ptr(), self.sol.V.data_ptr(), self.sol.M.data_ptr(),
-                    self._grad.data_ptr(), extra, self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.best_loss.data_ptr(),
-                    self.patience_cnt.data_ptr(), self.epochs_run.data_ptr(), self.active.data_ptr(), self.last_loss.data_ptr(),
-                    None, None, ctypes.byref(self._hp), self._schedule.data_ptr(), stream)
-            _cabi.check(rc, "ops_beam_sizing_step_grad_f32")
-            return
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = lib.ops_beam_solve_forces_f32(
-                self.B, Ne, self.x.data_ptr(), N if self.x.dim() == 2 else 0, self.E.data_ptr(), 0, self.I64.data_ptr(), Ne,
-                self.fix.data_ptr(), N if self.fix.dim() == 2 else 0, self.Fy.data_ptr(), N, self.wy.data_ptr(), 0,
-                self._V.data_ptr(), self._M.data_ptr(), self._status.data_ptr(), self.active.data_ptr(), sizing_tiling(N), stream)   # float32 forces: beam_solve.hip only
-            _cabi.check(rc, "ops_beam_solve_forces_f32")
-            rc = lib.ops_beam_sizing_step_vm32_f32(
-                self.B, Ne, self.I.data_ptr(), self.I64.data_ptr(), self._V.data_ptr(), self._M.data_ptr(),
-                self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.best_loss.data_ptr(),
-                self.patience_cnt.data_ptr(), self.epochs_run.data_ptr(), self.active.data_ptr(),
-                self.last_loss.data_ptr(), ctypes.byref(self._hp), self._schedule.data_ptr(), stream)
-        _cabi.check(rc, "ops_beam_sizing_step_vm32_f32")
+        """One epoch for every case of the shard: FE solve (:176-190) then optimiser step (:195-219)."""
+        (self._epoch_fused if self._fused else self._epoch_total if self._total else self._epoch_separate)()
 
-    def _tiling(self) -> int:
-        return sizing_tiling(self.N, shared_geometry=self.x.dim() == 1 and self.fix.dim() == 1)
+    def _epoch_fused(self) -> None:
+        """Solve + optimiser step in ONE launch: the wavefront that solved a case steps it on the forces it still holds in LDS."""
+        N, Ne = self.N, self.Ne
+        with torch.cuda.device(self.device):
+            rc = _cabi.load().ops_beam_sizing_epoch_f32(
+                self.B, Ne, *_rows(self.x, N), *_rows(self.E, Ne), *_rows(self.fix, N), self.Fy.data_ptr(), N, *_rows(self.wy, Ne),
+                *(t.data_ptr() for t in (self.I, self.I_last, self.exp_avg, self.exp_avg_sq, self.best_loss, self.patience_cnt,
+                                         self.epochs_run, self.active, self.last_loss)),
+                ctypes.byref(self._hp), self._schedule.data_ptr(), self._status.data_ptr(), self._solve_tiling,
+                torch.cuda.current_stream(self.device).cuda_stream)
+        _cabi.check(rc, "ops_beam_sizing_epoch_f32")
+
+    def _epoch_total(self) -> None:
+        """Three launches: the float64 solve on I64, dL/dI through it (explicit part + adjoint solve), the gradient-fed step."""
+        self.sol = beam_solve(self.x, self.E, self.I64, self.fix, self.Fy, self.wy, tiling=self._solve_tiling, out=self.sol)
+        _beam_sizing_grad_launch(self.x, self.E, self.I64, self.fix, self.wy, self.sol, self._hp, self._obj, self.active,
+                                 self._grad, self._loss_extra, self._grad_status)
+        _sizing_step(self._step, self.sol.V, self.sol.M, self._hp, self._grad, self._loss_extra, self._schedule)
+
+    def _epoch_separate(self) -> None:
+        """Two launches.  Inside the loop the reference reads only eleResponse: the solve writes forces only (float32:
+        beam_solve.hip only) and skips wavefronts of finished cases; the step reads those rows."""
+        N, Ne = self.N, self.Ne
+        with torch.cuda.device(self.device):
+            rc = _cabi.load().ops_beam_solve_forces_f32(
+                self.B, Ne, *_rows(self.x, N), *_rows(self.E, Ne), self.I64.data_ptr(), Ne, *_rows(self.fix, N), self.Fy.data_ptr(), N,
+                *_rows(self.wy, Ne), self._V.data_ptr(), self._M.data_ptr(), self._status.data_ptr(), self.active.data_ptr(),
+                self._solve_tiling, torch.cuda.current_stream(self.device).cuda_stream)
+        _cabi.check(rc, "ops_beam_solve_forces_f32")
+        _sizing_step(self._step, self._V, self._M, self._hp, schedule=self._schedule)
 
     def finalize(self) -> None:
         """What the reference reads after the loop (:224-232) and records (:239-249): the state of every case's LAST
-        solve.  `I64` (separate launches) froze when a case stopped / `I_last` (fused epochs) recorded its inertias, so one full solve reproduces it -- displacements included -- and the
-        float32 roundings of shear / moment (:189-190) are taken from it."""
-        # same tiling as the epochs, whatever the shard size: the records do not depend on how many GPUs share the cases
+        solve.  `I64` (separate launches) froze when a case stopped / `I_last` (fused epochs) recorded its inertias, so one full
+        solve -- with the epochs' tiling -- reproduces it, displacements included, and the float32 roundings of shear / moment
+        (:189-190) are taken from it."""
         if self._fused:
             self.I64 = self.I_last.double()
-        self.sol = beam_solve(self.x, self.E, self.I64, self.fix, self.Fy, self.wy, tiling=self._tiling() if self._fused else sizing_tiling(self.N),
-                              out=self.sol)
+        self.sol = beam_solve(self.x, self.E, self.I64, self.fix, self.Fy, self.wy, tiling=self._solve_tiling, out=self.sol)
         self.V32, self.M32 = self.sol.V.float(), self.sol.M.float()
 
 
@@ -589,15 +577,7 @@ def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25
             k += 1
     else:
         hist = []
-        while epochs_done < cfg.max_e:
-            st.epoch()
-            epochs_done += 1
-            if record_loss:
-                hist.append(st.last_loss.clone())
-            if epochs_done % poll_every:
-                continue
-            if not bool(st.active.any()):       # host sync once per `poll_every` epochs
-                break
+        run_epochs(st.epoch, cfg.max_e, poll_every, st.active, (lambda: hist.append(st.last_loss.clone())) if record_loss else None)
         if record_loss:
             st.loss_history = torch.stack(hist) if hist else torch.zeros((0, st.B), dtype=torch.float32, device=device)
     # a case that is still active here ran out of max_e inside the step kernel already (it clears `active`)

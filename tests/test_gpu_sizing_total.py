@@ -418,6 +418,25 @@ def test_explicit_mode_is_untouched_by_a_total_run_in_the_same_process(lib):
         sizing.optimize_cases(cases, cfg, DEV, gradient="total", alpha_deflection=100.0)
 
 
+def test_reuse_rearms_the_two_launch_epoch_like_a_fresh_state(lib, monkeypatch):
+    """The separate path (solve, then step: OPS_AMD_SIZING_FUSED=0) under reuse=True: the second shard runs on the first one's
+    re-armed state and captured graph, and the two shards carry the bits of one fresh run of all four cases."""
+    from openpystruct_amd import sizing
+    monkeypatch.setattr(sizing, "_FUSED_EPOCH", False)
+    monkeypatch.setattr(sizing, "_EPOCH_GRAPHS", {})           # (this test's state is not left behind for a later one to re-arm)
+    cfg = sizing.SizingConfig(num_nodes=41, roller_nodes=(10, 30), max_e=6)
+    cases = sizing.make_cases(4, cfg, seed=41)
+    fresh = _snapshot(sizing.optimize_cases(cases, cfg, DEV, poll_every=2))
+    assert (fresh["status"] == 0).all() and (fresh["epochs_run"] == 6).all()
+    states, halves = [], []
+    for lo in (0, 2):
+        states.append(sizing.optimize_cases(cases.slice(lo, lo + 2), cfg, DEV, poll_every=2, reuse=True))
+        halves.append(_snapshot(states[-1]))
+    assert states[1] is states[0] and not states[0]._fused and states[0].objective == ("explicit", 0.0, 0.0)
+    for k, a in fresh.items():
+        assert _same_bits(np.concatenate([h[k] for h in halves]), a), k
+
+
 def test_generate_dataset_in_total_mode_returns_the_record_schema(lib):
     from openpystruct_amd import sizing
     rec = sizing.generate_dataset(8, device=DEV, gradient="total")

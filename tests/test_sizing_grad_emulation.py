@@ -237,6 +237,22 @@ def test_objective_arguments_are_checked_on_the_host():
     for bad in (("explicit", 1.0, 0.01), ("total", 1.0, None), ("total", 1.0, 0.0), ("total", -1.0, 0.01), ("adjoint", 0.0, None)):
         with pytest.raises(ValueError):
             sizing._objective(*bad)
-    cases = types.SimpleNamespace(Fy=torch.zeros((2, 600)))
+    # the frame loop's two terms go through the same check (sizing_common.checked_objective)
+    from openpystruct_amd import frames
+    assert frames._objective("explicit", 0.0, None, 0.0, None) == ("explicit", 0.0, 0.0, 0.0, 0.0)
+    assert frames._objective("total", 50.0, 0.02, 100.0, 0.01) == ("total", 50.0, 0.02, 100.0, 0.01)
+    assert frames._objective("total", 0.0, 0.02, 100.0, 0.01) == ("total", 0.0, 0.0, 100.0, 0.01)      # an absent term stores no limit
+    for bad in (("explicit", 1.0, 0.02, 0.0, None), ("total", 1.0, None, 0.0, None), ("total", 1.0, 0.0, 0.0, None),
+                ("total", -1.0, 0.02, 0.0, None), ("adjoint", 0.0, None, 0.0, None), ("total", 0.0, None, 1.0, None)):
+        with pytest.raises(ValueError):
+            frames._objective(*bad)
+    with pytest.raises(ValueError, match=r'alpha_sway > 0 needs gradient="total"'):
+        frames._objective("explicit", 1.0, 0.02, 0.0, None)
+    with pytest.raises(ValueError, match="alpha_sway > 0 needs a sway_limit > 0"):
+        frames._objective("total", 1.0, None, 0.0, None)
+    with pytest.raises(ValueError, match="alpha_sway must be >= 0"):
+        frames._objective("total", float("nan"), 0.02, 0.0, None)
+    assert sizing.GRADIENTS is frames.GRADIENTS
+    cases =types.SimpleNamespace(Fy=torch.zeros((2, 600)))
     with pytest.raises(ValueError, match="512"):
         sizing.SizingState(cases, sizing.SizingConfig(num_nodes=600), torch.device("cpu"), gradient="total")
