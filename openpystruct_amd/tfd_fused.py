@@ -18,7 +18,7 @@ other activations, CPU: the framework's own forward.
 from __future__ import annotations
 
 import ctypes
-import os
+import functools
 import types
 from typing import Optional
 
@@ -43,7 +43,8 @@ LAYER_BWD = switches.get("tfd_layer_bwd") == "1"       # A/B switch: 0 = eight l
 
 
 class _State:
-    """The dropout stream of one encoder (its call counter must outlive a captured HIP graph) and how parameter gradients leave."""
+    """One patched encoder's state on one device: its dropout stream (the call counter must outlive a captured HIP graph), how parameter
+    gradients leave, and every hand-off between calls that belong to ONE pass or step of this model -- nothing of it is process-global."""
 
     def __init__(self, device, seed: int, direct_param_grads: bool = False, counter: Optional[torch.Tensor] = None):
         self.device = device
@@ -61,6 +62,16 @@ class _State:
         self.train_mode = True   # False: an evaluation pass through the one-launch kernels (every dropout probability 0)
         self.keep_draws = False  # tests: keep the front end's draws (t [B, Nc], eps [B, Nc, d]) of the last pass in `draws`
         self.draws = None
+        self.pending_layer = None   # (argument block, output, tensors to keep alive) of a layer whose forward launch waits for its successor
+        self.pending_bwd = None     # (argument block, dx32, tensors to keep alive) of a later layer whose backward launch waits for its predecessor
+        self.loss_spec = None       # (targets, criterion, alpha0, running sum): armed by the training step for ITS next forward pass (arm_head_loss)
+        self.taken_loss = None      # the loss that pass computed on the head's tile, until take_head_loss fetches it
+        self.gather = None          # dict(src, targets, order, cursor, idx_out, sigma, seed): armed for a whole run (arm_gather)
+        self.gathered = False       # the front end assembled the current pass's batch itself: the head reads its targets by the gathered rows
+
+    def site_seed(self, site: int) -> int:
+        """The seed of dropout / noise site `site` (layer li: 4 li .. 4 li + 3; front end: 100, 101; head: 102, 103)."""
+        return self.seed + 7919 * site
 
     def advance(self) -> None:
         if not self.external or not self.train_mode:        # (an evaluation pass has no batch-assembly launch in front of it)
@@ -80,13 +91,81 @@ class _State:
             self._zeros16[key] = torch.zeros(key, dtype=torch.bfloat16, device=self.device)
         return self._zeros16[key]
 
-    def used(self, site: int) -> torch.Tensor:
+    def used(self) -> torch.Tensor:
         """Where a forward launch leaves the counter value it drew its mask from (one per call: its backward reads it)."""
         return torch.empty(1, dtype=torch.int64, device=self.device)
 
 
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _bf16(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """An incoming gradient as a contiguous bfloat16 tensor (None: an unused output's, passed on)."""
+    if g is None:
+        return None
+    g = g.contiguous()
+    return g if g.dtype == torch.bfloat16 else g.to(torch.bfloat16)
+
+
+def _f32(g: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    return None if g is None else g.contiguous().float()
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _grads_are_flat_views(*params) -> bool:
+    """Every parameter's `.grad` is a float32 contiguous view (of the training loop's zeroed flat buffer): a launch may add into it."""
+    return all(t.grad is not None and t.grad.dtype == torch.float32 and t.grad.is_contiguous() for t in params)
+
+
+def _shadow_recs(mods, names=None):
+    """The shadow records (train.ShadowRec) of the modules' products `names` (default: each one's `_ops_prod`), every one with a bias --
+    or None when a product is not registered."""
+    recs = [getattr(getattr(m, n, None), "rec", None) for m, n in zip(mods, names or ("_ops_prod",) * len(mods))]
+    return recs if all(r is not None and r.b_sh is not None for r in recs) else None
+
+
+def _bf16_autocast() -> bool:
+    return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+
+
+# The three row-wise backward launches of csrc/seq_block.hip.  `drop` = (p, seed, used): the forward launch's dropout probability, its
+# site's seed and the counter value it left.  Called by the Functions below and by EncoderLayerFn.backward's eight-launch branch.
+
+def _attention_bwd(qkv, g, Bn, S, H, dh, drop):
+    """dqkv [Bn S, 3 H dh] bf16 from the context gradient g [Bn S, H dh] bf16."""
+    p, seed, used = drop
+    dqkv = torch.empty_like(qkv)
+    with torch.cuda.device(qkv.device):
+        _cabi.check(_cabi.load().ops_seq_attention_bwd(Bn, S, H, dh, qkv.data_ptr(), g.data_ptr(), dqkv.data_ptr(), p, seed, used.data_ptr(),
+                                                       _stream(qkv.device)), "ops_seq_attention_bwd")
+    return dqkv
+
+
+def _dropout_add_layernorm_bwd(g32, g16, z, mean, rstd, gamma, drop, dgamma, dbeta):
+    """(dx bf16, dres float32) from the gradients of the two outputs (either may be None); the launch ADDS into dgamma / dbeta (float atomics)."""
+    p, seed, used = drop
+    T, d = z.shape
+    dx = torch.empty((T, d), dtype=torch.bfloat16, device=z.device)
+    dres = torch.empty((T, d), dtype=torch.float32, device=z.device)
+    with torch.cuda.device(z.device):
+        _cabi.check(_cabi.load().ops_dropout_add_layernorm_bwd(T, d, _ptr(g32), _ptr(g16), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                                               gamma.data_ptr(), p, seed, used.data_ptr(), dx.data_ptr(), dres.data_ptr(),
+                                                               dgamma.data_ptr(), dbeta.data_ptr(), _stream(z.device)),
+                    "ops_dropout_add_layernorm_bwd")
+    return dx, dres
+
+
+def _act_dropout_bwd(x, g, slope, drop):
+    p, seed, used = drop
+    dx = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _cabi.check(_cabi.load().ops_act_dropout_bwd(x.numel(), x.data_ptr(), g.data_ptr(), dx.data_ptr(), slope, p, seed, used.data_ptr(),
+                                                     _stream(x.device)), "ops_act_dropout_bwd")
+    return dx
 
 
 class SeqAttention(torch.autograd.Function):
@@ -98,27 +177,19 @@ class SeqAttention(torch.autograd.Function):
         qkv = qkv.contiguous()
         d = qkv.shape[1] // 3
         out = torch.empty((Bn * S, d), dtype=torch.bfloat16, device=qkv.device)
-        used = st.used(site)
+        used = st.used()
         with torch.cuda.device(qkv.device):
-            _cabi.check(lib.ops_seq_attention_fwd(Bn, S, H, d // H, qkv.data_ptr(), out.data_ptr(), float(p), st.seed + 7919 * site,
+            _cabi.check(lib.ops_seq_attention_fwd(Bn, S, H, d // H, qkv.data_ptr(), out.data_ptr(), float(p), st.site_seed(site),
                                                    st.counter.data_ptr(), used.data_ptr(), _stream(qkv.device)), "ops_seq_attention_fwd")
         ctx.save_for_backward(qkv)
-        ctx.cfg = (Bn, S, H, d, float(p), st.seed + 7919 * site, used)
+        ctx.cfg = (Bn, S, H, d, (float(p), st.site_seed(site), used))
         return out
 
     @staticmethod
     def backward(ctx, g):
-        lib = _cabi.load()
         (qkv,) = ctx.saved_tensors
-        Bn, S, H, d, p, seed, used = ctx.cfg
-        g = g.contiguous()
-        if g.dtype != torch.bfloat16:
-            g = g.to(torch.bfloat16)
-        dqkv = torch.empty_like(qkv)
-        with torch.cuda.device(qkv.device):
-            _cabi.check(lib.ops_seq_attention_bwd(Bn, S, H, d // H, qkv.data_ptr(), g.data_ptr(), dqkv.data_ptr(), p, seed, used.data_ptr(),
-                                                   _stream(qkv.device)), "ops_seq_attention_bwd")
-        return dqkv, None, None, None, None, None, None
+        Bn, S, H, d, drop = ctx.cfg
+        return _attention_bwd(qkv, _bf16(g), Bn, S, H, d // H, drop), None, None, None, None, None, None
 
 
 class DropoutAddLayerNorm(torch.autograd.Function):
@@ -136,42 +207,28 @@ class DropoutAddLayerNorm(torch.autograd.Function):
         z = torch.empty((T, d), dtype=torch.float32, device=dev)
         mean = torch.empty(T, dtype=torch.float32, device=dev)
         rstd = torch.empty(T, dtype=torch.float32, device=dev)
-        used = st.used(site)
+        used = st.used()
         with torch.cuda.device(dev):
             _cabi.check(lib.ops_dropout_add_layernorm_fwd(T, d, x.data_ptr(), res.data_ptr(), int(res.dtype == torch.bfloat16), gamma.data_ptr(),
-                                                           beta.data_ptr(), float(eps), float(p), st.seed + 7919 * site, st.counter.data_ptr(),
+                                                           beta.data_ptr(), float(eps), float(p), st.site_seed(site), st.counter.data_ptr(),
                                                            used.data_ptr(), y32.data_ptr(), y16.data_ptr(), z.data_ptr(), mean.data_ptr(),
                                                            rstd.data_ptr(), _stream(dev)), "ops_dropout_add_layernorm_fwd")
         ctx.save_for_backward(z, mean, rstd, gamma, beta)
-        ctx.cfg = (float(p), st.seed + 7919 * site, used, st, site, res.dtype)
+        ctx.cfg = ((float(p), st.site_seed(site), used), st, res.dtype)
         ctx.set_materialize_grads(False)        # an unused output's gradient arrives as None, not as a freshly filled zero tensor (one node each)
         return y32, y16
 
     @staticmethod
     def backward(ctx, g32, g16):
-        lib = _cabi.load()
         z, mean, rstd, gamma, beta = ctx.saved_tensors
-        p, seed, used, st, site, res_dtype = ctx.cfg
-        T, d = z.shape
-        dev = z.device
+        drop, st, res_dtype = ctx.cfg
         if g32 is None and g16 is None:
             return None, None, None, None, None, None, None, None
-        if g32 is not None:
-            g32 = g32.contiguous()
-        if g16 is not None:
-            g16 = g16.contiguous()
-            if g16.dtype != torch.bfloat16:
-                g16 = g16.to(torch.bfloat16)
-        dx = torch.empty((T, d), dtype=torch.bfloat16, device=dev)
-        dres = torch.empty((T, d), dtype=torch.float32, device=dev)
-        direct = st.direct and all(t.grad is not None and t.grad.dtype == torch.float32 and t.grad.is_contiguous() for t in (gamma, beta))
+        g32, g16 = (None if g32 is None else g32.contiguous()), _bf16(g16)
+        direct = st.direct and _grads_are_flat_views(gamma, beta)
         dg = gamma.grad if direct else torch.zeros_like(gamma)        # the launch ADDS (float atomics)
         db = beta.grad if direct else torch.zeros_like(beta)
-        with torch.cuda.device(dev):
-            _cabi.check(lib.ops_dropout_add_layernorm_bwd(T, d, g32.data_ptr() if g32 is not None else None, g16.data_ptr() if g16 is not None else None,
-                                                           z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), p, seed, used.data_ptr(),
-                                                           dx.data_ptr(), dres.data_ptr(), dg.data_ptr(), db.data_ptr(), _stream(dev)),
-                         "ops_dropout_add_layernorm_bwd")
+        dx, dres = _dropout_add_layernorm_bwd(g32, g16, z, mean, rstd, gamma, drop, dg, db)
         if res_dtype != torch.float32:
             dres = dres.to(res_dtype)
         return dx, dres, None if direct else dg, None if direct else db, None, None, None, None
@@ -185,42 +242,31 @@ class ActDropout(torch.autograd.Function):
         lib = _cabi.load()
         x = x.contiguous()
         y = torch.empty_like(x)
-        used = st.used(site)
+        used = st.used()
         with torch.cuda.device(x.device):
-            _cabi.check(lib.ops_act_dropout_fwd(x.numel(), x.data_ptr(), y.data_ptr(), float(slope), float(p), st.seed + 7919 * site,
+            _cabi.check(lib.ops_act_dropout_fwd(x.numel(), x.data_ptr(), y.data_ptr(), float(slope), float(p), st.site_seed(site),
                                                  st.counter.data_ptr(), used.data_ptr(), _stream(x.device)), "ops_act_dropout_fwd")
         ctx.save_for_backward(x)
-        ctx.cfg = (float(slope), float(p), st.seed + 7919 * site, used)
+        ctx.cfg = (float(slope), (float(p), st.site_seed(site), used))
         return y
 
     @staticmethod
     def backward(ctx, g):
-        lib = _cabi.load()
         (x,) = ctx.saved_tensors
-        slope, p, seed, used = ctx.cfg
-        g = g.contiguous()
-        if g.dtype != torch.bfloat16:
-            g = g.to(torch.bfloat16)
-        dx = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            _cabi.check(lib.ops_act_dropout_bwd(x.numel(), x.data_ptr(), g.data_ptr(), dx.data_ptr(), slope, p, seed, used.data_ptr(),
-                                                 _stream(x.device)), "ops_act_dropout_bwd")
-        return dx, None, None, None, None
+        slope, drop = ctx.cfg
+        return _act_dropout_bwd(x, _bf16(g), slope, drop), None, None, None, None
 
 
 LAYER_PAIR_FWD = switches.get("tfd_layer_pair") == "1"      # A/B switch: two consecutive layers' forward passes as one launch
-_PENDING_LAYER = None       # (argument block, output, tensors to keep alive) of a layer whose forward launch waits for its successor
 LAYER_PAIR_BWD = switches.get("tfd_layer_pair_bwd") == "1"  # ... and their backward passes
-_PENDING_BWD = None         # (argument block, dx32, tensors to keep alive) of a later layer whose backward launch waits for its predecessor
 
 
-def flush_pending_backward() -> None:
-    """Launch a deferred backward pass whose predecessor never came (a first layer whose inputs need no gradient).  Called by the training
-    loop's weight-gradient flush, i.e. behind every backward pass."""
-    global _PENDING_BWD
-    if _PENDING_BWD is not None:
-        pb, pdx, keep = _PENDING_BWD
-        _PENDING_BWD = None
+def _launch_pending_bwd(st: _State) -> None:
+    """Launch a deferred backward pass whose predecessor never came (a first layer whose inputs need no gradient).  Handed to the step
+    that collects the weight gradients (train.run_before_wgrad_flush), which runs it in front of its grouped launches."""
+    if st.pending_bwd is not None:
+        pb, pdx, _keep = st.pending_bwd
+        st.pending_bwd = None
         with torch.cuda.device(pdx.device):
             _cabi.check(_cabi.load().ops_tfd_encoder_layer_bwd(ctypes.byref(pb), _stream(pdx.device)), "ops_tfd_encoder_layer_bwd")
 
@@ -237,7 +283,6 @@ class EncoderLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x32, x16, layer, Bn, S, st: _State, li: int, defer: bool = False):
-        global _PENDING_LAYER
         lib = _cabi.load()
         mha = layer.self_attn
         H, d = mha.num_heads, mha.embed_dim
@@ -253,8 +298,8 @@ class EncoderLayerFn(torch.autograd.Function):
         u, h = torch.empty((T, ff), **bf), torch.empty((T, ff), **bf)
         z2, mean2, rstd2 = torch.empty((T, d), **f32), torch.empty(T, **f32), torch.empty(T, **f32)
         y32, y16 = torch.empty((T, d), **f32), torch.empty((T, d), **bf)
-        used = st.used(4 * li)
-        seeds = [st.seed + 7919 * (4 * li + k) for k in range(4)]
+        used = st.used()
+        seeds = [st.site_seed(4 * li + k) for k in range(4)]
         ps = (float(mha.dropout), float(layer.dropout1.p), float(layer.dropout.p), float(layer.dropout2.p)) if st.train_mode else (0.0, 0.0, 0.0, 0.0)
         a = _cabi.TfdLayerArgs(identity_act=int(IDENTITY_ACT), 
             Bn=Bn, S=S, H=H, dh=dh, d=d, ff=ff, x32=x32.data_ptr(),
@@ -269,20 +314,20 @@ class EncoderLayerFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             ctx.pair_later = False               # this layer is the LATER one of a pair launch (its backward may wait for its predecessor's)
             if defer:                            # the next layer's call launches both (ops_tfd_encoder_layer_pair_fwd)
-                assert _PENDING_LAYER is None
+                assert st.pending_layer is None
                 # (everything the deferred launch writes stays alive until it is launched: in a no-grad pass nothing else holds these
                 #  tensors, and the caching allocator would hand their memory to the next layer's buffers -- whose launch is this same one)
-                _PENDING_LAYER = (a, y32, (x32, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2, y16))
-            elif _PENDING_LAYER is not None:
-                pa, py, _keep = _PENDING_LAYER
-                _PENDING_LAYER = None
+                st.pending_layer = (a, y32, (x32, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2, y16))
+            elif st.pending_layer is not None:
+                pa, py, _keep = st.pending_layer
+                st.pending_layer = None
                 assert py.data_ptr() == x32.data_ptr()
                 _cabi.check(lib.ops_tfd_encoder_layer_pair_fwd(ctypes.byref(pa), ctypes.byref(a), _stream(dev)), "ops_tfd_encoder_layer_pair_fwd")
                 ctx.pair_later = True
             else:
                 _cabi.check(lib.ops_tfd_encoder_layer_fwd(ctypes.byref(a), _stream(dev)), "ops_tfd_encoder_layer_fwd")
         ctx.save_for_backward(x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2)
-        ctx.cfg = (layer, Bn, S, H, dh, d, ff, ps, seeds, used, (rin, rout, r1, r2))
+        ctx.cfg = (layer, Bn, S, H, dh, d, ff, ps, seeds, used, (rin, rout, r1, r2), st)
         ctx.set_materialize_grads(False)
         return y32, y16
 
@@ -293,11 +338,10 @@ class EncoderLayerFn(torch.autograd.Function):
         from . import train
         lib = _cabi.load()
         x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2 = ctx.saved_tensors
-        layer, Bn, S, H, dh, d, ff, ps, seeds, used, (rin, rout, r1, r2) = ctx.cfg
+        layer, Bn, S, H, dh, d, ff, ps, seeds, used, (rin, rout, r1, r2), st = ctx.cfg
         T = Bn * S
         dev = z1.device
         bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
         if g32 is not None:
             g32 = g32.contiguous()
         if g16 is not None:
@@ -310,7 +354,7 @@ class EncoderLayerFn(torch.autograd.Function):
                 d_f, d_u, d_a, dqkv = torch.empty((T, d), **bf), torch.empty((T, ff), **bf), torch.empty((T, d), **bf), torch.empty((T, 3 * d), **bf)
                 dx32 = torch.empty((T, d), **f32)
                 a = _cabi.TfdLayerBwdArgs(identity_act=int(IDENTITY_ACT), 
-                    Bn=Bn, S=S, H=H, dh=dh, d=d, ff=ff, g32=ptr(g32), g16=ptr(g16),
+                    Bn=Bn, S=S, H=H, dh=dh, d=d, ff=ff, g32=_ptr(g32), g16=_ptr(g16),
                     Wt_in=tiles["in"][1].data_ptr(), Wt_out=tiles["out"][1].data_ptr(), Wt_1=tiles["l1"][1].data_ptr(), Wt_2=tiles["l2"][1].data_ptr(),
                     gamma1=layer.norm1.weight.data_ptr(), gamma2=layer.norm2.weight.data_ptr(),
                     p_attn=ps[0], p_1=ps[1], p_act=ps[2], p_2=ps[3], seed_attn=seeds[0], seed_1=seeds[1], seed_act=seeds[2], seed_2=seeds[3],
@@ -328,10 +372,10 @@ class EncoderLayerFn(torch.autograd.Function):
                     tr = torch.zeros(16 * ((Bn + (16 // S) - 1) // (16 // S)), dtype=torch.int64, device=dev)
                     _TRACE_BWD.append(tr)
                     a.trace = tr.data_ptr()
-                global _PENDING_BWD
-                if _PENDING_BWD is not None:
-                    pb, pdx, keep = _PENDING_BWD
-                    _PENDING_BWD = None
+                if st.pending_bwd is not None:
+                    pb, pdx, _keep = st.pending_bwd
+                    st.pending_bwd = None
+                    train.run_before_wgrad_flush(None)
                     if g32 is not None and g16 is None and pdx.data_ptr() == g32.data_ptr() and _TRACE_BWD is None:
                         _cabi.check(lib.ops_tfd_encoder_layer_pair_bwd(ctypes.byref(pb), ctypes.byref(a), s), "ops_tfd_encoder_layer_pair_bwd")
                     else:                        # (not the successor's gradient after all: the two launches)
@@ -344,7 +388,8 @@ class EncoderLayerFn(torch.autograd.Function):
                     #  dqkv before the waiting launch has written them)
                     # the predecessor's backward call -- the next node autograd runs: this layer's inputs are its two outputs -- launches both
                     # (the saved tensors too: autograd releases them when this call returns, before the launch that reads them)
-                    _PENDING_BWD = (a, dx32, (g32, g16, d_f, d_u, d_a, dqkv, part, x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2))
+                    st.pending_bwd = (a, dx32, (g32, g16, d_f, d_u, d_a, dqkv, part, x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2))
+                    train.run_before_wgrad_flush(functools.partial(_launch_pending_bwd, st))     # ... or, if it never comes, the step's flush
                 else:
                     _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
                 if part is not None:
@@ -358,26 +403,15 @@ class EncoderLayerFn(torch.autograd.Function):
                 train.shadow_param_grads(rin, dqkv, x16)
                 return dx32, None, None, None, None, None, None, None
             # LayerNorm2 <- (g32, g16)
-            d_f, dres2 = torch.empty((T, d), **bf), torch.empty((T, d), **f32)
-            _cabi.check(lib.ops_dropout_add_layernorm_bwd(T, d, ptr(g32), ptr(g16), z2.data_ptr(), mean2.data_ptr(), rstd2.data_ptr(),
-                                                           layer.norm2.weight.data_ptr(), ps[3], seeds[3], used.data_ptr(), d_f.data_ptr(), dres2.data_ptr(),
-                                                           layer.norm2.weight.grad.data_ptr(), layer.norm2.bias.grad.data_ptr(), s), "ops_dropout_add_layernorm_bwd")
+            n1, n2 = layer.norm1, layer.norm2
+            d_f, dres2 = _dropout_add_layernorm_bwd(g32, g16, z2, mean2, rstd2, n2.weight, (ps[3], seeds[3], used), n2.weight.grad, n2.bias.grad)
             train.shadow_param_grads(r2, d_f, h)
-            d_h = d_f @ r2.w_sh
-            d_u = torch.empty((T, ff), **bf)
-            _cabi.check(lib.ops_act_dropout_bwd(T * ff, u.data_ptr(), d_h.data_ptr(), d_u.data_ptr(), 0.0, ps[2], seeds[2], used.data_ptr(), s), "ops_act_dropout_bwd")
+            d_u = _act_dropout_bwd(u, d_f @ r2.w_sh, 0.0, (ps[2], seeds[2], used))
             train.shadow_param_grads(r1, d_u, y1_16)
-            d_y1 = d_u @ r1.w_sh
             # LayerNorm1 <- (dres2, d_y1)
-            d_a, dres1 = torch.empty((T, d), **bf), torch.empty((T, d), **f32)
-            _cabi.check(lib.ops_dropout_add_layernorm_bwd(T, d, dres2.data_ptr(), d_y1.data_ptr(), z1.data_ptr(), mean1.data_ptr(), rstd1.data_ptr(),
-                                                           layer.norm1.weight.data_ptr(), ps[1], seeds[1], used.data_ptr(), d_a.data_ptr(), dres1.data_ptr(),
-                                                           layer.norm1.weight.grad.data_ptr(), layer.norm1.bias.grad.data_ptr(), s), "ops_dropout_add_layernorm_bwd")
+            d_a, dres1 = _dropout_add_layernorm_bwd(dres2, d_u @ r1.w_sh, z1, mean1, rstd1, n1.weight, (ps[1], seeds[1], used), n1.weight.grad, n1.bias.grad)
             train.shadow_param_grads(rout, d_a, ctxa)
-            d_ctx = d_a @ rout.w_sh
-            dqkv = torch.empty((T, 3 * d), **bf)
-            _cabi.check(lib.ops_seq_attention_bwd(Bn, S, H, dh, qkv.data_ptr(), d_ctx.data_ptr(), dqkv.data_ptr(), ps[0], seeds[0], used.data_ptr(), s),
-                         "ops_seq_attention_bwd")
+            dqkv = _attention_bwd(qkv, d_a @ rout.w_sh, Bn, S, H, dh, (ps[0], seeds[0], used))
             train.shadow_param_grads(rin, dqkv, x16)
             d_x16 = dqkv @ rin.w_sh
         return dres1, d_x16, None, None, None, None, None, None
@@ -459,15 +493,13 @@ def _layer_fused_ok(layer: nn.Module, st: _State) -> bool:
     16-byte aligned in the shadow buffer, LayerNorm gradients going straight into zeroed `.grad` views."""
     mha = layer.self_attn
     d, H = mha.embed_dim, mha.num_heads
-    recs = [getattr(getattr(mha, "_ops_in_proj", None), "rec", None), getattr(getattr(mha, "_ops_out_proj", None), "rec", None),
-            getattr(getattr(layer.linear1, "_ops_prod", None), "rec", None), getattr(getattr(layer.linear2, "_ops_prod", None), "rec", None)]
-    if not (LAYER_FWD and st.direct and hasattr(layer, "_ops_tiles") and all(r is not None and r.b_sh is not None for r in recs)):
+    recs = _shadow_recs((mha, mha, layer.linear1, layer.linear2), ("_ops_in_proj", "_ops_out_proj", "_ops_prod", "_ops_prod"))
+    if not (LAYER_FWD and st.direct and hasattr(layer, "_ops_tiles") and recs is not None):
         return False
     ff = layer.linear1.out_features
     if not (d <= 128 and d % 8 == 0 and d // H <= 16 and H <= 8 and 16 <= ff <= 256 and ff % 8 == 0):
         return False
-    return all(t.grad is not None and t.grad.dtype == torch.float32 and t.grad.is_contiguous()
-               for t in (layer.norm1.weight, layer.norm1.bias, layer.norm2.weight, layer.norm2.bias))
+    return _grads_are_flat_views(layer.norm1.weight, layer.norm1.bias, layer.norm2.weight, layer.norm2.bias)
 
 
 def _layer_ok(layer: nn.Module) -> bool:
@@ -506,9 +538,7 @@ def _attention_ok(enc: nn.TransformerEncoder, S: int, training: bool) -> bool:
 
 def encoder_forward(enc: nn.TransformerEncoder, src: torch.Tensor, st: _State) -> torch.Tensor:
     """The fast path proper: src [B, S, d] float32 -> [B, S, d] float32 (training mode, S <= 8)."""
-    global _PENDING_LAYER, _PENDING_BWD
-    _PENDING_LAYER = None                  # (a pass that died between a deferred launch and its successor leaves nothing behind)
-    _PENDING_BWD = None
+    st.pending_layer = st.pending_bwd = None       # (an earlier pass of THIS model that died between a deferred launch and its partner leaves nothing behind)
     B, S, d = src.shape
     T = B * S
     st.advance()                           # fresh dropout masks for this pass (the launches only read the counter)
@@ -523,7 +553,7 @@ def encoder_forward(enc: nn.TransformerEncoder, src: torch.Tensor, st: _State) -
         mha = layer.self_attn
         if x16 is not None and _layer_fused_ok(layer, st):
             # the whole layer forward: one launch -- or, for two consecutive layers, one launch for both (the first one's is deferred)
-            defer = bool(LAYER_PAIR_FWD and _PENDING_LAYER is None and li + 1 < nl and _layer_fused_ok(enc.layers[li + 1], st) and _TRACE_BWD is None)
+            defer = bool(LAYER_PAIR_FWD and st.pending_layer is None and li + 1 < nl and _layer_fused_ok(enc.layers[li + 1], st) and _TRACE_BWD is None)
             res, x16 = EncoderLayerFn.apply(res, x16, layer, B, S, st, li, defer)
             continue
         qkv = mha._ops_in_proj(res if x16 is None else x16)                                         # [T, 3 d] bf16
@@ -565,20 +595,14 @@ class DiffusionCombine(torch.autograd.Function):
         B, Nc, d, st = ctx.cfg
         if g is None and g16 is None:
             return (None,) * 9
-        if g is not None:
-            g = g.contiguous().float()
-        if g16 is not None:
-            g16 = g16.contiguous()
-            if g16.dtype != torch.bfloat16:
-                g16 = g16.to(torch.bfloat16)
+        g, g16 = _f32(g), _bf16(g16)
         dev = (g if g is not None else g16).device
         dm = torch.empty((B * Nc, d), dtype=torch.bfloat16, device=dev)
-        direct = st.direct and cls.grad is not None and cls.grad.dtype == torch.float32 and cls.grad.is_contiguous()
+        direct = st.direct and _grads_are_flat_views(cls)
         dcls = cls.grad if direct else torch.zeros_like(cls)
         with torch.cuda.device(dev):
-            _cabi.check(lib.ops_diffusion_combine_bwd(B, Nc, d, g.data_ptr() if g is not None else None, g16.data_ptr() if g16 is not None else None,
-                                                       sa.data_ptr(), sb.data_ptr(), dm.data_ptr(), dcls.data_ptr(), _stream(dev)),
-                         "ops_diffusion_combine_bwd")
+            _cabi.check(lib.ops_diffusion_combine_bwd(B, Nc, d, _ptr(g), _ptr(g16), sa.data_ptr(), sb.data_ptr(), dm.data_ptr(), dcls.data_ptr(),
+                                                       _stream(dev)), "ops_diffusion_combine_bwd")
         return dm, None, None, None, None if direct else dcls, None, None, None, None
 
 
@@ -629,10 +653,10 @@ class FrontFn(torch.autograd.Function):
         t = torch.empty(rows, dtype=torch.int64, device=dev) if keep else None
         eps = torch.empty((rows, d), **f32) if keep else None
         st.gathered = False
-        gs = _GATHER if (_GATHER is not None and _GATHER["owner"] is model and st.train_mode and st.external and st.counter.numel() >= 2) else None
+        gs = st.gather if (st.train_mode and st.external and st.counter.numel() >= 2) else None
         if gs is not None and not (gs["src"].shape[1] == Nc and gs["src"].shape[2] == d and gs["src"].device == dev):
             gs = None
-        a = _cabi.TfdFrontArgs(identity_act=int(IDENTITY_ACT), B=B, Nc=Nc, d=d, hid=hid, T=int(dm.T), x=x.data_ptr(), alpha_cumprod=dm._acp.data_ptr(), seed=st.seed + 7919 * 100,
+        a = _cabi.TfdFrontArgs(identity_act=int(IDENTITY_ACT), B=B, Nc=Nc, d=d, hid=hid, T=int(dm.T), x=x.data_ptr(), alpha_cumprod=dm._acp.data_ptr(), seed=st.site_seed(100),
                                counter=st.counter.data_ptr(), W0=tiles["mlp0"][0].data_ptr(), b0=r0.b_sh.data_ptr(), W2=tiles["mlp2"][0].data_ptr(),
                                b2=r2.b_sh.data_ptr(), cls=model.cls_token.data_ptr(), pe=model.pos_encoder.pe.data_ptr(), xn16=xn16.data_ptr(),
                                h=h.data_ptr(), sa=sa.data_ptr(), sb=sb.data_ptr(), z=z.data_ptr(), z16=z16.data_ptr(),
@@ -660,16 +684,11 @@ class FrontFn(torch.autograd.Function):
         model, B, Nc, d, hid, st, (r0, r2) = ctx.cfg
         tiles = model.transformer_encoder._ops_extra_tiles
         dev = xn16.device
-        if g is not None:
-            g = g.contiguous().float()
-        if g16 is not None:
-            g16 = g16.contiguous()
-            if g16.dtype != torch.bfloat16:
-                g16 = g16.to(torch.bfloat16)
+        g, g16 = _f32(g), _bf16(g16)
         rows = B * Nc
         dm_, d_h = torch.empty((rows, d), dtype=torch.bfloat16, device=dev), torch.empty((rows, hid), dtype=torch.bfloat16, device=dev)
         cls = model.cls_token
-        a = _cabi.TfdFrontBwdArgs(B=B, Nc=Nc, d=d, hid=hid, g32=g.data_ptr() if g is not None else None, g16=g16.data_ptr() if g16 is not None else None,
+        a = _cabi.TfdFrontBwdArgs(B=B, Nc=Nc, d=d, hid=hid, g32=_ptr(g), g16=_ptr(g16),
                                   sa=sa.data_ptr(), sb=sb.data_ptr(), h=h.data_ptr(), Wt2=tiles["mlp2"][1].data_ptr(), dm=dm_.data_ptr(), d_h=d_h.data_ptr(),
                                   dcls=cls.grad.data_ptr())
         with torch.cuda.device(dev):
@@ -684,12 +703,11 @@ def _front_fused_ok(model: nn.Module, st: _State, d: int) -> bool:
     tiles = getattr(model.transformer_encoder, "_ops_extra_tiles", None) or {}
     if not (FRONT and DRAW and st.direct and "mlp0" in tiles and "mlp2" in tiles and type(mlp[0]) is nn.Linear and type(mlp[2]) is nn.Linear):
         return False
-    recs = [getattr(getattr(m, "_ops_prod", None), "rec", None) for m in (mlp[0], mlp[2])]
     hid = mlp[0].out_features
     cls = model.cls_token
-    return (all(r is not None and r.b_sh is not None for r in recs) and d % 8 == 0 and d <= 128 and 16 <= hid <= 256 and hid % 8 == 0
+    return (_shadow_recs((mlp[0], mlp[2])) is not None and d % 8 == 0 and d <= 128 and 16 <= hid <= 256 and hid % 8 == 0
             and mlp[0].in_features == d and mlp[2].out_features == d and cls.dtype == torch.float32 and cls.is_contiguous() and cls.numel() == d
-            and cls.grad is not None and cls.grad.dtype == torch.float32 and cls.grad.is_contiguous()
+            and _grads_are_flat_views(cls)
             and model.pos_encoder.pe.dtype == torch.float32 and model.pos_encoder.pe.is_contiguous())
 
 
@@ -714,11 +732,11 @@ class HeadFn(torch.autograd.Function):
         bf, f32 = dict(dtype=torch.bfloat16, device=dev), dict(dtype=torch.float32, device=dev)
         a16, h, out = torch.empty((B, hid), **bf), torch.empty((B, hid), **bf), torch.empty((B, C), **bf)
         mean, rstd = torch.empty(B, **f32), torch.empty(B, **f32)
-        used = st.used(103)
+        used = st.used()
         p = float(model.dropout.p) if st.train_mode else 0.0
         a = _cabi.TfdHeadArgs(identity_act=int(IDENTITY_ACT), B=B, S=S, d=d, hid=hid, C=C, y16=x16.data_ptr(), W1=tiles["fc1"][0].data_ptr(), b1=r1.b_sh.data_ptr(),
                               gamma=model.norm1.weight.data_ptr(), beta=model.norm1.bias.data_ptr(), eps=float(model.norm1.eps),
-                              W2=tiles["fc2"][0].data_ptr(), b2=r2.b_sh.data_ptr(), p_drop=p, seed=st.seed + 7919 * 103,
+                              W2=tiles["fc2"][0].data_ptr(), b2=r2.b_sh.data_ptr(), p_drop=p, seed=st.site_seed(103),
                               counter=st.counter.data_ptr(), used_call=used.data_ptr(), a16=a16.data_ptr(), mean=mean.data_ptr(),
                               rstd=rstd.data_ptr(), h=h.data_ptr(), out=out.data_ptr())
         ctx.loss = None
@@ -729,8 +747,8 @@ class HeadFn(torch.autograd.Function):
             loss = torch.empty((), **f32)
             alpha, minc, maxc = crit.alpha.detach(), sc(crit.min_constraint), sc(crit.max_constraint)
             a.targets, a.grad, a.loss_part, a.alpha = targets.data_ptr(), grad.data_ptr(), part.data_ptr(), alpha.data_ptr()
-            if getattr(st, "gathered", False) and _GATHER is not None:      # the front end assembled this batch: targets by its row indices
-                a.targets, a.target_rows = _GATHER["targets"].data_ptr(), _GATHER["idx_out"].data_ptr()
+            if st.gathered and st.gather is not None:      # the front end assembled this batch: targets by its row indices
+                a.targets, a.target_rows = st.gather["targets"].data_ptr(), st.gather["idx_out"].data_ptr()
             a.min_constraint = minc.data_ptr() if minc is not None else None
             a.max_constraint = maxc.data_ptr() if maxc is not None else None
             a.box_weight = float(crit.penalty_weight)
@@ -756,15 +774,9 @@ class HeadFn(torch.autograd.Function):
         dev = x16.device
         if ctx.loss is not None:
             # the forward launch's own d loss / d out (the loss enters the total with weight one) + whatever else hangs on the predictions
-            g2 = None
-            if g is not None:
-                g2 = g.contiguous() if g.dtype == torch.bfloat16 else g.to(torch.bfloat16)
-            g = ctx.loss[0]                     # (g2: summed into it by the launch below, in place)
+            g2, g = _bf16(g), ctx.loss[0]       # (g2: summed into g by the launch below, in place)
         else:
-            g2 = None
-            g = g.contiguous()
-            if g.dtype != torch.bfloat16:
-                g = g.to(torch.bfloat16)
+            g2, g = None, _bf16(g)
         d_a = torch.empty((B, hid), dtype=torch.bfloat16, device=dev)
         full = st.zeros16((B * S, d))
         a = _cabi.TfdHeadBwdArgs(B=B, S=S, d=d, hid=hid, C=C, g=g.data_ptr(), Wt2=tiles["fc2"][1].data_ptr(), Wt1=tiles["fc1"][1].data_ptr(),
@@ -794,26 +806,45 @@ class HeadFn(torch.autograd.Function):
         return full, None, None, None, None, None
 
 
-_GATHER = None            # dict(src, order, cursor, idx_out, sigma, seed): armed by the training loop for a whole run (arm_gather)
+def encoder_state(enc: nn.Module, device) -> _State:
+    """The state of a patched encoder (patch_encoder / patch_model) on `device`, made on first use: ONE dropout stream for the model and
+    its encoder -- the encoder pass advances the call counter once per step (one captured add_), and the head's dropout (site 103, drawn
+    after the encoder) reads the same counter; a state of its own that nothing advanced gave it the same mask in every step of a run."""
+    states = enc._ops_dropout_state
+    st = states.get(device)
+    if st is None:
+        seed, direct = enc._ops_state_args
+        st = states[device] = _State(device, seed, direct, getattr(enc, "_ops_step_counter", None))
+    return st
+
+
+def _states(model: nn.Module):
+    return getattr(getattr(model, "transformer_encoder", None), "_ops_dropout_state", {}).values()
 
 
 def arm_gather(model: nn.Module, src: torch.Tensor, targets: torch.Tensor, order: torch.Tensor, cursor: torch.Tensor, idx_out: torch.Tensor,
                sigma: torch.Tensor, seed: int) -> None:
-    """From now on the fused front end of THIS patched model in training mode assembles its own batch (any other model's passes are untouched:
-    a run that died before `disarm_gather` must not feed its tensors to the next one): sample b = row order[cursor + b] of
+    """From now on the fused front end of THIS patched model in training mode assembles its own batch (kept on the model's state for
+    src.device, so no other model's passes see it; arm after `share_step_counter`, which discards states): sample b = row order[cursor + b] of
     `src` [n, Nc, d] float32 + sigma * N(0, 1) from the batch-assembly stream (`seed`, the shared step counter), the tensor handed to
     `model(x)` only gives the batch size; idx_out [>= B] receives the rows, through which the head's loss-on-the-tile reads rows of
     `targets` [n, C] float32 (the step must arm it: arm_head_loss); the launch advances the step counter and `cursor` itself.
-    `disarm_gather()` ends it."""
-    global _GATHER
+    `disarm_gather(model)` ends it, and so does `unpatch_model`."""
     assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 3 and order.dtype == torch.int64 and cursor.dtype == torch.int64
     assert targets.dtype == torch.float32 and targets.is_contiguous() and targets.dim() == 2 and targets.shape[0] == src.shape[0]
-    _GATHER = dict(owner=model, src=src, targets=targets, order=order, cursor=cursor, idx_out=idx_out, sigma=sigma, seed=int(seed) & 0x7FFFFFFFFFFFFFFF)
+    encoder_state(model.transformer_encoder, src.device).gather = dict(src=src, targets=targets, order=order, cursor=cursor, idx_out=idx_out, sigma=sigma,
+                                                                       seed=int(seed) & 0x7FFFFFFFFFFFFFFF)
 
 
-def disarm_gather() -> None:
-    global _GATHER
-    _GATHER = None
+def disarm_gather(model: nn.Module) -> None:
+    for st in _states(model):
+        st.gather = None
+
+
+def _all_fused_ok(model: nn.Module, st: _State, d: int) -> bool:
+    """Front end, head and every encoder layer have their one-launch form."""
+    enc = model.transformer_encoder
+    return _front_fused_ok(model, st, d) and _head_fused_ok(model, st, d) and enc.norm is None and all(_layer_fused_ok(l, st) for l in enc.layers)
 
 
 def gather_fusable(model: nn.Module, device, d: int) -> bool:
@@ -823,30 +854,29 @@ def gather_fusable(model: nn.Module, device, d: int) -> bool:
     if enc is None or "forward" not in model.__dict__ or getattr(enc, "_ops_step_counter", None) is None:
         return False
     st = _State(torch.device(device), 1, True, enc._ops_step_counter)
-    return bool(FRONT_GATHER and HEAD_LOSS and st.external and st.counter.numel() >= 2 and _front_fused_ok(model, st, d) and _head_fused_ok(model, st, d)
-                and enc.norm is None and all(_layer_fused_ok(l, st) for l in enc.layers))
+    return bool(FRONT_GATHER and HEAD_LOSS and st.external and st.counter.numel() >= 2 and _all_fused_ok(model, st, d))
 
 
-_PENDING_LOSS = None      # (targets, criterion, alpha0, running sum): armed by the training step for ITS next forward pass
-_TAKEN_LOSS = None
-
-
-def arm_head_loss(targets: torch.Tensor, crit: nn.Module, alpha0, acc) -> bool:
-    """The training step's next forward pass of a patched model may compute its TrainableL1L2Loss on the head's output tile (two launches
-    of the step less); `take_head_loss()` afterwards tells whether it did.  False: not this criterion / these targets."""
-    global _PENDING_LOSS, _TAKEN_LOSS
+def arm_head_loss(model: nn.Module, targets: torch.Tensor, crit: nn.Module, alpha0, acc) -> bool:
+    """The training step's next forward pass of THIS patched model may compute its TrainableL1L2Loss on the head's output tile (two launches
+    of the step less); `take_head_loss(model)` afterwards tells whether it did.  False: not this criterion / these targets / not patched."""
     from .surrogates import TrainableL1L2Loss
-    _TAKEN_LOSS = None
     ok = (HEAD_LOSS and type(crit) is TrainableL1L2Loss and torch.is_tensor(targets) and targets.is_cuda and targets.dtype == torch.float32
-          and targets.dim() == 2 and targets.is_contiguous())
-    _PENDING_LOSS = (targets, crit, alpha0, acc) if ok else None
+          and targets.dim() == 2 and targets.is_contiguous() and hasattr(getattr(model, "transformer_encoder", None), "_ops_dropout_state"))
+    for st in _states(model):
+        st.loss_spec = st.taken_loss = None
+    if ok:
+        encoder_state(model.transformer_encoder, targets.device).loss_spec = (targets, crit, alpha0, acc)
     return ok
 
 
-def take_head_loss():
-    """The loss the last forward pass computed on the head's tile (an autograd scalar), or None."""
-    global _PENDING_LOSS, _TAKEN_LOSS
-    loss, _TAKEN_LOSS, _PENDING_LOSS = _TAKEN_LOSS, None, None
+def take_head_loss(model: nn.Module):
+    """The loss this model's last forward pass computed on the head's tile (an autograd scalar), or None."""
+    loss = None
+    for st in _states(model):
+        if loss is None:
+            loss = st.taken_loss
+        st.taken_loss = st.loss_spec = None
     return loss
 
 
@@ -855,11 +885,10 @@ def _head_fused_ok(model: nn.Module, st: _State, d: int) -> bool:
     if type(model.fc1) is not nn.Linear or type(model.fc2) is not nn.Linear:
         return False
     tiles = getattr(enc, "_ops_extra_tiles", None) or {}
-    recs = [getattr(getattr(m, "_ops_prod", None), "rec", None) for m in (model.fc1, model.fc2)]
     hid, C = model.fc1.out_features, model.fc2.out_features
-    return (HEAD and st.direct and "fc1" in tiles and "fc2" in tiles and all(r is not None and r.b_sh is not None for r in recs) and d % 8 == 0
+    return (HEAD and st.direct and "fc1" in tiles and "fc2" in tiles and _shadow_recs((model.fc1, model.fc2)) is not None and d % 8 == 0
             and d <= 128 and 16 <= hid <= 256 and hid % 8 == 0 and 4 <= C <= 128 and C % 4 == 0 and model.fc1.in_features == d
-            and all(t.grad is not None and t.grad.dtype == torch.float32 and t.grad.is_contiguous() for t in (model.norm1.weight, model.norm1.bias)))
+            and _grads_are_flat_views(model.norm1.weight, model.norm1.bias))
 
 
 def model_forward(model: nn.Module, x: torch.Tensor, st: _State) -> torch.Tensor:
@@ -868,13 +897,13 @@ def model_forward(model: nn.Module, x: torch.Tensor, st: _State) -> torch.Tensor
     noise are drawn inside the first launch (DRAW; or by the framework's generators in the module's order: torch.randint, torch.randn_like).  `st` is the
     ENCODER's dropout state: its pass below advances the counter before the head's dropout (the only site out here with p > 0,
     TFD:573) draws its mask."""
-    lib = _cabi.load()
     B, Nc, d = x.shape
     dm = model.diffusion
     x = x.contiguous()
     if _front_fused_ok(model, st, d):
         z, z16 = FrontFn.apply(x, model.cls_token, model, st)                                      # draws, x_noisy, MLP, combine: one launch
         return _model_tail(model, z, z16, st, B, Nc, d)
+    lib = _cabi.load()
     rows = B * Nc
     xn32 = torch.empty((rows, d), dtype=torch.float32, device=x.device)
     xn16 = torch.empty((rows, d), dtype=torch.bfloat16, device=x.device)
@@ -885,7 +914,7 @@ def model_forward(model: nn.Module, x: torch.Tensor, st: _State) -> torch.Tensor
             keep = st.keep_draws or KEEP_DRAWS
             t = torch.empty(rows, dtype=torch.int64, device=x.device) if keep else None
             eps = torch.empty((rows, d), dtype=torch.float32, device=x.device) if keep else None
-            _cabi.check(lib.ops_diffusion_noise_draw(rows, d, int(dm.T), x.data_ptr(), dm._acp.data_ptr(), st.seed + 7919 * 100, st.counter.data_ptr(),
+            _cabi.check(lib.ops_diffusion_noise_draw(rows, d, int(dm.T), x.data_ptr(), dm._acp.data_ptr(), st.site_seed(100), st.counter.data_ptr(),
                                                       xn32.data_ptr(), xn16.data_ptr(), sa.data_ptr(), sb.data_ptr(), t.data_ptr() if keep else None,
                                                       eps.data_ptr() if keep else None, _stream(x.device)), "ops_diffusion_noise_draw")
             if keep:
@@ -907,18 +936,15 @@ def _model_tail(model: nn.Module, z: torch.Tensor, z16: torch.Tensor, st: _State
     z = model.transformer_encoder(z)
     if st.last16 is not None and model.transformer_encoder.norm is None and _head_fused_ok(model, st, d):
         last16, st.last16 = st.last16, None
-        global _PENDING_LOSS, _TAKEN_LOSS
-        spec, _PENDING_LOSS = _PENDING_LOSS, None
+        spec, st.loss_spec = st.loss_spec, None
         if (spec is not None and st.train_mode and torch.is_grad_enabled() and tuple(spec[0].shape) == (B, model.fc2.out_features)
                 and spec[0].device == last16.device):
-            out, _TAKEN_LOSS = HeadFn.apply(last16, model, B, Nc + 1, st, spec)   # ... and the loss on its output tile
+            out, st.taken_loss = HeadFn.apply(last16, model, B, Nc + 1, st, spec)   # ... and the loss on its output tile
             return out
         return HeadFn.apply(last16, model, B, Nc + 1, st, None)                      # the whole head: one launch
     if st.last16 is not None and model.transformer_encoder.norm is None:
-        from . import train
-        train.set_next_input_grad_dest(st.zeros16((B * (Nc + 1), d)).view(B, Nc + 1, d)[:, 0, :])   # fc1's input gradient lands in the [CLS] rows
-        a = model.fc1(ClsRows.apply(st.last16, B, Nc + 1, st))                     # bf16 [B, hidden], read in place (no slice copy / cast)
-        train.set_next_input_grad_dest(None)
+        # bf16 [B, hidden], read in place (no slice copy / cast); fc1's input gradient lands in the [CLS] rows of a persistent zero tensor
+        a = model.fc1._ops_prod(ClsRows.apply(st.last16, B, Nc + 1, st), gx_dest=st.zeros16((B * (Nc + 1), d)).view(B, Nc + 1, d)[:, 0, :])
         st.last16 = None
     else:
         a = model.fc1(z[:, 0, :])
@@ -944,27 +970,18 @@ def patch_model(model: nn.Module, seed: int, direct_param_grads: bool = False) -
     if LAYER_FWD and HEAD and "forward" in model.fc2.__dict__:
         # the head's two weight matrices join the layers' tiled copies (one-launch head: HeadFn)
         enable_layer_tiles(model.transformer_encoder, extra={"fc1": model.fc1.weight, "fc2": model.fc2.weight, "mlp0": mlp[0].weight, "mlp2": mlp[2].weight})
-    # ONE dropout stream for the model and its encoder: the encoder pass advances the call counter once per step (one captured
-    # add_), and the head's dropout (site 103, drawn after the encoder) reads the same counter -- a state of its own that nothing
-    # advanced gave it the same mask in every step of a run
-    state = model.transformer_encoder._ops_dropout_state
     cls = type(model)
 
     def forward(self, x):
         fast = ((self.training or (EVAL_FAST and not torch.is_grad_enabled())) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32
-                and x.shape[1] == self.n_cases and x.shape[1] < 8 and torch.is_autocast_enabled("cuda")
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+                and x.shape[1] == self.n_cases and x.shape[1] < 8 and _bf16_autocast())
         if not fast:
             return cls.forward(self, x)
-        st = state.get(x.device)
-        if st is None:
-            st = state[x.device] = _State(x.device, seed, direct_param_grads, getattr(self.transformer_encoder, "_ops_step_counter", None))
+        st = encoder_state(self.transformer_encoder, x.device)
         if not self.training:
             # evaluation (no gradients): the same launches with every dropout probability 0 (the diffusion noise is NOT gated on the
             # mode, TFD:443-478) -- only when every block has its one-launch form; ~70 us per batch against ~500 through the modules
-            enc = self.transformer_encoder
-            if not (_front_fused_ok(self, st, x.shape[2]) and _head_fused_ok(self, st, x.shape[2]) and enc.norm is None
-                    and all(_layer_fused_ok(l, st) for l in enc.layers)):
+            if not _all_fused_ok(self, st, x.shape[2]):
                 return cls.forward(self, x)
             st.train_mode = False
             try:
@@ -978,6 +995,7 @@ def patch_model(model: nn.Module, seed: int, direct_param_grads: bool = False) -
 
 
 def unpatch_model(model: nn.Module) -> None:
+    """The module's own forward again; the states go, and whatever was armed on them (arm_gather, arm_head_loss) with them."""
     if "forward" in model.__dict__:
         del model.__dict__["forward"]
     if hasattr(model, "transformer_encoder"):
@@ -991,21 +1009,18 @@ def patch_encoder(enc: nn.TransformerEncoder, seed: int, direct_param_grads: boo
     training loop's flat buffer), so LayerNorm gradients may be assigned there.  Returns whether the encoder qualifies at all."""
     if not (ENABLED and type(enc) is nn.TransformerEncoder and all(_layer_ok(l) for l in enc.layers)):
         return False
-    state = {}
-    enc._ops_dropout_state = state          # device -> _State; patch_model's front end / head draw from the same stream
+    enc._ops_dropout_state = {}             # device -> _State (encoder_state); patch_model's front end / head draw from the same stream
+    enc._ops_state_args = (seed, direct_param_grads)
 
     def forward(self, src, mask=None, src_key_padding_mask=None, is_causal=None):
-        st0 = state.get(src.device)
+        st0 = self._ops_dropout_state.get(src.device)
         eval_pass = st0 is not None and not st0.train_mode and not self.training and not torch.is_grad_enabled()    # (set by the model's patched forward)
         fast = ((self.training or eval_pass) and src.is_cuda and src.dim() == 3 and src.shape[1] <= 8 and mask is None and src_key_padding_mask is None
-                and not is_causal and torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
+                and not is_causal and _bf16_autocast()
                 and src.dtype == torch.float32 and _attention_ok(self, src.shape[1], self.training))
         if not fast:
             return nn.TransformerEncoder.forward(self, src, mask=mask, src_key_padding_mask=src_key_padding_mask, is_causal=is_causal)
-        st = state.get(src.device)
-        if st is None:
-            st = state[src.device] = _State(src.device, seed, direct_param_grads, getattr(self, "_ops_step_counter", None))
-        return encoder_forward(self, src, st)
+        return encoder_forward(self, src, encoder_state(self, src.device))
 
     enc.forward = types.MethodType(forward, enc)
     if LAYER_FWD:
@@ -1017,6 +1032,7 @@ def unpatch_encoder(enc: nn.Module) -> None:
     if "forward" in enc.__dict__:
         del enc.__dict__["forward"]
     enc.__dict__.pop("_ops_dropout_state", None)
+    enc.__dict__.pop("_ops_state_args", None)
     enc.__dict__.pop("_ops_tile_entries", None)
     enc.__dict__.pop("_ops_extra_tiles", None)
     enc.__dict__.pop("_ops_step_counter", None)

@@ -26,6 +26,7 @@ the running statistics are averaged over ranks at the end of every epoch so that
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import os
 import sys
@@ -322,35 +323,26 @@ def _debug_nan(model, opt, flat, s_loss, epoch, b, sX, sY):
         raise RuntimeError("non-finite value in the training step")
 
 
-_NEXT_GX_DEST = None      # see set_next_input_grad_dest
-
-
-def set_next_input_grad_dest(dest: Optional[torch.Tensor]) -> None:
-    """The NEXT shadow product's backward pass writes its input gradient straight into `dest` (a [rows, K] bfloat16 tensor, rows may be
-    strided) instead of a fresh tensor: the Transformer-Diffusion head hands the [CLS] rows of a persistent zero tensor, and the row
-    scatter that followed the product disappears from the step."""
-    global _NEXT_GX_DEST
-    _NEXT_GX_DEST = dest if switches.get("gx_dest") == "1" else None
-
-
 class _ShadowLinearFn(torch.autograd.Function):
-    """y = x W^T + b with W, b taken from the optimiser's bfloat16 shadow; the weight / bias gradients are not returned to
-    autograd but left (in bfloat16) in `stash`, from where ONE multi-tensor copy moves all of them into the flat float32
-    gradient buffer.  Same arithmetic as nn.Linear under bf16 autocast (bf16 operands, fp32 accumulation, bf16 results),
-    without its per-step kernels: weight cast, bias cast, gradient cast back and accumulate -- four per parameter."""
+    """y = x W^T + b with W, b taken from the optimiser's bfloat16 shadow (`rec`: ShadowRec); the weight / bias gradients are not
+    returned to autograd but go where `shadow_param_grads` sends them.  Same arithmetic as nn.Linear under bf16 autocast (bf16 operands,
+    fp32 accumulation, bf16 results), without its per-step kernels: weight cast, bias cast, gradient cast back and accumulate -- four
+    per parameter."""
 
     @staticmethod
-    def forward(ctx, x, w_sh, b_sh, stash, iw, ib, anchor, w_grad=None, b_grad=None):
+    def forward(ctx, x, rec, anchor, gx_dest=None):
         # `anchor` (the layer's float32 weight Parameter) is not read: it makes autograd record the node even when x
-        # needs no gradient (first layer); its own gradient slot stays None -- the gradients travel through `stash`
-        # (or, for products over thousands of rows, straight into `w_grad`, the weight's slice of the zeroed flat gradient buffer)
+        # needs no gradient (first layer); its own gradient slot stays None
+        # `gx_dest`: the backward pass writes the input gradient straight into it (a [rows, K] bfloat16 tensor, rows may be strided) instead of
+        # a fresh tensor: the Transformer-Diffusion head hands the [CLS] rows of a persistent zero tensor, and the row scatter that followed
+        # the product disappears from the step
+        w_sh, b_sh = rec.w_sh, rec.b_sh
         xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
         x2 = xb.reshape(-1, xb.shape[-1])
         y = torch.addmm(b_sh, x2, w_sh.t()) if b_sh is not None else x2 @ w_sh.t()
         ctx.save_for_backward(x2, w_sh)
-        ctx.stash, ctx.iw, ctx.ib, ctx.xshape, ctx.xdtype, ctx.w_grad, ctx.b_grad = stash, iw, ib, x.shape, x.dtype, w_grad, b_grad
-        global _NEXT_GX_DEST
-        ctx.gx_dest, _NEXT_GX_DEST = _NEXT_GX_DEST, None
+        ctx.rec, ctx.xshape, ctx.xdtype = rec, x.shape, x.dtype
+        ctx.gx_dest = gx_dest if (gx_dest is not None and switches.get("gx_dest") == "1") else None
         return y.reshape(*x.shape[:-1], w_sh.shape[0])
 
     @staticmethod
@@ -359,31 +351,7 @@ class _ShadowLinearFn(torch.autograd.Function):
         g2 = gy.reshape(-1, gy.shape[-1])
         if g2.dtype != torch.bfloat16:
             g2 = g2.to(torch.bfloat16)
-        if ctx.w_grad is not None and x2.shape[0] >= _SPLIT_WGRAD_ROWS and _SPLIT_WGRAD_ROWS > 0:
-            # many rows, small output: the library walks all rows inside a handful of tiles (25 us for 3584 x 360 x 120) and the bias
-            # gradient is another reduction pass (11 us); the split-row kernel of csrc/seq_block.hip adds partial tiles -- and the
-            # column sums of the slabs it reads anyway -- into the float32 gradients itself
-            from . import _cabi
-            g2 = g2.contiguous()
-            rows_ok = switches.get("wgrad_rows") == "1" and _WGRAD_QUEUE is not None and x2.dim() == 2 and x2.stride(1) == 1 and x2.stride(0) >= x2.shape[1]
-            x2c = x2 if rows_ok else x2.contiguous()        # the grouped launch takes row strides (the head reads the [CLS] rows in place)
-            fused_bias = ctx.ib is not None and ctx.b_grad is not None
-            if _WGRAD_QUEUE is not None:
-                # deferred: the training step launches every queued product at once after backward (flush_wgrad_queue)
-                _WGRAD_QUEUE.append((g2, x2c, ctx.w_grad, ctx.b_grad if fused_bias else None))
-            else:
-                with torch.cuda.device(g2.device):
-                    rc = _cabi.load().ops_linear_wgrad_accumulate(x2c.shape[0], g2.shape[1], x2c.shape[1], g2.data_ptr(), x2c.data_ptr(),
-                                                                  ctx.w_grad.data_ptr(), ctx.b_grad.data_ptr() if fused_bias else None,
-                                                                  torch.cuda.current_stream(g2.device).cuda_stream)
-                if rc != 0:
-                    raise RuntimeError(f"ops_linear_wgrad_accumulate failed with code {rc}")
-            if ctx.ib is not None and not fused_bias:
-                ctx.stash[ctx.ib] = g2.sum(0)
-        else:
-            ctx.stash[ctx.iw] = g2.t() @ x2
-            if ctx.ib is not None:
-                ctx.stash[ctx.ib] = g2.sum(0)
+        g2 = shadow_param_grads(ctx.rec, g2, x2, row_stride_switch=True)
         gx = None
         if ctx.needs_input_grad[0]:
             dest = ctx.gx_dest
@@ -393,11 +361,13 @@ class _ShadowLinearFn(torch.autograd.Function):
                 gx = (g2 @ w_sh).reshape(ctx.xshape)
                 if gx.dtype != ctx.xdtype:
                     gx = gx.to(ctx.xdtype)
-        return gx, None, None, None, None, None, None, None, None
+        return gx, None, None, None
 
 
 class ShadowRec:
-    """One shadow product's operands and gradient destinations (enable_shadow_linears)."""
+    """One shadow product's operands and gradient destinations (enable_shadow_linears): the weight / bias gradients leave (in bfloat16)
+    through `stash`, from where ONE multi-tensor copy moves all of them into the flat float32 gradient buffer -- or, for products over
+    many rows, are added straight into `w_grad` / `b_grad`, the parameters' slices of the zeroed flat gradient buffer."""
     __slots__ = ("w_sh", "b_sh", "w_grad", "b_grad", "stash", "iw", "ib")
 
     def __init__(self, w_sh, b_sh, w_grad, b_grad, stash, iw, ib):
@@ -413,17 +383,24 @@ def queue_column_sums(rows: torch.Tensor, dest: torch.Tensor) -> bool:
     return True
 
 
-def shadow_param_grads(rec: ShadowRec, g2: torch.Tensor, x2: torch.Tensor) -> None:
-    """Weight / bias gradients of y = x W^T + b given dY = g2 [T, N] and X = x2 [T, K] (bfloat16): exactly what
-    _ShadowLinearFn.backward does with them -- queued for the step's grouped split-row launch when the product has many rows, the
-    library's product into the stash otherwise."""
+def shadow_param_grads(rec: ShadowRec, g2: torch.Tensor, x2: torch.Tensor, row_stride_switch: bool = False) -> torch.Tensor:
+    """Weight / bias gradients of y = x W^T + b given dY = g2 [T, N] and X = x2 [T, K] (bfloat16) -- the one statement of the protocol,
+    for _ShadowLinearFn.backward and for the fused blocks that run the product themselves: queued for the step's grouped split-row launch
+    (launched at once where no step collects) when the product has many rows, the library's product into the stash otherwise.
+    `row_stride_switch`: a row-strided x2 travels without a copy only with the switch wgrad_rows on (the autograd path; the fused blocks
+    always hand theirs over as it is).  Returns dY as it was used (made contiguous on the split-row path)."""
     if rec.w_grad is not None and x2.shape[0] >= _SPLIT_WGRAD_ROWS and _SPLIT_WGRAD_ROWS > 0:
+        # many rows, small output: the library walks all rows inside a handful of tiles (25 us for 3584 x 360 x 120) and the bias
+        # gradient is another reduction pass (11 us); the split-row kernel of csrc/seq_block.hip adds partial tiles -- and the
+        # column sums of the slabs it reads anyway -- into the float32 gradients itself
         from . import _cabi
         g2 = g2.contiguous()
-        rows_ok = _WGRAD_QUEUE is not None and x2.dim() == 2 and x2.stride(1) == 1 and x2.stride(0) >= x2.shape[1]
-        x2c = x2 if rows_ok else x2.contiguous()          # (row-strided operands: the grouped launch takes the stride)
+        rows_ok = ((not row_stride_switch or switches.get("wgrad_rows") == "1") and _WGRAD_QUEUE is not None and x2.dim() == 2
+                   and x2.stride(1) == 1 and x2.stride(0) >= x2.shape[1])
+        x2c = x2 if rows_ok else x2.contiguous()          # the grouped launch takes row strides (the head reads the [CLS] rows in place)
         fused_bias = rec.ib is not None and rec.b_grad is not None
         if _WGRAD_QUEUE is not None:
+            # deferred: the training step launches every queued product at once after backward (flush_wgrad_queue)
             _WGRAD_QUEUE.append((g2, x2c, rec.w_grad, rec.b_grad if fused_bias else None))
         else:
             with torch.cuda.device(g2.device):
@@ -438,6 +415,7 @@ def shadow_param_grads(rec: ShadowRec, g2: torch.Tensor, x2: torch.Tensor) -> No
         rec.stash[rec.iw] = g2.t() @ x2
         if rec.ib is not None:
             rec.stash[rec.ib] = g2.sum(0)
+    return g2
 
 
 def shadow_grads_are_deferred(rec: ShadowRec, rows: int) -> bool:
@@ -452,18 +430,57 @@ def shadow_grads_are_deferred(rec: ShadowRec, rows: int) -> bool:
 # reduces inside the workgroup, so a 10-sample tail batch (70 / 10 rows: twelve library GEMMs of ~16 us + twelve column sums per epoch)
 # is one grouped launch too; only products over fewer rows than one MFMA tile stay with the library
 _SPLIT_WGRAD_ROWS = int(switches.get("split_wgrad_rows"))
-_WGRAD_QUEUE = None          # a list while a training step collects its split-row weight gradients for ONE grouped launch
+
+
+# The step that is collecting right now (grouped_wgrads; autograd nodes reach it here): the list of what its backward pass has queued for
+# the grouped weight-gradient launches -- job tuples (dY, X, dW, dbias), whose operands stay alive in here, and at most one callable, a
+# launch that must run in front of them (run_before_wgrad_flush)
+_WGRAD_QUEUE: Optional[list] = None
+
+
+@contextlib.contextmanager
+def grouped_wgrads(device, stash, dst, enabled: bool = True):
+    """`with grouped_wgrads(device, stash, dst): loss.backward()` -- the backward protocol of a step on shadow products: while the body runs
+    the split-row weight gradients are collected (`enabled` False: every product launches inside backward); a clean exit launches them
+    grouped, moves the live `stash` entries (bfloat16) into their float32 destinations `dst` with one multi-tensor copy and clears the
+    stash.  An exception skips all that; either way nothing is left collecting."""
+    global _WGRAD_QUEUE
+    _WGRAD_QUEUE = [] if enabled else None
+    try:
+        yield _WGRAD_QUEUE
+        flush_wgrad_queue(device)
+    finally:
+        _WGRAD_QUEUE = None
+    live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]      # (a product nobody called this step leaves None)
+    if live:
+        torch._foreach_copy_([dd for dd, _ in live], [ss for _, ss in live])
+    for k in range(len(stash)):
+        stash[k] = None
+
+
+def run_before_wgrad_flush(launch) -> None:
+    """`launch()` runs at the collecting step's flush, in front of its grouped launches (tfd_fused: a layer's backward launch that waits
+    for a predecessor which may never run); None: the one that waited has been taken care of.  At most one waits at a time."""
+    if _WGRAD_QUEUE is not None:
+        waiting = [e for e in _WGRAD_QUEUE if callable(e)]
+        assert launch is None or not waiting
+        for e in waiting:
+            _WGRAD_QUEUE.remove(e)
+        if launch is not None:
+            _WGRAD_QUEUE.append(launch)
 
 
 def flush_wgrad_queue(device) -> None:
-    """Launch everything `_ShadowLinearFn.backward` queued (operands stay alive in the queue until here), 16 products per launch."""
-    from . import _cabi
-    tf = sys.modules.get(__package__ + ".tfd_fused")
-    if tf is not None:
-        tf.flush_pending_backward()        # a layer's backward launch that waited for a predecessor which never ran
-    q = _WGRAD_QUEUE
+    """Launch what the collecting step holds: the waiting launch, then everything queued, 16 products per launch."""
+    if not _WGRAD_QUEUE:
+        return
+    for launch in [e for e in _WGRAD_QUEUE if callable(e)]:
+        launch()
+    q = [e for e in _WGRAD_QUEUE if not callable(e)]
+    _WGRAD_QUEUE.clear()
     if not q:
         return
+    from . import _cabi
     lib = _cabi.load()
     with torch.cuda.device(device):
         s = torch.cuda.current_stream(device).cuda_stream
@@ -481,7 +498,6 @@ def flush_wgrad_queue(device) -> None:
             rc = lib.ops_linear_wgrad_accumulate_group(len(part), arr, s)
             if rc != 0:
                 raise RuntimeError(f"ops_linear_wgrad_accumulate_group failed with code {rc}")
-    q.clear()
 
 
 def enable_shadow_linears(model: nn.Module, opt: "FlatClipAdam", params, flat: torch.Tensor):
@@ -507,11 +523,13 @@ def enable_shadow_linears(model: nn.Module, opt: "FlatClipAdam", params, flat: t
             b_sh = sh[ob:ob + bias.numel()]
             b_grad = flat[ob:ob + bias.numel()]
             ib = len(stash); stash.append(None); dst.append(b_grad)
-        def prod(x):
-            return _ShadowLinearFn.apply(x, w_sh, b_sh, stash, iw, ib, weight, w_grad, b_grad)
+        # (also what a fused block that runs this product itself needs: the shadow operands, and where its gradients go -- shadow_param_grads)
+        rec = ShadowRec(w_sh, b_sh, w_grad, b_grad, stash, iw, ib)
 
-        # what a fused block that runs this product itself needs: the shadow operands, and where its gradients go (shadow_param_grads)
-        prod.rec = ShadowRec(w_sh, b_sh, w_grad, b_grad, stash, iw, ib)
+        def prod(x, gx_dest=None):
+            return _ShadowLinearFn.apply(x, rec, weight, gx_dest)
+
+        prod.rec = rec
         return prod
 
     for mod in model.modules():
@@ -757,9 +775,9 @@ class _Step:
             head_loss = None
             if self.head_loss_ok:
                 # Transformer-Diffusion fast path: the loss on the head's output tile, finished by the head's backward launch
-                self.tfd.arm_head_loss(Yb, crit, alpha0, loss_acc)
+                self.tfd.arm_head_loss(self.model, Yb, crit, alpha0, loss_acc)
                 preds = self.model(Xn)
-                head_loss = self.tfd.take_head_loss()
+                head_loss = self.tfd.take_head_loss(self.model)
                 if head_loss is None and self.fuse_gather:
                     # (with the batch assembled by the front-end launch the static target buffer `Yb` is never filled: the framework-side
                     #  loss below would be evaluated against stale targets -- fail loudly instead)
@@ -785,9 +803,9 @@ class _Step:
             # (with the running sum both launches have already added their values up: the step's scalar only roots the backward pass,
             #  so the two terms are tied without an addition node -- its value is then the data loss alone)
             loss = _TieTerms.apply(loss, term) if (loss_acc is not None and self.physics.fused) else loss + term
-        global _WGRAD_QUEUE
-        _WGRAD_QUEUE = [] if (self.g_stash and _GROUP_WGRAD) else None       # split-row weight gradients: one grouped launch after backward
-        try:
+        # split-row weight gradients: one grouped launch after backward; the shadow-linear weight / bias gradients: one multi-tensor
+        # cast-and-copy into `flat`
+        with grouped_wgrads(self.device, self.g_stash, self.g_dst, enabled=bool(self.g_stash and _GROUP_WGRAD)):
             # the root gradient is a persistent ones tensor: no ones_like() fill node per step.  (r03 kept the implicit form because the
             # explicit one "produced" NaNs in bias gradients of framework-path runs; the NaNs were the HIP runtime's captured-memset
             # defect under the framework's own bias-gradient reductions -- runtime.py item 2 -- and the root gradient only moved the
@@ -798,15 +816,6 @@ class _Step:
                 loss.backward(gradient=_root_ones(self.device))
             else:
                 loss.backward()
-            flush_wgrad_queue(self.device)
-        finally:
-            _WGRAD_QUEUE = None
-        if self.g_stash:                      # the shadow-linear weight / bias gradients: one multi-tensor cast-and-copy into `flat`
-            live = [(dd, ss) for dd, ss in zip(self.g_dst, self.g_stash) if ss is not None]      # (a product nobody called this step leaves None)
-            if live:
-                torch._foreach_copy_([dd for dd, _ in live], [ss for _, ss in live])
-            for k in range(len(self.g_stash)):
-                self.g_stash[k] = None
         return loss.detach()
 
     def apply_update(self):
@@ -879,7 +888,6 @@ def _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use
     if kind == "tfd" and device.type == "cuda":
         from . import tfd_fused          # (here and not at the top: a CPU-only process never needs it)
         st.tfd = tfd_fused
-        tfd_fused.disarm_gather()        # (whatever an earlier run that did not reach its end left armed)
     if init_fn is not None:
         init_fn(model)
     st.bayes_hip = None
@@ -1397,7 +1405,7 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
     reference's DataLoader shuffle, PINN:701, is unseeded; the golden-fixture tests replay the order it drew).
     `autocast_dtype=torch.float16`: the reference's AMP mode (fp16 autocast + GradScaler, PINN:706, :759-768) on the framework modules; the
     returned dict then carries `grad_scaler` = {"scale", "skipped_steps", "steps"}.
-    (An exception in `_run_epochs` skips the teardown below, as it always has: the next run's set-up disarms what this one left armed.)"""
+    (An exception in `_run_epochs` skips the teardown below, as it always has: what the run armed lives on its own model's state.)"""
     st = _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use_graph, physics, init_fn)
     cfg, model, device = st.cfg, st.model, st.device
     hist, best_val, best_state, seg_ev, step_mode = _run_epochs(st, max_epochs if max_epochs is not None else cfg.num_epochs, batch_order, log)
@@ -1411,8 +1419,7 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
         clear_blas_workspaces()
     disable_shadow_linears(st.patched)   # the returned model is a plain module again
     if st.fast_encoder is not None:
-        st.tfd.disarm_gather()
-        st.tfd.unpatch_model(st.fast_encoder)
+        st.tfd.unpatch_model(st.fast_encoder)      # (its states go, and the armed batch assembly with them)
     if hasattr(model, "direct_param_grads"):
         model.direct_param_grads = False
     if best_state is not None:

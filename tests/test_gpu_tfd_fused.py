@@ -157,31 +157,36 @@ def _encoder(d=120, H=8, ff=256, layers=2, p=0.0, seed=0):
     return enc.to(DEV)
 
 
-def test_patched_encoder_matches_the_framework_encoder_under_autocast(monkeypatch):
-    from openpystruct_amd import tfd_fused as TF, train
-    monkeypatch.setattr(train, "_SPLIT_WGRAD_ROWS", 512)      # 448 rows through the LIBRARY products (r04's default sends them to the split-row kernel: next test)
-    enc = _encoder()
-    ref = copy.deepcopy(enc)
-    params = list(enc.parameters())
+def _shadowed(module, lr=1e-3):
+    """Every `.grad` of `module` a view of one flat buffer and its Linear maps on the optimiser's bf16 shadow products (as train._setup_step
+    leaves a model): (flat, opt, stash, dst, patched)."""
+    from openpystruct_amd import train
+    params = list(module.parameters())
     flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
     off = 0
     for q in params:
         q.grad = flat[off:off + q.numel()].view_as(q)
         off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(enc, opt, params, flat)
+    opt = train.FlatClipAdam(params, flat, lr)
+    return (flat, opt) + tuple(train.enable_shadow_linears(module, opt, params, flat))
+
+
+def test_patched_encoder_matches_the_framework_encoder_under_autocast(monkeypatch):
+    from openpystruct_amd import tfd_fused as TF, train
+    monkeypatch.setattr(train, "_SPLIT_WGRAD_ROWS", 512)      # 448 rows through the LIBRARY products (r04's default sends them to the split-row kernel: next test)
+    enc = _encoder()
+    ref = copy.deepcopy(enc)
+    flat, opt, stash, dst, patched = _shadowed(enc)
     assert TF.patch_encoder(enc, seed=11, direct_param_grads=True)
     g = torch.Generator().manual_seed(2)
     x = torch.randn(64, 7, 120, generator=g).to(DEV).requires_grad_()
     w = torch.randn(64, 7, 120, generator=g).to(DEV)
     enc.train(); ref.train()
     flat.zero_()
-    with torch.autocast("cuda", dtype=torch.bfloat16):
+    with train.grouped_wgrads(torch.device(DEV), stash, dst, enabled=False), torch.autocast("cuda", dtype=torch.bfloat16):
         out = enc(x)
         (out * w).sum().backward()
-    live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-    assert len(live) == len(dst)                                        # every registered product ran (448 rows: the library path)
-    torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
+        assert all(ss is not None for ss in stash) and len(stash) == len(dst)      # every registered product ran (448 rows: the library path)
     xr = x.detach().clone().requires_grad_()
     with torch.autocast("cuda", dtype=torch.bfloat16):
         outr = ref(xr)
@@ -204,14 +209,7 @@ def test_patched_encoder_with_thousands_of_rows_takes_the_split_row_gradient_pat
     from openpystruct_amd import tfd_fused as TF, train
     enc = _encoder(seed=3)
     ref = copy.deepcopy(enc)
-    params = list(enc.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(enc, opt, params, flat)
+    flat, opt, stash, dst, patched = _shadowed(enc)
     assert TF.patch_encoder(enc, seed=12, direct_param_grads=True)
     g = torch.Generator().manual_seed(4)
     x = torch.randn(512, 7, 120, generator=g).to(DEV).requires_grad_()
@@ -283,14 +281,7 @@ def test_patched_model_matches_the_module_with_the_same_noise(monkeypatch, draw)
     torch.manual_seed(5)
     model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=0.0).to(DEV)
     ref = copy.deepcopy(model)
-    params = list(model.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+    flat, opt, stash, dst, patched = _shadowed(model)
     assert TF.patch_model(model, seed=3, direct_param_grads=True) and "forward" in model.__dict__
     B = 512
     g = torch.Generator().manual_seed(6)
@@ -313,12 +304,9 @@ def test_patched_model_matches_the_module_with_the_same_noise(monkeypatch, draw)
     monkeypatch.setattr(torch, "randint", fake_randint)
     monkeypatch.setattr(torch, "randn_like", fake_randn_like)
     model.train(); ref.train()
-    with torch.autocast("cuda", dtype=torch.bfloat16):
+    with train.grouped_wgrads(torch.device(DEV), stash, dst, enabled=False), torch.autocast("cuda", dtype=torch.bfloat16):
         out = model(x)
         (out.float() * w).sum().backward()
-    live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-    if live:
-        torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
     if draw:
         t_k, e_k = model.transformer_encoder._ops_dropout_state[x.device].draws
         assert int(t_k.min()) >= 0 and int(t_k.max()) < model.diffusion.T and abs(float(e_k.mean())) < 0.01 and abs(float(e_k.std()) - 1.0) < 0.01
@@ -343,14 +331,7 @@ def test_head_dropout_mask_is_redrawn_every_step_and_every_graph_replay():
     torch.manual_seed(5)
     model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=0.0).to(DEV)
     model.dropout.p = 0.5
-    params = list(model.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+    flat, opt, stash, dst, patched = _shadowed(model)
     assert TF.patch_model(model, seed=3, direct_param_grads=True)
     model.fc2 = nn.Identity()
     model.train()
@@ -395,29 +376,16 @@ def test_one_launch_layer_forward_equals_the_eight_launch_form(monkeypatch, B, p
         monkeypatch.setattr(TF, "LAYER_BWD", layer_bwd)
         torch.manual_seed(5)
         model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=p).to(DEV)
-        params = list(model.parameters())
-        flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-        off = 0
-        for q in params:
-            q.grad = flat[off:off + q.numel()].view_as(q)
-            off += q.numel()
-        opt = train.FlatClipAdam(params, flat, 1e-3)
-        stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+        flat, opt, stash, dst, patched = _shadowed(model)
         assert TF.patch_model(model, seed=3, direct_param_grads=True)
         model.train()
         g = torch.Generator().manual_seed(6)
         x = torch.randn(B, 6, 120, generator=g).to(DEV)
         w = torch.randn(B, 100, generator=g).to(DEV) / B
         torch.manual_seed(11)                                   # the same diffusion steps / noise in both runs
-        train._WGRAD_QUEUE = []
-        with torch.autocast("cuda", dtype=torch.bfloat16):
+        with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
             out = model(x)
             (out.float() * w).sum().backward()
-        train.flush_wgrad_queue(torch.device(DEV))
-        train._WGRAD_QUEUE = None
-        live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-        if live:
-            torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
         torch.cuda.synchronize()
         res = out.float().clone(), {n: q.grad.clone() for n, q in model.named_parameters()}
         train.disable_shadow_linears(patched)
@@ -448,31 +416,19 @@ def test_two_layers_in_one_launch_equal_the_two_launches(monkeypatch, B, p, laye
         monkeypatch.setattr(TF, "LAYER_PAIR_BWD", pair_bwd)
         torch.manual_seed(5)
         model = ModelOnePassTransformerWithDiffusion(6, 120, 100, num_transformer_layers=layers, dropout=p).to(DEV)
-        params = list(model.parameters())
-        flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-        off = 0
-        for q in params:
-            q.grad = flat[off:off + q.numel()].view_as(q)
-            off += q.numel()
-        opt = train.FlatClipAdam(params, flat, 1e-3)
-        stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+        flat, opt, stash, dst, patched = _shadowed(model)
         assert TF.patch_model(model, seed=3, direct_param_grads=True)
         model.train()
         g = torch.Generator().manual_seed(6)
         x = torch.randn(B, 6, 120, generator=g).to(DEV)
         w = torch.randn(B, 100, generator=g).to(DEV) / B
         torch.manual_seed(11)
-        train._WGRAD_QUEUE = []
-        with torch.autocast("cuda", dtype=torch.bfloat16):
+        with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
             out = model(x)
             (out.float() * w).sum().backward()
-        train.flush_wgrad_queue(torch.device(DEV))
-        train._WGRAD_QUEUE = None
-        live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-        if live:
-            torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
         torch.cuda.synchronize()
-        assert TF._PENDING_LAYER is None and TF._PENDING_BWD is None
+        st = model.transformer_encoder._ops_dropout_state[x.device]
+        assert st.pending_layer is None and st.pending_bwd is None
         res = out.float().clone(), flat.clone()
         train.disable_shadow_linears(patched)
         TF.unpatch_model(model)
@@ -538,41 +494,29 @@ def test_loss_on_the_head_tile_equals_the_loss_launch(monkeypatch, B, p, alpha0,
         torch.manual_seed(5)
         model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=p).to(DEV)
         crit = TrainableL1L2Loss(0.5, torch.tensor(-1.0, device=DEV), torch.tensor(0.4, device=DEV), 0.5).to(DEV)
-        params = list(model.parameters())
-        flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-        off = 0
-        for q in params:
-            q.grad = flat[off:off + q.numel()].view_as(q)
-            off += q.numel()
-        opt = train.FlatClipAdam(params, flat, 1e-3)
-        stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+        flat, opt, stash, dst, patched = _shadowed(model)
         assert TF.patch_model(model, seed=3, direct_param_grads=True)
         model.train()
         g = torch.Generator().manual_seed(6)
         x = torch.randn(B, 6, 120, generator=g).to(DEV)
         y = torch.randn(B, 100, generator=g).to(DEV)
         acc = torch.full((), 2.0, device=DEV)
-        train._WGRAD_QUEUE = []
-        with torch.autocast("cuda", dtype=torch.bfloat16):
-            if on_tile:
-                assert TF.arm_head_loss(y, crit, alpha0, acc)
-                out = model(x)
-                loss = TF.take_head_loss()
-                assert loss is not None and TF.take_head_loss() is None
-            else:
-                out = model(x)
-                loss = fused_loss(crit, out, y, alpha0=alpha0, unit_grad=True, acc=acc)
-            term = None
-            if second:
-                term = 0.03 * (out * torch.linspace(-1.0, 2.0, 100, device=DEV).to(out.dtype)).sum().float()
-                # (the tile's loss value exists once the head's BACKWARD launch has run: the terms are tied, not added, as train.py ties them)
-                loss = train._TieTerms.apply(loss, term) if on_tile else loss + term
-        loss.backward(gradient=torch.ones((), device=DEV))
-        train.flush_wgrad_queue(torch.device(DEV))
-        train._WGRAD_QUEUE = None
-        live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-        if live:
-            torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
+        with train.grouped_wgrads(torch.device(DEV), stash, dst):
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                if on_tile:
+                    assert TF.arm_head_loss(model, y, crit, alpha0, acc)
+                    out = model(x)
+                    loss = TF.take_head_loss(model)
+                    assert loss is not None and TF.take_head_loss(model) is None
+                else:
+                    out = model(x)
+                    loss = fused_loss(crit, out, y, alpha0=alpha0, unit_grad=True, acc=acc)
+                term = None
+                if second:
+                    term = 0.03 * (out * torch.linspace(-1.0, 2.0, 100, device=DEV).to(out.dtype)).sum().float()
+                    # (the tile's loss value exists once the head's BACKWARD launch has run: the terms are tied, not added, as train.py ties them)
+                    loss = train._TieTerms.apply(loss, term) if on_tile else loss + term
+            loss.backward(gradient=torch.ones((), device=DEV))
         torch.cuda.synchronize()
         res = float(loss) + (float(term) if (second and on_tile) else 0.0), float(acc), out.float().clone(), flat.clone()
         train.disable_shadow_linears(patched)
@@ -586,6 +530,55 @@ def test_loss_on_the_head_tile_equals_the_loss_launch(monkeypatch, B, p, alpha0,
     if not second:
         assert abs((a1 - 2.0) - l1) <= 1e-6 * abs(l1)
     assert float((g0 - g1).norm() / g0.norm()) < 1e-5 and float(g0.abs().max()) > 0
+
+
+def test_two_models_do_not_take_each_others_head_loss():
+    """The armed loss belongs to ONE model's state: a training forward of model B between `arm_head_loss(A, ...)` and `A(x)` (a second
+    model's pass inside the step, e.g. a validation model) neither computes A's loss on its own tile nor leaves A without one.  B = 3
+    samples: 21 rows (the split-row threshold is 16), one 16-sample head workgroup.  Outputs bit-equal to a run in which A is armed only
+    after B's pass, A's loss to the bound of test_loss_on_the_head_tile_equals_the_loss_launch.  (With the spec in a module global, as it
+    was, B's head took it -- same target shape -- and A's step fell back to the loss launches: this test failed there.)"""
+    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion, TrainableL1L2Loss
+    B = 3
+    g = torch.Generator().manual_seed(6)
+    xa, xb = torch.randn(B, 6, 120, generator=g).to(DEV), torch.randn(B, 6, 120, generator=g).to(DEV)
+    y = torch.randn(B, 100, generator=g).to(DEV)
+
+    def run(arm_before_b):
+        models = []
+        for seed in (5, 7):
+            torch.manual_seed(seed)
+            model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=0.1).to(DEV)
+            flat, opt, stash, dst, patched = _shadowed(model)
+            assert TF.patch_model(model, seed=seed, direct_param_grads=True)
+            models.append((model.train(), stash, dst, patched))
+        (ma, stash, dst, _), (mb, _, _, _) = models
+        crit = TrainableL1L2Loss(0.5, torch.tensor(-1.0, device=DEV), torch.tensor(0.4, device=DEV), 0.5).to(DEV)
+        acc = torch.zeros((), device=DEV)
+        with train.grouped_wgrads(torch.device(DEV), stash, dst):
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                if arm_before_b:
+                    assert TF.arm_head_loss(ma, y, crit, 0.5, acc)
+                out_b = mb(xb)
+                loss_b = TF.take_head_loss(mb)
+                if not arm_before_b:
+                    assert TF.arm_head_loss(ma, y, crit, 0.5, acc)
+                out_a = ma(xa)
+                loss_a = TF.take_head_loss(ma)
+            assert loss_b is None and loss_a is not None
+            loss_a.backward(gradient=torch.ones((), device=DEV))        # (the head's backward launch finishes the value)
+        torch.cuda.synchronize()
+        res = out_a.float().clone(), out_b.float().clone(), float(loss_a)
+        for model, _, _, patched in models:
+            train.disable_shadow_linears(patched)
+            TF.unpatch_model(model)
+        return res
+
+    a0, b0, l0 = run(False)
+    a1, b1, l1 = run(True)
+    assert torch.equal(b1, b0) and torch.equal(a1, a0) and float(a0.abs().max()) > 0 and float(b0.abs().max()) > 0
+    assert np.isfinite(l0) and l0 > 0 and abs(l1 - l0) <= 2e-6 * abs(l0)
 
 
 def test_four_layer_encoder_keeps_training_on_fresh_weights(monkeypatch):
@@ -603,14 +596,7 @@ def test_four_layer_encoder_keeps_training_on_fresh_weights(monkeypatch):
         monkeypatch.setattr(TF, "LAYER_BWD", layer_fwd)
         torch.manual_seed(5)
         model = ModelOnePassTransformerWithDiffusion(6, 120, 100, num_transformer_layers=4, dropout=0.1).to(DEV)
-        params = list(model.parameters())
-        flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-        off = 0
-        for q in params:
-            q.grad = flat[off:off + q.numel()].view_as(q)
-            off += q.numel()
-        opt = train.FlatClipAdam(params, flat, 1e-2)
-        stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+        flat, opt, stash, dst, patched = _shadowed(model, 1e-2)
         assert TF.patch_model(model, seed=3, direct_param_grads=True)
         opt.repack = getattr(model.transformer_encoder, "_ops_tile_entries", None)
         if layer_fwd:
@@ -624,15 +610,9 @@ def test_four_layer_encoder_keeps_training_on_fresh_weights(monkeypatch):
         for step in range(4):
             flat.zero_()
             torch.manual_seed(11 + step)
-            train._WGRAD_QUEUE = []
-            with torch.autocast("cuda", dtype=torch.bfloat16):
+            with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
                 out = model(x)
                 (out.float() * w).sum().backward()
-            train.flush_wgrad_queue(torch.device(DEV))
-            train._WGRAD_QUEUE = None
-            live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-            if live:
-                torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
             outs.append(out.float().clone())
             opt.step()
         torch.cuda.synchronize()
@@ -709,7 +689,8 @@ def test_front_end_assembling_its_own_batch_reproduces_the_assembly_launch(monke
         monkeypatch.setattr(tfd_fused, "FRONT_GATHER", fused)
         out = train.train_surrogate("tfd", tfd_data, device="cuda", max_epochs=4, seed=3, batch_order=batch_order)
         hist[fused] = out["history"]
-        assert tfd_fused._GATHER is None                     # disarmed at the end of the run
+        # no fast-path state is left on the returned model, so nothing armed either
+        assert not hasattr(out["model"].transformer_encoder, "_ops_dropout_state")
     for key in ("train", "val"):
         a, b = np.array(hist[True][key]), np.array(hist[False][key])
         assert np.all(np.isfinite(a)) and np.abs(a / b - 1.0).max() < 2e-3, (key, a, b)
@@ -818,14 +799,7 @@ def test_fast_path_gradients_against_float64_autograd(monkeypatch, B, cfg):
     cfg = cfg or dict(n_cases=6, feat_dim=120, n_elem=100)         # default: the reference's sizes; the others: other tile counts / head widths
     model = ModelOnePassTransformerWithDiffusion(dropout=0.0, **cfg).to(DEV)
     ref = copy.deepcopy(model).double()
-    params = list(model.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+    flat, opt, stash, dst, patched = _shadowed(model)
     assert TF.patch_model(model, seed=3, direct_param_grads=True)
     st_probe = TF._State(torch.device(DEV), 1, True)
     assert TF._front_fused_ok(model, st_probe, cfg["feat_dim"]) and TF._head_fused_ok(model, st_probe, cfg["feat_dim"])     # the one-launch blocks are what runs
@@ -834,15 +808,9 @@ def test_fast_path_gradients_against_float64_autograd(monkeypatch, B, cfg):
     x = torch.randn(B, cfg["n_cases"], cfg["feat_dim"], generator=g).to(DEV)
     w = torch.randn(B, cfg["n_elem"], generator=g).to(DEV) / B
     model.train(); ref.train()
-    train._WGRAD_QUEUE = []
-    with torch.autocast("cuda", dtype=torch.bfloat16):
+    with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
         out = model(x)
         (out.float() * w).sum().backward()
-    train.flush_wgrad_queue(torch.device(DEV))
-    train._WGRAD_QUEUE = None
-    live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-    if live:
-        torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
     t_k, e_k = model.transformer_encoder._ops_dropout_state[x.device].draws
     monkeypatch.setattr(torch, "randint", lambda lo, hi, size, device=None, **kw: t_k)
     monkeypatch.setattr(torch, "randn_like", lambda t, **kw: e_k.to(t.dtype))
@@ -902,14 +870,7 @@ def test_fast_path_gradients_of_a_smooth_network_match_float64(monkeypatch, B):
         layer.activation = lambda t: t
         layer.activation_relu_or_gelu = 0
     ref.diffusion.mlp[1] = torch.nn.Identity()
-    params = list(model.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+    flat, opt, stash, dst, patched = _shadowed(model)
     assert TF.patch_model(model, seed=3, direct_param_grads=True)
     st_probe = TF._State(torch.device(DEV), 1, True)
     assert TF._front_fused_ok(model, st_probe, 120) and TF._head_fused_ok(model, st_probe, 120)
@@ -918,15 +879,9 @@ def test_fast_path_gradients_of_a_smooth_network_match_float64(monkeypatch, B):
     x = torch.randn(B, 6, 120, generator=g).to(DEV)
     w = torch.randn(B, 100, generator=g).to(DEV) / B
     model.train(); ref.train()
-    train._WGRAD_QUEUE = []
-    with torch.autocast("cuda", dtype=torch.bfloat16):
+    with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
         out = model(x)
         (out.float() * w).sum().backward()
-    train.flush_wgrad_queue(torch.device(DEV))
-    train._WGRAD_QUEUE = None
-    live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]
-    if live:
-        torch._foreach_copy_([a for a, _ in live], [b for _, b in live])
     t_k, e_k = model.transformer_encoder._ops_dropout_state[x.device].draws
     monkeypatch.setattr(torch, "randint", lambda lo, hi, size, device=None, **kw: t_k)
     monkeypatch.setattr(torch, "randn_like", lambda t, **kw: e_k.to(t.dtype))
@@ -1162,14 +1117,7 @@ def test_evaluation_pass_through_the_one_launch_kernels_equals_the_module(monkey
     torch.manual_seed(5)
     model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=0.1).to(DEV)
     ref = copy.deepcopy(model)
-    params = list(model.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+    flat, opt, stash, dst, patched = _shadowed(model)
     assert TF.patch_model(model, seed=3, direct_param_grads=True)
     x = torch.randn(200, 6, 120, generator=torch.Generator().manual_seed(6)).to(DEV)
     model.eval(); ref.eval()

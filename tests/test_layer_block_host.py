@@ -44,3 +44,27 @@ def test_tfd_patch_needs_the_shadow_products():
     m.eval()
     with torch.no_grad():
         assert m(x).shape == (3, 100)
+
+
+def test_the_collecting_step_exists_only_inside_its_context_and_runs_a_waiting_launch_once():
+    """train.grouped_wgrads is the one place that sets the collecting step: it exists inside the block, is gone after it -- after an exception
+    too -- and a launch that waits for the flush (tfd_fused: a deferred layer backward) runs exactly once on a clean exit, while the step is
+    still the collecting one, and not at all when the body raised.  (Nothing is queued: the grouped flush itself launches nothing.)"""
+    import pytest
+    from openpystruct_amd import train
+    cpu, ran = torch.device("cpu"), []
+    assert train._WGRAD_QUEUE is None
+    stash, dst = [torch.ones(3), None], [torch.zeros(3), torch.zeros(2)]
+    with train.grouped_wgrads(cpu, stash, dst) as step:
+        assert step is train._WGRAD_QUEUE and step is not None and len(step) == 0
+        train.run_before_wgrad_flush(lambda: ran.append(train._WGRAD_QUEUE is step))
+        assert ran == []
+    assert ran == [True] and train._WGRAD_QUEUE is None
+    assert torch.equal(dst[0], torch.ones(3)) and stash == [None, None]          # the live stash entry moved, the stash cleared
+    with pytest.raises(ZeroDivisionError):
+        with train.grouped_wgrads(cpu, stash, dst):
+            train.run_before_wgrad_flush(lambda: ran.append("after an exception"))
+            1 / 0
+    assert ran == [True] and train._WGRAD_QUEUE is None
+    with train.grouped_wgrads(cpu, stash, dst, enabled=False) as step:            # not collecting: products launch inside backward
+        assert step is None and train._WGRAD_QUEUE is None
