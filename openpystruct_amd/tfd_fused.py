@@ -9,10 +9,10 @@ whose forward and backward are one launch each (r03):
     HeadFn           fc1 -> LayerNorm -> ReLU -> dropout -> fc2 on the [CLS] rows
 
 on fragment-tiled bf16 weight copies (enable_layer_tiles; rebuilt behind every Adam update) -- 16 kernel nodes per captured training
-step where the framework's modules need ~260.  Weight / bias gradients leave through train.shadow_param_grads (one grouped split-row
+step where the framework's modules need ~260.  Weight / bias gradients leave through shadow.shadow_param_grads (one grouped split-row
 launch per step).  Evaluation passes without gradients run the same launches with every dropout probability 0.  Blocks whose sizes do
 not fit the one-launch kernels fall back to the r02 form: the separate launches of csrc/seq_block.hip (attention, dropout + add +
-LayerNorm, ReLU + dropout, diffusion noise / combine) between the optimiser's bf16 shadow products (train._ShadowLinearFn); masks,
+LayerNorm, ReLU + dropout, diffusion noise / combine) between the optimiser's bf16 shadow products (shadow._ShadowLinearFn); masks,
 other activations, CPU: the framework's own forward.
 """
 from __future__ import annotations
@@ -25,7 +25,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _cabi, switches
+from . import _cabi, shadow, switches
 
 ENABLED = switches.get("tfd_fast_encoder") == "1"      # A/B switch: 0 = nn.TransformerEncoder's own forward
 LAYER_FWD = switches.get("tfd_layer_fwd") == "1"       # A/B switch: 0 = eight launches per layer forward instead of one
@@ -122,7 +122,7 @@ def _grads_are_flat_views(*params) -> bool:
 
 
 def _shadow_recs(mods, names=None):
-    """The shadow records (train.ShadowRec) of the modules' products `names` (default: each one's `_ops_prod`), every one with a bias --
+    """The shadow records (shadow.ShadowRec) of the modules' products `names` (default: each one's `_ops_prod`), every one with a bias --
     or None when a product is not registered."""
     recs = [getattr(getattr(m, n, None), "rec", None) for m, n in zip(mods, names or ("_ops_prod",) * len(mods))]
     return recs if all(r is not None and r.b_sh is not None for r in recs) else None
@@ -263,7 +263,7 @@ LAYER_PAIR_BWD = switches.get("tfd_layer_pair_bwd") == "1"  # ... and their back
 
 def _launch_pending_bwd(st: _State) -> None:
     """Launch a deferred backward pass whose predecessor never came (a first layer whose inputs need no gradient).  Handed to the step
-    that collects the weight gradients (train.run_before_wgrad_flush), which runs it in front of its grouped launches."""
+    that collects the weight gradients (shadow.run_before_wgrad_flush), which runs it in front of its grouped launches."""
     if st.pending_bwd is not None:
         pb, pdx, _keep = st.pending_bwd
         st.pending_bwd = None
@@ -277,7 +277,7 @@ class EncoderLayerFn(torch.autograd.Function):
     LayerNorm, feed-forward, dropout + add + LayerNorm; bf16 MFMA products on the shadow weights, everything else as the separate
     launches compute it, same dropout streams).  Backward: the launches of csrc/seq_block.hip and the library's input-gradient products,
     driven from here in the order autograd would run them; weight / bias gradients go where the shadow products send them
-    (train.shadow_param_grads), LayerNorm gradients straight into their `.grad` (the caller zeroes the flat buffer every step).
+    (shadow.shadow_param_grads), LayerNorm gradients straight into their `.grad` (the caller zeroes the flat buffer every step).
     Inputs (x32, x16): the residual stream and its bf16 copy (the previous block's two outputs; x16's VALUES are bf16(x32)), so that
     the two input gradients travel separately and no add node is needed."""
 
@@ -335,7 +335,6 @@ class EncoderLayerFn(torch.autograd.Function):
     def backward(ctx, g32, g16):
         if g32 is None and g16 is None:
             return (None,) * 8
-        from . import train
         lib = _cabi.load()
         x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2 = ctx.saved_tensors
         layer, Bn, S, H, dh, d, ff, ps, seeds, used, (rin, rout, r1, r2), st = ctx.cfg
@@ -364,7 +363,7 @@ class EncoderLayerFn(torch.autograd.Function):
                     dgamma2=layer.norm2.weight.grad.data_ptr(), dbeta2=layer.norm2.bias.grad.data_ptr())
                 nwg = (Bn + (16 // S) - 1) // (16 // S)
                 part = None
-                if train._WGRAD_QUEUE is not None and LN_PARTIALS:
+                if shadow.collecting() and LN_PARTIALS:
                     # LayerNorm gamma / beta gradients: per-workgroup column sums, reduced by four jobs of the grouped weight-gradient launch
                     part = torch.empty((nwg, 4, 128), **f32)
                     a.ln_part = part.data_ptr()
@@ -375,44 +374,44 @@ class EncoderLayerFn(torch.autograd.Function):
                 if st.pending_bwd is not None:
                     pb, pdx, _keep = st.pending_bwd
                     st.pending_bwd = None
-                    train.run_before_wgrad_flush(None)
+                    shadow.run_before_wgrad_flush(None)
                     if g32 is not None and g16 is None and pdx.data_ptr() == g32.data_ptr() and _TRACE_BWD is None:
                         _cabi.check(lib.ops_tfd_encoder_layer_pair_bwd(ctypes.byref(pb), ctypes.byref(a), s), "ops_tfd_encoder_layer_pair_bwd")
                     else:                        # (not the successor's gradient after all: the two launches)
                         _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(pb), s), "ops_tfd_encoder_layer_bwd")
                         _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
-                elif (LAYER_PAIR_BWD and ctx.pair_later and _TRACE_BWD is None and train._WGRAD_QUEUE is not None      # (queue mode: a flush follows)
-                      and all(train.shadow_grads_are_deferred(r, T) for r in (r2, r1, rout, rin))):
+                elif (LAYER_PAIR_BWD and ctx.pair_later and _TRACE_BWD is None and shadow.collecting()      # (queue mode: a flush follows)
+                      and all(shadow.shadow_grads_are_deferred(r, T) for r in (r2, r1, rout, rin))):
                     # (only when the four weight-gradient registrations below merely QUEUE: a product the library runs at once -- fewer rows
                     #  than one MFMA tile, e.g. a one- or two-sample tail batch, or OPS_AMD_SPLIT_WGRAD_ROWS=0 -- would read d_f / d_u / d_a /
                     #  dqkv before the waiting launch has written them)
                     # the predecessor's backward call -- the next node autograd runs: this layer's inputs are its two outputs -- launches both
                     # (the saved tensors too: autograd releases them when this call returns, before the launch that reads them)
                     st.pending_bwd = (a, dx32, (g32, g16, d_f, d_u, d_a, dqkv, part, x16, qkv, ctxa, z1, mean1, rstd1, y1_16, u, h, z2, mean2, rstd2))
-                    train.run_before_wgrad_flush(functools.partial(_launch_pending_bwd, st))     # ... or, if it never comes, the step's flush
+                    shadow.run_before_wgrad_flush(functools.partial(_launch_pending_bwd, st))     # ... or, if it never comes, the step's flush
                 else:
                     _cabi.check(lib.ops_tfd_encoder_layer_bwd(ctypes.byref(a), s), "ops_tfd_encoder_layer_bwd")
                 if part is not None:
                     flatp = part.view(nwg, 512)
                     for k, q in enumerate((layer.norm2.weight, layer.norm2.bias, layer.norm1.weight, layer.norm1.bias)):
-                        ok = train.queue_column_sums(flatp[:, 128 * k:128 * k + d], q.grad)
+                        ok = shadow.queue_column_sums(flatp[:, 128 * k:128 * k + d], q.grad)
                         assert ok
-                train.shadow_param_grads(r2, d_f, h)
-                train.shadow_param_grads(r1, d_u, y1_16)
-                train.shadow_param_grads(rout, d_a, ctxa)
-                train.shadow_param_grads(rin, dqkv, x16)
+                shadow.shadow_param_grads(r2, d_f, h)
+                shadow.shadow_param_grads(r1, d_u, y1_16)
+                shadow.shadow_param_grads(rout, d_a, ctxa)
+                shadow.shadow_param_grads(rin, dqkv, x16)
                 return dx32, None, None, None, None, None, None, None
             # LayerNorm2 <- (g32, g16)
             n1, n2 = layer.norm1, layer.norm2
             d_f, dres2 = _dropout_add_layernorm_bwd(g32, g16, z2, mean2, rstd2, n2.weight, (ps[3], seeds[3], used), n2.weight.grad, n2.bias.grad)
-            train.shadow_param_grads(r2, d_f, h)
+            shadow.shadow_param_grads(r2, d_f, h)
             d_u = _act_dropout_bwd(u, d_f @ r2.w_sh, 0.0, (ps[2], seeds[2], used))
-            train.shadow_param_grads(r1, d_u, y1_16)
+            shadow.shadow_param_grads(r1, d_u, y1_16)
             # LayerNorm1 <- (dres2, d_y1)
             d_a, dres1 = _dropout_add_layernorm_bwd(dres2, d_u @ r1.w_sh, z1, mean1, rstd1, n1.weight, (ps[1], seeds[1], used), n1.weight.grad, n1.bias.grad)
-            train.shadow_param_grads(rout, d_a, ctxa)
+            shadow.shadow_param_grads(rout, d_a, ctxa)
             dqkv = _attention_bwd(qkv, d_a @ rout.w_sh, Bn, S, H, dh, (ps[0], seeds[0], used))
-            train.shadow_param_grads(rin, dqkv, x16)
+            shadow.shadow_param_grads(rin, dqkv, x16)
             d_x16 = dqkv @ rin.w_sh
         return dres1, d_x16, None, None, None, None, None, None
 
@@ -678,7 +677,6 @@ class FrontFn(torch.autograd.Function):
     def backward(ctx, g, g16):
         if g is None and g16 is None:
             return None, None, None, None
-        from . import train
         lib = _cabi.load()
         xn16, h, sa, sb = ctx.saved_tensors
         model, B, Nc, d, hid, st, (r0, r2) = ctx.cfg
@@ -693,8 +691,8 @@ class FrontFn(torch.autograd.Function):
                                   dcls=cls.grad.data_ptr())
         with torch.cuda.device(dev):
             _cabi.check(lib.ops_tfd_front_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_front_bwd")
-        train.shadow_param_grads(r2, dm_, h)
-        train.shadow_param_grads(r0, d_h, xn16)
+        shadow.shadow_param_grads(r2, dm_, h)
+        shadow.shadow_param_grads(r0, d_h, xn16)
         return None, None, None, None
 
 
@@ -766,7 +764,6 @@ class HeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, g_loss=None):
-        from . import train
         lib = _cabi.load()
         x16, a16, mean, rstd, h = ctx.saved_tensors
         model, B, S, d, hid, C, p, st, (r1, r2) = ctx.cfg
@@ -799,10 +796,10 @@ class HeadFn(torch.autograd.Function):
             _cabi.check(lib.ops_tfd_head_bwd(ctypes.byref(a), _stream(dev)), "ops_tfd_head_bwd")
         if part is not None:
             for k, q in enumerate((model.norm1.weight, model.norm1.bias)):
-                if not train.queue_column_sums(part[:, k, :], q.grad):
+                if not shadow.queue_column_sums(part[:, k, :], q.grad):
                     q.grad.add_(part[:, k, :].sum(0))
-        train.shadow_param_grads(r2, g, h)
-        train.shadow_param_grads(r1, d_a, x16.view(B, S, d)[:, 0, :])       # (row-strided operand: no copy of the [CLS] rows)
+        shadow.shadow_param_grads(r2, g, h)
+        shadow.shadow_param_grads(r1, d_a, x16.view(B, S, d)[:, 0, :])       # (row-strided operand: no copy of the [CLS] rows)
         return full, None, None, None, None, None
 
 
@@ -1005,7 +1002,7 @@ def unpatch_model(model: nn.Module) -> None:
 def patch_encoder(enc: nn.TransformerEncoder, seed: int, direct_param_grads: bool = False) -> bool:
     """Route `enc.forward` through the fast path whenever it applies (GPU, training, bf16 autocast, no masks, short sequences);
     anything else falls through to the framework's forward.  Needs the shadow products registered on every layer's attention
-    (train.enable_shadow_linears).  `direct_param_grads`: the caller zeroes every parameter's `.grad` before each backward pass (the
+    (shadow.enable_shadow_linears).  `direct_param_grads`: the caller zeroes every parameter's `.grad` before each backward pass (the
     training loop's flat buffer), so LayerNorm gradients may be assigned there.  Returns whether the encoder qualifies at all."""
     if not (ENABLED and type(enc) is nn.TransformerEncoder and all(_layer_ok(l) for l in enc.layers)):
         return False

@@ -26,7 +26,6 @@ the running statistics are averaged over ranks at the end of every epoch so that
 """
 from __future__ import annotations
 
-import contextlib
 import copy
 import os
 import sys
@@ -35,13 +34,14 @@ from dataclasses import dataclass
 from typing import Dict, Optional
 
 import torch
-
-from . import switches  # noqa: E402
 import torch.distributed as dist
 import torch.nn as nn
 from torch.optim.lr_scheduler import ExponentialLR
 
+from . import _cabi, switches
 from .dataprep import SurrogateData
+from .flat_adam import FlatClipAdam, flat_grads
+from .shadow import disable_shadow_linears, enable_shadow_linears, grouped_wgrads      # (functions only: shadow's two rebound globals have no copy here)
 from .surrogates import fused_loss, BayesianTransformerWithDiffusion, ChainGNN, CompositeLoss, FNO1dModel, FNNPlain, FNNWithResidual, ModelOnePassTransformerWithDiffusion, TrainableL1L2Loss
 
 
@@ -155,73 +155,6 @@ class FnnConfig:
     c: float = 1.0
 
 
-_FUSED_LOSS = switches.get("fused_loss") == "1"      # A/B switch: 0 = the nn.Module losses
-
-
-class FlatClipAdam:
-    """`clip_grad_norm_(params, max_norm)` + `torch.optim.Adam(lr, weight_decay)` as two HIP launches over flat buffers
-    (csrc/flat_adam.hip).  The parameters are re-homed into one flat float32 buffer (each `p.data` becomes a view of it),
-    next to the flat gradient buffer the training loop already all-reduces; `lr` and the step count are device scalars,
-    so a captured HIP graph follows the scheduler."""
-
-    def __init__(self, params, flat_grad: torch.Tensor, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 max_norm: float = 1.0, decoupled: bool = False):
-        from . import _cabi
-        self._cabi, self._lib = _cabi, _cabi.load()
-        dev = flat_grad.device
-        self.p = torch.empty_like(flat_grad)
-        off = 0
-        with torch.no_grad():
-            for q in params:
-                n = q.numel()
-                self.p[off:off + n].copy_(q.reshape(-1))
-                q.data = self.p[off:off + n].view_as(q)
-                off += n
-        assert off == flat_grad.numel()
-        self.g = flat_grad
-        self.m, self.v = torch.zeros_like(flat_grad), torch.zeros_like(flat_grad)
-        self.lr = torch.tensor(float(lr), dtype=torch.float32, device=dev)
-        self.step_count = torch.zeros((), dtype=torch.int32, device=dev)
-        self.ws = torch.empty(int(self._lib.ops_flat_adam_workspace_bytes()), dtype=torch.uint8, device=dev)
-        self.betas, self.eps, self.weight_decay, self.max_norm, self.decoupled = betas, eps, weight_decay, max_norm, decoupled
-        self.p_bf16: Optional[torch.Tensor] = None      # bfloat16 shadow of the parameters (enable_shadow)
-        self.zero_grads = False     # zero the gradient buffer inside the update launch (the next step's zero_grad(): one fill node less)
-        self.repack = None          # ctypes array of MlpRepackEntry: padded bf16 weight copies the update refreshes too (pinn_fused.py)
-        self.norm_ready_parts = 0   # > 0: the gradient producers leave that many norm partial sums + the advanced step in `ws` (pinn_fused.enable_norm)
-
-    def enable_shadow(self) -> torch.Tensor:
-        """A bfloat16 copy of the flat parameter buffer that every step refreshes in the Adam kernel itself: layers that
-        run their GEMMs in bfloat16 read it instead of casting their float32 weights in every forward pass."""
-        if self.p_bf16 is None:
-            self.p_bf16 = self.p.to(torch.bfloat16)
-        return self.p_bf16
-
-    def refresh_shadow(self) -> None:
-        if self.p_bf16 is not None:
-            self.p_bf16.copy_(self.p)
-
-    def step(self, grad_scale: float = 1.0) -> None:
-        dev = self.g.device
-        args = (self.g.numel(), self.p.data_ptr(), self.g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.lr.data_ptr(),
-                self.step_count.data_ptr(), self.max_norm, grad_scale, self.betas[0], self.betas[1], self.eps, self.weight_decay,
-                int(self.decoupled) | (2 if self.zero_grads else 0) | ((self._cabi.ADAM_NORM_READY | (self.norm_ready_parts << 16)) if self.norm_ready_parts else 0),
-                self.p_bf16.data_ptr() if self.p_bf16 is not None else None, self.ws.data_ptr())
-        with torch.cuda.device(dev):
-            s = torch.cuda.current_stream(dev).cuda_stream
-            if self.repack is not None:
-                rc = self._lib.ops_flat_clip_adam_step_repack_f32(*args, len(self.repack), self.repack, s)
-            else:
-                rc = self._lib.ops_flat_clip_adam_step_f32(*args, s)
-        if rc != self._cabi.OK:
-            raise RuntimeError(f"ops_flat_clip_adam_step_f32 failed with code {rc}")
-
-    def state_dict(self):
-        return {"m": self.m.clone(), "v": self.v.clone(), "step": self.step_count.clone(), "lr": self.lr.clone()}
-
-    def load_state_dict(self, sd) -> None:
-        self.m.copy_(sd["m"]); self.v.copy_(sd["v"]); self.step_count.copy_(sd["step"]); self.lr.copy_(sd["lr"])
-
-
 @dataclass
 class GnnConfig:
     """/root/reference/OpenPyStruct_GNN_MultiCase_Beta.py:38-55 (AdamW, no alpha term, :394, :437-446)."""
@@ -269,8 +202,59 @@ class FnoConfig:
     fno_width: int = 128
 
 
-_DEBUG_NAN = os.environ.get("OPS_AMD_DEBUG_NAN", "0") == "1"
+_FUSED_LOSS = switches.get("fused_loss") == "1"      # A/B switch: 0 = the nn.Module losses
+_SHADOW_LINEAR = switches.get("shadow_linear") == "1"   # A/B switch: 0 = nn.Linear under autocast
+_GROUP_WGRAD = switches.get("group_wgrad") == "1"    # A/B switch: 0 = one launch per product, inside backward
 _EXPLICIT_ROOT = switches.get("explicit_root") == "1"      # A/B switch: 0 = loss.backward() with its implicit ones_like() fill node
+_DEBUG_NAN = os.environ.get("OPS_AMD_DEBUG_NAN", "0") == "1"
+# data-parallel step (world > 1).  Default: [graph A: noise, forward, loss, backward] -> gradient all-reduce -> [graph B: average, clip,
+# Adam], the collective enqueued asynchronously (the host never blocks on it: `wait()` only orders the compute stream behind the
+# collective's) -- OPS_AMD_DP_ASYNC=0 is the plain blocking-call form, bit for bit the same arithmetic (tests/test_surrogates.py).
+# r06: under `nccl` the collective is captured too -- the whole step is ONE graph, one replay per step and no host work between its segments
+# (one-rank RCCL timing, profiles/r05_notes.md 6: PINN 137.5 us against 169.1 us for two graphs around an eager collective, TFD 191.3 / 219.8;
+# the same bits as the plain run).  A failure while capturing falls back to the two-graph form; a captured collective that goes wrong on
+# N > 1 ranks would hang at REPLAY, past every fallback, so the first replay runs under a timer that ends the rank with exit code 17
+# (OPS_AMD_DP_STALL_S seconds, default 120: the launcher then takes the job down; a fresh job may set OPS_AMD_DP_ONE_GRAPH=0 -- never a re-exec
+# from a process that holds the GPU).  OPS_AMD_DP_ONE_GRAPH=0: [graph A | all-reduce | graph B].
+_DP_ASYNC = os.environ.get("OPS_AMD_DP_ASYNC", "1") == "1"
+_DP_ONE_GRAPH = os.environ.get("OPS_AMD_DP_ONE_GRAPH", "1") == "1"
+_DP_STALL_S = float(os.environ.get("OPS_AMD_DP_STALL_S", "120"))
+_FORCE_DP = os.environ.get("OPS_AMD_FORCE_DP", "0") == "1"           # run the data-parallel branch with a one-rank process group too
+_DP_PROFILE = os.environ.get("OPS_AMD_DP_PROFILE", "0") == "1"       # HIP events around the step's segments, reported as out["dp_segments"]
+
+stall_hook = None     # callable(what) run by a firing _StallGuard just before the process ends
+
+
+class _StallGuard:
+    """`with _StallGuard(seconds, what):` -- if the block has not finished after `seconds`, the process ends with exit code 17 and a line on
+    stderr saying what stalled (a hung graph replay of a captured collective cannot be recovered inside the process)."""
+
+    def __init__(self, seconds: float, what: str):
+        self.seconds, self.what, self.timer = seconds, what, None
+
+    def _fire(self):
+        if stall_hook is not None:       # the caller's last words (bench.py: the FE record measured before the training part)
+            try:
+                stall_hook(self.what)
+            except Exception:
+                pass
+        sys.stderr.write(f"openpystruct_amd: {self.what} did not finish within {self.seconds:.0f} s -- ending this rank (exit 17); "
+                         f"run again with OPS_AMD_DP_ONE_GRAPH=0 for the two-graph step\n")
+        sys.stderr.flush()
+        os._exit(17)
+
+    def __enter__(self):
+        import threading
+        self.timer = threading.Timer(self.seconds, self._fire)
+        self.timer.daemon = True
+        self.timer.start()
+        return self
+
+    def __exit__(self, *exc):
+        self.timer.cancel()
+        return False
+
+
 _ROOT_ONES = {}
 
 
@@ -279,11 +263,6 @@ def _root_ones(device):
     if key not in _ROOT_ONES:
         _ROOT_ONES[key] = torch.ones((), dtype=torch.float32, device=device)
     return _ROOT_ONES[key]
-
-
-def _cabi_rows() -> int:
-    from . import _cabi
-    return _cabi.MLP_MAX_ROWS
 
 
 def clear_blas_workspaces() -> None:
@@ -321,300 +300,6 @@ def _debug_nan(model, opt, flat, s_loss, epoch, b, sX, sY):
                 idx = (~torch.isfinite(q.grad)).nonzero().flatten()[:40].tolist()
                 print("   ", n, tuple(q.shape), "non-finite at", idx, "values", q.grad.flatten()[idx[:6]].tolist(), flush=True)
         raise RuntimeError("non-finite value in the training step")
-
-
-class _ShadowLinearFn(torch.autograd.Function):
-    """y = x W^T + b with W, b taken from the optimiser's bfloat16 shadow (`rec`: ShadowRec); the weight / bias gradients are not
-    returned to autograd but go where `shadow_param_grads` sends them.  Same arithmetic as nn.Linear under bf16 autocast (bf16 operands,
-    fp32 accumulation, bf16 results), without its per-step kernels: weight cast, bias cast, gradient cast back and accumulate -- four
-    per parameter."""
-
-    @staticmethod
-    def forward(ctx, x, rec, anchor, gx_dest=None):
-        # `anchor` (the layer's float32 weight Parameter) is not read: it makes autograd record the node even when x
-        # needs no gradient (first layer); its own gradient slot stays None
-        # `gx_dest`: the backward pass writes the input gradient straight into it (a [rows, K] bfloat16 tensor, rows may be strided) instead of
-        # a fresh tensor: the Transformer-Diffusion head hands the [CLS] rows of a persistent zero tensor, and the row scatter that followed
-        # the product disappears from the step
-        w_sh, b_sh = rec.w_sh, rec.b_sh
-        xb = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
-        x2 = xb.reshape(-1, xb.shape[-1])
-        y = torch.addmm(b_sh, x2, w_sh.t()) if b_sh is not None else x2 @ w_sh.t()
-        ctx.save_for_backward(x2, w_sh)
-        ctx.rec, ctx.xshape, ctx.xdtype = rec, x.shape, x.dtype
-        ctx.gx_dest = gx_dest if (gx_dest is not None and switches.get("gx_dest") == "1") else None
-        return y.reshape(*x.shape[:-1], w_sh.shape[0])
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, w_sh = ctx.saved_tensors
-        g2 = gy.reshape(-1, gy.shape[-1])
-        if g2.dtype != torch.bfloat16:
-            g2 = g2.to(torch.bfloat16)
-        g2 = shadow_param_grads(ctx.rec, g2, x2, row_stride_switch=True)
-        gx = None
-        if ctx.needs_input_grad[0]:
-            dest = ctx.gx_dest
-            if dest is not None and dest.dtype == torch.bfloat16 and tuple(dest.shape) == (g2.shape[0], w_sh.shape[1]) and ctx.xdtype == torch.bfloat16:
-                gx = torch.mm(g2, w_sh, out=dest)
-            else:
-                gx = (g2 @ w_sh).reshape(ctx.xshape)
-                if gx.dtype != ctx.xdtype:
-                    gx = gx.to(ctx.xdtype)
-        return gx, None, None, None
-
-
-class ShadowRec:
-    """One shadow product's operands and gradient destinations (enable_shadow_linears): the weight / bias gradients leave (in bfloat16)
-    through `stash`, from where ONE multi-tensor copy moves all of them into the flat float32 gradient buffer -- or, for products over
-    many rows, are added straight into `w_grad` / `b_grad`, the parameters' slices of the zeroed flat gradient buffer."""
-    __slots__ = ("w_sh", "b_sh", "w_grad", "b_grad", "stash", "iw", "ib")
-
-    def __init__(self, w_sh, b_sh, w_grad, b_grad, stash, iw, ib):
-        self.w_sh, self.b_sh, self.w_grad, self.b_grad, self.stash, self.iw, self.ib = w_sh, b_sh, w_grad, b_grad, stash, iw, ib
-
-
-def queue_column_sums(rows: torch.Tensor, dest: torch.Tensor) -> bool:
-    """dest [N] (float32, a slice of the zeroed flat gradient buffer) += column sums of rows [T, N] (float32, unit column stride) as a job
-    of the step's grouped weight-gradient launch.  False when no grouped launch is being collected (the caller adds them itself)."""
-    if _WGRAD_QUEUE is None or rows.dtype != torch.float32 or rows.stride(1) != 1 or dest.dtype != torch.float32 or not dest.is_contiguous():
-        return False
-    _WGRAD_QUEUE.append((rows, None, dest, None))
-    return True
-
-
-def shadow_param_grads(rec: ShadowRec, g2: torch.Tensor, x2: torch.Tensor, row_stride_switch: bool = False) -> torch.Tensor:
-    """Weight / bias gradients of y = x W^T + b given dY = g2 [T, N] and X = x2 [T, K] (bfloat16) -- the one statement of the protocol,
-    for _ShadowLinearFn.backward and for the fused blocks that run the product themselves: queued for the step's grouped split-row launch
-    (launched at once where no step collects) when the product has many rows, the library's product into the stash otherwise.
-    `row_stride_switch`: a row-strided x2 travels without a copy only with the switch wgrad_rows on (the autograd path; the fused blocks
-    always hand theirs over as it is).  Returns dY as it was used (made contiguous on the split-row path)."""
-    if rec.w_grad is not None and x2.shape[0] >= _SPLIT_WGRAD_ROWS and _SPLIT_WGRAD_ROWS > 0:
-        # many rows, small output: the library walks all rows inside a handful of tiles (25 us for 3584 x 360 x 120) and the bias
-        # gradient is another reduction pass (11 us); the split-row kernel of csrc/seq_block.hip adds partial tiles -- and the
-        # column sums of the slabs it reads anyway -- into the float32 gradients itself
-        from . import _cabi
-        g2 = g2.contiguous()
-        rows_ok = ((not row_stride_switch or switches.get("wgrad_rows") == "1") and _WGRAD_QUEUE is not None and x2.dim() == 2
-                   and x2.stride(1) == 1 and x2.stride(0) >= x2.shape[1])
-        x2c = x2 if rows_ok else x2.contiguous()          # the grouped launch takes row strides (the head reads the [CLS] rows in place)
-        fused_bias = rec.ib is not None and rec.b_grad is not None
-        if _WGRAD_QUEUE is not None:
-            # deferred: the training step launches every queued product at once after backward (flush_wgrad_queue)
-            _WGRAD_QUEUE.append((g2, x2c, rec.w_grad, rec.b_grad if fused_bias else None))
-        else:
-            with torch.cuda.device(g2.device):
-                rc = _cabi.load().ops_linear_wgrad_accumulate(x2c.shape[0], g2.shape[1], x2c.shape[1], g2.data_ptr(), x2c.data_ptr(),
-                                                              rec.w_grad.data_ptr(), rec.b_grad.data_ptr() if fused_bias else None,
-                                                              torch.cuda.current_stream(g2.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"ops_linear_wgrad_accumulate failed with code {rc}")
-        if rec.ib is not None and not fused_bias:
-            rec.stash[rec.ib] = g2.sum(0)
-    else:
-        rec.stash[rec.iw] = g2.t() @ x2
-        if rec.ib is not None:
-            rec.stash[rec.ib] = g2.sum(0)
-    return g2
-
-
-def shadow_grads_are_deferred(rec: ShadowRec, rows: int) -> bool:
-    """True when `shadow_param_grads(rec, g2, x2)` over `rows` rows only QUEUES its work for the step's grouped launch -- it then reads
-    neither operand before `flush_wgrad_queue`.  A caller whose kernel has not yet written g2 (tfd_fused: the later layer of a
-    pair launch) may only wait in that case: the library products and column sums of the other branches run at once."""
-    return (_WGRAD_QUEUE is not None and rec.w_grad is not None and _SPLIT_WGRAD_ROWS > 0 and rows >= _SPLIT_WGRAD_ROWS
-            and (rec.ib is None or rec.b_grad is not None))
-
-
-# products over at least this many rows take the split-row kernel (0: never).  r04: 16 (was 512) -- the kernel now keeps a whole tile per wave and
-# reduces inside the workgroup, so a 10-sample tail batch (70 / 10 rows: twelve library GEMMs of ~16 us + twelve column sums per epoch)
-# is one grouped launch too; only products over fewer rows than one MFMA tile stay with the library
-_SPLIT_WGRAD_ROWS = int(switches.get("split_wgrad_rows"))
-
-
-# The step that is collecting right now (grouped_wgrads; autograd nodes reach it here): the list of what its backward pass has queued for
-# the grouped weight-gradient launches -- job tuples (dY, X, dW, dbias), whose operands stay alive in here, and at most one callable, a
-# launch that must run in front of them (run_before_wgrad_flush)
-_WGRAD_QUEUE: Optional[list] = None
-
-
-@contextlib.contextmanager
-def grouped_wgrads(device, stash, dst, enabled: bool = True):
-    """`with grouped_wgrads(device, stash, dst): loss.backward()` -- the backward protocol of a step on shadow products: while the body runs
-    the split-row weight gradients are collected (`enabled` False: every product launches inside backward); a clean exit launches them
-    grouped, moves the live `stash` entries (bfloat16) into their float32 destinations `dst` with one multi-tensor copy and clears the
-    stash.  An exception skips all that; either way nothing is left collecting."""
-    global _WGRAD_QUEUE
-    _WGRAD_QUEUE = [] if enabled else None
-    try:
-        yield _WGRAD_QUEUE
-        flush_wgrad_queue(device)
-    finally:
-        _WGRAD_QUEUE = None
-    live = [(dd, ss) for dd, ss in zip(dst, stash) if ss is not None]      # (a product nobody called this step leaves None)
-    if live:
-        torch._foreach_copy_([dd for dd, _ in live], [ss for _, ss in live])
-    for k in range(len(stash)):
-        stash[k] = None
-
-
-def run_before_wgrad_flush(launch) -> None:
-    """`launch()` runs at the collecting step's flush, in front of its grouped launches (tfd_fused: a layer's backward launch that waits
-    for a predecessor which may never run); None: the one that waited has been taken care of.  At most one waits at a time."""
-    if _WGRAD_QUEUE is not None:
-        waiting = [e for e in _WGRAD_QUEUE if callable(e)]
-        assert launch is None or not waiting
-        for e in waiting:
-            _WGRAD_QUEUE.remove(e)
-        if launch is not None:
-            _WGRAD_QUEUE.append(launch)
-
-
-def flush_wgrad_queue(device) -> None:
-    """Launch what the collecting step holds: the waiting launch, then everything queued, 16 products per launch."""
-    if not _WGRAD_QUEUE:
-        return
-    for launch in [e for e in _WGRAD_QUEUE if callable(e)]:
-        launch()
-    q = [e for e in _WGRAD_QUEUE if not callable(e)]
-    _WGRAD_QUEUE.clear()
-    if not q:
-        return
-    from . import _cabi
-    lib = _cabi.load()
-    with torch.cuda.device(device):
-        s = torch.cuda.current_stream(device).cuda_stream
-        for i0 in range(0, len(q), _cabi.WGRAD_MAX_GROUP):
-            part = q[i0:i0 + _cabi.WGRAD_MAX_GROUP]
-            arr = (_cabi.WgradProblem * len(part))()
-            for e, (g2, x2, wg, bg) in zip(arr, part):
-                if x2 is None:                                           # column-sum job: wg [N] += column sums of the float32 rows g2 [T, N]
-                    e.T, e.N, e.K = g2.shape[0], g2.shape[1], 0
-                    e.dY, e.X, e.dW, e.dbias, e.ldy, e.ldx = g2.data_ptr(), None, wg.data_ptr(), None, g2.stride(0), 0
-                    continue
-                e.T, e.N, e.K = x2.shape[0], g2.shape[1], x2.shape[1]
-                e.dY, e.X, e.dW, e.dbias = g2.data_ptr(), x2.data_ptr(), wg.data_ptr(), (bg.data_ptr() if bg is not None else None)
-                e.ldy, e.ldx = g2.stride(0), x2.stride(0)                # (row views with unit column stride travel without a copy)
-            rc = lib.ops_linear_wgrad_accumulate_group(len(part), arr, s)
-            if rc != 0:
-                raise RuntimeError(f"ops_linear_wgrad_accumulate_group failed with code {rc}")
-
-
-def enable_shadow_linears(model: nn.Module, opt: "FlatClipAdam", params, flat: torch.Tensor):
-    """Routes every plain nn.Linear of `model` through _ShadowLinearFn.  Returns (stash, grad_views, patched modules)."""
-    import types
-    sh = opt.enable_shadow()
-    offs, off = {}, 0
-    for q in params:
-        offs[id(q)] = off
-        off += q.numel()
-    stash, dst, patched = [], [], []
-
-    def register(weight, bias):
-        """y = x W^T + b through the shadow of (weight, bias); their gradients travel through `stash` (or, for products over
-        thousands of rows, are added straight into their slices of the zeroed flat gradient buffer)."""
-        ow = offs[id(weight)]
-        w_sh = sh[ow:ow + weight.numel()].view_as(weight)
-        w_grad = flat[ow:ow + weight.numel()].view_as(weight)
-        iw = len(stash); stash.append(None); dst.append(w_grad)
-        b_sh, ib, b_grad = None, None, None
-        if bias is not None:
-            ob = offs[id(bias)]
-            b_sh = sh[ob:ob + bias.numel()]
-            b_grad = flat[ob:ob + bias.numel()]
-            ib = len(stash); stash.append(None); dst.append(b_grad)
-        # (also what a fused block that runs this product itself needs: the shadow operands, and where its gradients go -- shadow_param_grads)
-        rec = ShadowRec(w_sh, b_sh, w_grad, b_grad, stash, iw, ib)
-
-        def prod(x, gx_dest=None):
-            return _ShadowLinearFn.apply(x, rec, weight, gx_dest)
-
-        prod.rec = rec
-        return prod
-
-    for mod in model.modules():
-        if isinstance(mod, nn.MultiheadAttention):
-            # the attention's projections are bare Parameters / a Linear subclass that its functional forward never calls: hand the
-            # shadow products to the encoder fast path (tfd_fused.py), which is their only user
-            if mod._qkv_same_embed_dim and mod.in_proj_bias is not None and id(mod.in_proj_weight) in offs and id(mod.out_proj.weight) in offs:
-                mod._ops_in_proj = register(mod.in_proj_weight, mod.in_proj_bias)
-                mod._ops_out_proj = register(mod.out_proj.weight, mod.out_proj.bias)
-                patched.append(mod)
-            continue
-        if type(mod) is not nn.Linear or id(mod.weight) not in offs:
-            continue
-        prod = register(mod.weight, mod.bias)
-
-        def fwd(self, x, prod=prod):
-            if not x.is_cuda:
-                return F_linear(x, self.weight, self.bias)
-            return prod(x)
-
-        mod.forward = types.MethodType(fwd, mod)
-        mod._ops_prod = prod
-        patched.append(mod)
-    return stash, dst, patched
-
-
-def disable_shadow_linears(patched) -> None:
-    for mod in patched:
-        if "forward" in mod.__dict__:
-            del mod.__dict__["forward"]
-        for name in ("_ops_in_proj", "_ops_out_proj", "_ops_prod"):
-            if name in mod.__dict__:
-                del mod.__dict__[name]
-
-
-_GROUP_WGRAD = switches.get("group_wgrad") == "1"    # A/B switch: 0 = one launch per product, inside backward
-# data-parallel step (world > 1).  Default: [graph A: noise, forward, loss, backward] -> gradient all-reduce -> [graph B: average, clip,
-# Adam], the collective enqueued asynchronously (the host never blocks on it: `wait()` only orders the compute stream behind the
-# collective's) -- OPS_AMD_DP_ASYNC=0 is the plain blocking-call form, bit for bit the same arithmetic (tests/test_surrogates.py).
-# r06: under `nccl` the collective is captured too -- the whole step is ONE graph, one replay per step and no host work between its segments
-# (one-rank RCCL timing, profiles/r05_notes.md 6: PINN 137.5 us against 169.1 us for two graphs around an eager collective, TFD 191.3 / 219.8;
-# the same bits as the plain run).  A failure while capturing falls back to the two-graph form; a captured collective that goes wrong on
-# N > 1 ranks would hang at REPLAY, past every fallback, so the first replay runs under a timer that ends the rank with exit code 17
-# (OPS_AMD_DP_STALL_S seconds, default 120: the launcher then takes the job down; a fresh job may set OPS_AMD_DP_ONE_GRAPH=0 -- never a re-exec
-# from a process that holds the GPU).  OPS_AMD_DP_ONE_GRAPH=0: [graph A | all-reduce | graph B].
-_DP_ASYNC = os.environ.get("OPS_AMD_DP_ASYNC", "1") == "1"
-_DP_ONE_GRAPH = os.environ.get("OPS_AMD_DP_ONE_GRAPH", "1") == "1"
-_DP_STALL_S = float(os.environ.get("OPS_AMD_DP_STALL_S", "120"))
-
-
-stall_hook = None     # callable(what) run by a firing _StallGuard just before the process ends
-
-
-class _StallGuard:
-    """`with _StallGuard(seconds, what):` -- if the block has not finished after `seconds`, the process ends with exit code 17 and a line on
-    stderr saying what stalled (a hung graph replay of a captured collective cannot be recovered inside the process)."""
-
-    def __init__(self, seconds: float, what: str):
-        self.seconds, self.what, self.timer = seconds, what, None
-
-    def _fire(self):
-        if stall_hook is not None:       # the caller's last words (bench.py: the FE record measured before the training part)
-            try:
-                stall_hook(self.what)
-            except Exception:
-                pass
-        sys.stderr.write(f"openpystruct_amd: {self.what} did not finish within {self.seconds:.0f} s -- ending this rank (exit 17); "
-                         f"run again with OPS_AMD_DP_ONE_GRAPH=0 for the two-graph step\n")
-        sys.stderr.flush()
-        os._exit(17)
-
-    def __enter__(self):
-        import threading
-        self.timer = threading.Timer(self.seconds, self._fire)
-        self.timer.daemon = True
-        self.timer.start()
-        return self
-
-    def __exit__(self, *exc):
-        self.timer.cancel()
-        return False
-_FORCE_DP = os.environ.get("OPS_AMD_FORCE_DP", "0") == "1"           # run the data-parallel branch with a one-rank process group too
-_DP_PROFILE = os.environ.get("OPS_AMD_DP_PROFILE", "0") == "1"       # HIP events around the step's segments, reported as out["dp_segments"]
-F_linear = torch.nn.functional.linear
-_SHADOW_LINEAR = switches.get("shadow_linear") == "1"   # A/B switch: 0 = nn.Linear under autocast
 
 
 def build_model_and_loss(kind: str, cfg, data: SurrogateData, device):
@@ -902,11 +587,7 @@ def _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use
     st.model, st.crit = model, crit
     # one flat gradient buffer; every .grad is a view into it (autograd accumulates in place)
     st.params = params = [q for q in model.parameters()]
-    st.flat = flat = torch.zeros(sum(q.numel() for q in params), device=device, dtype=torch.float32)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
+    st.flat = flat = flat_grads(params, device)
     st.g_stash, st.g_dst, st.patched = [], [], []
     st.fast_encoder = None
     st.shared_counter = False
@@ -1113,10 +794,9 @@ class _CapturedStep:
             return
         with_y = False
         if st.fused_prep:                # gather + noise (+ bf16 cast) and, where they are float32, the targets in one launch
-            from . import _cabi
             with_y = st.y_in_prep and sY.dtype == torch.float32 and sY.is_contiguous()
             with torch.cuda.device(st.device):
-                rc = st.opt._lib.ops_gather_rows_noise_targets_f32(
+                rc = _cabi.load().ops_gather_rows_noise_targets_f32(
                     int(idx.numel()), int(Xtr[0].numel()), Xtr.data_ptr(), idx.data_ptr(), self.s_noise.data_ptr(), st.engine_seed,
                     st.prep_counter.data_ptr(), sX.data_ptr(), int(sX.dtype == torch.bfloat16), Ytr.data_ptr() if with_y else None,
                     int(Ytr[0].numel()) if with_y else 0, sY.data_ptr() if with_y else None, torch.cuda.current_stream(st.device).cuda_stream)
@@ -1147,7 +827,7 @@ class _Validation:
         # PINN: validation through the engine's evaluation pass (running statistics, no dropout) when the validation set has its layout
         self.engine_eval = bool(engine is not None and switches.get("pinn_engine_eval") == "1" and Xva.dtype == torch.float32
                                 and Xva.is_contiguous() and Yva.dtype == torch.float32 and Yva.is_contiguous() and Xva.dim() == 2
-                                and cfg.batch_size <= _cabi_rows())
+                                and cfg.batch_size <= _cabi.MLP_MAX_ROWS)
         self.slot_graph = self.vgraph_all = self.val_rows = self.v_acc = None
         self.ev_graphs, self.vgraphs = {}, {}    # row count -> (graph, static row indices) of the engine / (graph, static batch, targets) of the module
         if cap.graph is None:

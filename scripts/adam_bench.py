@@ -4,17 +4,14 @@ us per step over a captured graph of 50 steps."""
 import os, sys
 sys.path.insert(0, os.getcwd())
 import torch
-from openpystruct_amd import _cabi, train
+from openpystruct_amd import _cabi, flat_adam
 ru = lambda v, m: (v + m - 1) // m * m
 sets = {"pinn": [(350, 684), (350,), (350,), (350,)] + [(175, 350), (175,), (350, 175), (350,), (1, 1, 3), (1,), (1,), (1,), (350,), (350,)] * 2 + [(302, 350), (302,)],
         "tfd": [(256, 120), (256,), (120, 256), (120,), (1, 1, 120)] + [(360, 120), (360,), (120, 120), (120,), (256, 120), (256,), (120, 256), (120,), (120,), (120,), (120,), (120,)] * 2 + [(256, 120), (256,), (256,), (256,), (100, 256), (100,)]}
 for name, shapes in sets.items():
     ps = [torch.nn.Parameter(torch.randn(s, device="cuda") * 0.1) for s in shapes]
-    flat = torch.zeros(sum(p.numel() for p in ps), device="cuda")
-    off = 0
-    for p in ps:
-        p.grad = flat[off:off + p.numel()].view_as(p); off += p.numel()
-    opt = train.FlatClipAdam(ps, flat, 1e-3)
+    flat = flat_adam.flat_grads(ps, "cuda")
+    opt = flat_adam.FlatClipAdam(ps, flat, 1e-3)
     opt.enable_shadow()
     mats = [p for p in ps if p.dim() == 2][:_cabi.MLP_MAX_REPACK]
     tiles = [(torch.zeros(ru(N, 16), ru(K, 32), dtype=torch.bfloat16, device="cuda"), torch.zeros(ru(K, 16), ru(N, 32), dtype=torch.bfloat16, device="cuda")) for N, K in (m.shape for m in mats)]

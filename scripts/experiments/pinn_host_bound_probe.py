@@ -5,7 +5,7 @@ import os, sys, time
 os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from openpystruct_amd import train
+from openpystruct_amd import flat_adam
 from openpystruct_amd.pinn_fused import PinnFusedStep
 from openpystruct_amd.surrogates import CompositeLoss, FNNWithResidual
 
@@ -14,11 +14,8 @@ torch.manual_seed(0)
 model = FNNWithResidual(684, 350, 2, 302, 0.5).to(dev)
 crit = CompositeLoss(100, 101, 101, 0.5, 0.1, 1e-3, 0.7, 1.5e-6).to(dev)
 params = list(model.parameters())
-flat = torch.zeros(sum(q.numel() for q in params), device=dev)
-off = 0
-for q in params:
-    q.grad = flat[off:off + q.numel()].view_as(q); off += q.numel()
-opt = train.FlatClipAdam(params, flat, 5e-4, weight_decay=1e-3)
+flat = flat_adam.flat_grads(params, dev)
+opt = flat_adam.FlatClipAdam(params, flat, 5e-4, weight_decay=1e-3)
 eng = PinnFusedStep(model, crit, seed=1)
 opt.repack = eng._repack
 fold = os.environ.get("OPS_AMD_PINN_NORM_FOLD", "1") == "1"

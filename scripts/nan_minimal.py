@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Pure PyTorch (nothing of openpystruct_amd is imported): a bf16-autocast training step of nn.TransformerEncoder captured in a HIP graph,
-replays interleaved with an EAGER step of another batch size -- the pattern in which the r03 NaNs appeared (profiles/r04_notes.md).
+"""PyTorch kernels only (of openpystruct_amd just flat_adam.flat_grads, plain tensor code): a bf16-autocast training step of
+nn.TransformerEncoder captured in a HIP graph, replays interleaved with an EAGER step of another batch size -- the pattern in which the r03 NaNs appeared (profiles/r04_notes.md).
 Several "runs" per process (a new model, optimiser, side stream and graph each, the previous ones destroyed), as train_surrogate does.
 Prints, per run, the first replay after which a parameter gradient is non-finite.  usage: nan_minimal.py [runs] [epochs]"""
-import gc, sys
+import gc, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.nn as nn
+from openpystruct_amd import flat_adam
 runs = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 epochs = int(sys.argv[2]) if len(sys.argv) > 2 else 8
 flags = set(sys.argv[3].split(",")) if len(sys.argv) > 3 else set()
@@ -21,10 +23,7 @@ def one_run(r):
     model = nn.Sequential(nn.TransformerEncoder(layer, 2)).to(dev)
     head = nn.Linear(D, 100).to(dev)
     params = list(model.parameters()) + list(head.parameters())
-    flat = torch.zeros(sum(p.numel() for p in params), device=dev)
-    off = 0
-    for p in params:
-        p.grad = flat[off:off + p.numel()].view_as(p); off += p.numel()
+    flat = flat_adam.flat_grads(params, dev)
     opt = torch.optim.Adam(params, lr=3e-3, capturable=True) if "sgd" not in flags else None
     import contextlib
     ac = (lambda: contextlib.nullcontext()) if "fp32" in flags else (lambda: torch.autocast("cuda", dtype=torch.bfloat16))

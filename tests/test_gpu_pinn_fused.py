@@ -53,13 +53,8 @@ def _make(seed, p_drop, nblk=2, F=684, H=350, C=302, nel=100, smooth=False):
 
 
 def _attach_flat(model):
-    params = list(model.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=params[0].device)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    return flat
+    from openpystruct_amd import flat_adam
+    return flat_adam.flat_grads(model.parameters(), next(model.parameters()).device)
 
 
 def _reference(model, crit, x, y, masks, p_drop):
@@ -469,7 +464,7 @@ def test_gradient_norm_left_by_the_weight_gradient_launch(B, p_drop):
     extra workgroups over the gradients no matrix covers), advances the optimiser's step and tabulates its bias corrections, and
     `FlatClipAdam` skips its norm launch (OPS_ADAM_NORM_READY).  The partial sums add up to the flat buffer's squared norm; two
     optimiser steps taken that way equal the two-launch form (norm launch + update) to float32 rounding of the clip factor."""
-    from openpystruct_amd import _cabi, train
+    from openpystruct_amd import _cabi, flat_adam
     from openpystruct_amd.pinn_fused import PinnFusedStep
     dev = torch.device("cuda:0")
 
@@ -478,7 +473,7 @@ def test_gradient_norm_left_by_the_weight_gradient_launch(B, p_drop):
         model, crit = model.to(dev), crit.to(dev)
         flat = _attach_flat(model)
         params = list(model.parameters())
-        opt = train.FlatClipAdam(params, flat, 5e-4, weight_decay=1e-3, max_norm=0.25)     # (below the gradient norm: the clip factor is in play)
+        opt = flat_adam.FlatClipAdam(params, flat, 5e-4, weight_decay=1e-3, max_norm=0.25)     # (below the gradient norm: the clip factor is in play)
         eng = PinnFusedStep(model, crit, seed=77)
         opt.repack = eng._repack
         if fold:
@@ -517,7 +512,7 @@ def test_weight_copies_rebuilt_by_the_next_gather_equal_the_optimisers_repack_la
     batch-assembly launch of step n + 1 (ops_mlp_gather_noise_repack) instead of a launch of their own behind the update.  Three training
     steps either way: the same float32 parameters bit for bit, the same copies after the closing `repack_now()`, and the copies a step
     reads are the ones of the update before it."""
-    from openpystruct_amd import train
+    from openpystruct_amd import flat_adam
     from openpystruct_amd.pinn_fused import PinnFusedStep
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(9)
@@ -529,7 +524,7 @@ def test_weight_copies_rebuilt_by_the_next_gather_equal_the_optimisers_repack_la
         model, crit = _make(4, 0.5)
         model, crit = model.to(dev), crit.to(dev)
         flat = _attach_flat(model)
-        opt = train.FlatClipAdam(list(model.parameters()), flat, 5e-4, weight_decay=1e-3, max_norm=1.0)
+        opt = flat_adam.FlatClipAdam(list(model.parameters()), flat, 5e-4, weight_decay=1e-3, max_norm=1.0)
         eng = PinnFusedStep(model, crit, seed=21)
         if merged:
             eng.repack_in_gather(opt.p)

@@ -325,18 +325,14 @@ def test_layer_whose_backward_cannot_run_trains_through_the_framework(monkeypatc
     """d = 256, H = 64: eight tokens fit the forward kernel and not the backward one, so a training pass takes the framework's forward
     (and its backward runs); five tokens fit both and stay on the fast path."""
     import torch.nn as nn
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import flat_adam, shadow, tfd_fused as TF
     torch.manual_seed(0)
     layer = nn.TransformerEncoderLayer(d_model=256, nhead=64, dim_feedforward=64, dropout=0.1, activation="relu", batch_first=True)
     enc = nn.TransformerEncoder(layer, num_layers=1).to(DEV)
     params = list(enc.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(enc, opt, params, flat)
+    flat = flat_adam.flat_grads(params, DEV)
+    opt = flat_adam.FlatClipAdam(params, flat, 1e-3)
+    stash, dst, patched = shadow.enable_shadow_linears(enc, opt, params, flat)
     assert TF.patch_encoder(enc, seed=5, direct_param_grads=True)
     calls = []
     inner = TF.encoder_forward
@@ -351,5 +347,5 @@ def test_layer_whose_backward_cannot_run_trains_through_the_framework(monkeypatc
         assert bool(calls) == fast
         assert torch.isfinite(out).all() and torch.isfinite(x.grad).all() and x.grad.abs().sum() > 0
     finally:
-        train.disable_shadow_linears(patched)
+        shadow.disable_shadow_linears(patched)
         TF.unpatch_encoder(enc)

@@ -77,16 +77,13 @@ def test_fused_stencil_batchnorm_under_autocast_returns_bf16_like_the_modules():
                                                        (1.0, 1e-2, 1.0, True), (0.5, 0.3, 50.0, True)])
 def test_flat_clip_adam_equals_torch_clip_plus_adam(gscale, wd, scale, decoupled):
     """csrc/flat_adam.hip == clip_grad_norm_(1.0) + torch.optim.Adam over several steps (clipping active and inactive)."""
-    from openpystruct_amd import train
+    from openpystruct_amd import flat_adam
     torch.manual_seed(1)
     shapes = [(37, 11), (11,), (5, 3, 2), (1,)]
     ps = [torch.nn.Parameter(torch.randn(s, device="cuda")) for s in shapes]
     ref = [torch.nn.Parameter(p.detach().clone()) for p in ps]
-    flat = torch.zeros(sum(p.numel() for p in ps), device="cuda")
-    off = 0
-    for p in ps:
-        p.grad = flat[off:off + p.numel()].view_as(p); off += p.numel()
-    opt = train.FlatClipAdam(ps, flat, 1e-2, weight_decay=wd, max_norm=1.0, decoupled=decoupled)
+    flat = flat_adam.flat_grads(ps, "cuda")
+    opt = flat_adam.FlatClipAdam(ps, flat, 1e-2, weight_decay=wd, max_norm=1.0, decoupled=decoupled)
     ropt = (torch.optim.AdamW if decoupled else torch.optim.Adam)(ref, lr=1e-2, weight_decay=wd)
     for step in range(6):
         gs = [torch.randn(s, device="cuda") * scale for s in shapes]
@@ -147,7 +144,7 @@ def test_graph_validation_pass_equals_an_eager_module_evaluation():
 
 
 def test_shadow_linear_path_trains_like_nn_linear_under_autocast(monkeypatch):
-    """bf16 shadow weights + stashed gradients (train._ShadowLinearFn) vs nn.Linear under autocast: same seeds, same data ->
+    """bf16 shadow weights + stashed gradients (shadow._ShadowLinearFn) vs nn.Linear under autocast: same seeds, same data ->
     the same loss trajectory up to bf16 rounding order; the returned model is a plain module again."""
     from openpystruct_amd import dataprep, sizing, train
     rec = sizing.generate_dataset(3000, sizing.SizingConfig(max_e=30), "cuda", seed=4)
@@ -378,18 +375,14 @@ def test_adam_step_refreshes_the_tiled_weight_copies_and_zeroes_the_gradients():
     """ops_flat_clip_adam_step_repack_f32: after the step every Wp / Wtp holds bf16(new W) / bf16(new W)^T in the tiled layout, zero in
     the padding, identical to a fresh ops_mlp_repack_weights; with OPS_ADAM_ZERO_GRADS the gradient buffer is left zeroed; the
     parameters equal the update without those extras.  Odd shapes included (rows / columns that are no multiples of 16 / 32 / 4)."""
-    from openpystruct_amd import _cabi, train
+    from openpystruct_amd import _cabi, flat_adam
     lib = _cabi.load()
     torch.manual_seed(3)
     shapes = [(360, 120), (120,), (120, 120), (256, 120), (120, 256), (7, 33), (13,), (350, 175), (302, 350)]
     ps = [torch.nn.Parameter(torch.randn(s, device="cuda")) for s in shapes]
     ref = [torch.nn.Parameter(p.detach().clone()) for p in ps]
-    flat, flat_r = (torch.zeros(sum(p.numel() for p in ps), device="cuda") for _ in range(2))
-    for lst, fl in ((ps, flat), (ref, flat_r)):
-        off = 0
-        for p in lst:
-            p.grad = fl[off:off + p.numel()].view_as(p); off += p.numel()
-    opt, ropt = train.FlatClipAdam(ps, flat, 1e-2), train.FlatClipAdam(ref, flat_r, 1e-2)
+    flat, flat_r = flat_adam.flat_grads(ps, "cuda"), flat_adam.flat_grads(ref, "cuda")
+    opt, ropt = flat_adam.FlatClipAdam(ps, flat, 1e-2), flat_adam.FlatClipAdam(ref, flat_r, 1e-2)
     ru = lambda v, m: (v + m - 1) // m * m      # noqa: E731
     mats = [p for p in ps if p.dim() == 2]
     tiles = [(torch.full((ru(N, 16), ru(K, 32)), 7.0, dtype=torch.bfloat16, device="cuda"),

@@ -160,20 +160,16 @@ def _encoder(d=120, H=8, ff=256, layers=2, p=0.0, seed=0):
 def _shadowed(module, lr=1e-3):
     """Every `.grad` of `module` a view of one flat buffer and its Linear maps on the optimiser's bf16 shadow products (as train._setup_step
     leaves a model): (flat, opt, stash, dst, patched)."""
-    from openpystruct_amd import train
+    from openpystruct_amd import flat_adam, shadow
     params = list(module.parameters())
-    flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    off = 0
-    for q in params:
-        q.grad = flat[off:off + q.numel()].view_as(q)
-        off += q.numel()
-    opt = train.FlatClipAdam(params, flat, lr)
-    return (flat, opt) + tuple(train.enable_shadow_linears(module, opt, params, flat))
+    flat = flat_adam.flat_grads(params, DEV)
+    opt = flat_adam.FlatClipAdam(params, flat, lr)
+    return (flat, opt) + tuple(shadow.enable_shadow_linears(module, opt, params, flat))
 
 
 def test_patched_encoder_matches_the_framework_encoder_under_autocast(monkeypatch):
-    from openpystruct_amd import tfd_fused as TF, train
-    monkeypatch.setattr(train, "_SPLIT_WGRAD_ROWS", 512)      # 448 rows through the LIBRARY products (r04's default sends them to the split-row kernel: next test)
+    from openpystruct_amd import shadow, tfd_fused as TF
+    monkeypatch.setattr(shadow, "_SPLIT_WGRAD_ROWS", 512)      # 448 rows through the LIBRARY products (r04's default sends them to the split-row kernel: next test)
     enc = _encoder()
     ref = copy.deepcopy(enc)
     flat, opt, stash, dst, patched = _shadowed(enc)
@@ -183,7 +179,7 @@ def test_patched_encoder_matches_the_framework_encoder_under_autocast(monkeypatc
     w = torch.randn(64, 7, 120, generator=g).to(DEV)
     enc.train(); ref.train()
     flat.zero_()
-    with train.grouped_wgrads(torch.device(DEV), stash, dst, enabled=False), torch.autocast("cuda", dtype=torch.bfloat16):
+    with shadow.grouped_wgrads(torch.device(DEV), stash, dst, enabled=False), torch.autocast("cuda", dtype=torch.bfloat16):
         out = enc(x)
         (out * w).sum().backward()
         assert all(ss is not None for ss in stash) and len(stash) == len(dst)      # every registered product ran (448 rows: the library path)
@@ -199,14 +195,14 @@ def test_patched_encoder_matches_the_framework_encoder_under_autocast(monkeypatc
     enc.eval(); ref.eval()
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
         assert _rel(enc(x), ref(x)) < 1e-2
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_encoder(enc)
     assert "forward" not in enc.__dict__ and not hasattr(enc.layers[0].self_attn, "_ops_in_proj")
 
 
 def test_patched_encoder_with_thousands_of_rows_takes_the_split_row_gradient_path():
     """Same comparison at the training batch (512 x 7 tokens): weight and bias gradients through ops_linear_wgrad_accumulate."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     enc = _encoder(seed=3)
     ref = copy.deepcopy(enc)
     flat, opt, stash, dst, patched = _shadowed(enc)
@@ -224,7 +220,7 @@ def test_patched_encoder_with_thousands_of_rows_takes_the_split_row_gradient_pat
     assert _rel(x.grad, xr.grad) < 3e-2
     for (n, q), (_, qr) in zip(enc.named_parameters(), ref.named_parameters()):
         assert _rel(q.grad, qr.grad) < 6e-2, n              # two bf16 evaluations of the same network
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_encoder(enc)
 
 
@@ -274,7 +270,7 @@ def test_patched_model_matches_the_module_with_the_same_noise(monkeypatch, draw)
     """ModelOnePassTransformerWithDiffusion through patch_model (fused diffusion front end, encoder blocks, fused head) vs its own
     forward, both under bf16 autocast, dropout 0, and with torch.randint / torch.randn_like replaced by a replayable stream:
     draw = True: the step indices / noise the front-end launch drew itself (kept and replayed to the module); False: framework draws."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     monkeypatch.setattr(TF, "DRAW", draw)
     monkeypatch.setattr(TF, "KEEP_DRAWS", True)
@@ -304,7 +300,7 @@ def test_patched_model_matches_the_module_with_the_same_noise(monkeypatch, draw)
     monkeypatch.setattr(torch, "randint", fake_randint)
     monkeypatch.setattr(torch, "randn_like", fake_randn_like)
     model.train(); ref.train()
-    with train.grouped_wgrads(torch.device(DEV), stash, dst, enabled=False), torch.autocast("cuda", dtype=torch.bfloat16):
+    with shadow.grouped_wgrads(torch.device(DEV), stash, dst, enabled=False), torch.autocast("cuda", dtype=torch.bfloat16):
         out = model(x)
         (out.float() * w).sum().backward()
     if draw:
@@ -317,7 +313,7 @@ def test_patched_model_matches_the_module_with_the_same_noise(monkeypatch, draw)
     assert _rel(out.float(), outr.float()) < 1.5e-2
     for (n, q), (_, qr) in zip(model.named_parameters(), ref.named_parameters()):
         assert _rel(q.grad, qr.grad) < 8e-2, n                          # two bf16 evaluations of the same network
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_model(model)
     assert "forward" not in model.__dict__ and "forward" not in model.transformer_encoder.__dict__
 
@@ -326,7 +322,7 @@ def test_head_dropout_mask_is_redrawn_every_step_and_every_graph_replay():
     """The head's dropout (TFD:573, site 103 of the fast path) must draw a fresh mask per step.  With the encoder's dropout off, the
     diffusion noise negligible (beta <= 1e-5) and fc2 replaced by the identity the output IS the dropped hidden vector: its zero
     pattern is the mask.  Two eager passes and two replays of one captured pass must each show a different pattern."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     torch.manual_seed(5)
     model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=0.0).to(DEV)
@@ -359,7 +355,7 @@ def test_head_dropout_mask_is_redrawn_every_step_and_every_graph_replay():
     graph.replay(); torch.cuda.synchronize()
     r2 = zeros_of(out).clone()
     assert float((r1 != r2).float().mean()) > 0.1                # ... and in every replay of a captured step
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_model(model)
 
 
@@ -368,7 +364,7 @@ def test_one_launch_layer_forward_equals_the_eight_launch_form(monkeypatch, B, p
     """csrc/seq_layer.hip (the whole encoder layer's forward as one MFMA launch) against the same layer through the separate launches +
     library products: SAME dropout streams (seeds, element indices, call counter), so with dropout on the two forms drop the same
     elements and differ only by the accumulation order of the bf16 products -- outputs and every gradient to 1e-2 relative L2."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
 
     def run(layer_fwd, layer_bwd=False):
@@ -383,12 +379,12 @@ def test_one_launch_layer_forward_equals_the_eight_launch_form(monkeypatch, B, p
         x = torch.randn(B, 6, 120, generator=g).to(DEV)
         w = torch.randn(B, 100, generator=g).to(DEV) / B
         torch.manual_seed(11)                                   # the same diffusion steps / noise in both runs
-        with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
+        with shadow.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
             out = model(x)
             (out.float() * w).sum().backward()
         torch.cuda.synchronize()
         res = out.float().clone(), {n: q.grad.clone() for n, q in model.named_parameters()}
-        train.disable_shadow_linears(patched)
+        shadow.disable_shadow_linears(patched)
         TF.unpatch_model(model)
         return res
 
@@ -408,7 +404,7 @@ def test_two_layers_in_one_launch_equal_the_two_launches(monkeypatch, B, p, laye
     backward passes (ops_tfd_encoder_layer_pair_bwd: the later layer's launch waits for its predecessor's call).  Three layers: a pair
     and a single launch.  B = 2 / B = 1 (T = 14 / 7 rows: fewer than the split-row threshold of 16): the weight-gradient products are the
     library's and run at once, so the later layer's backward must NOT wait (it read buffers nobody had written yet)."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
 
     def run(pair, pair_bwd=False):
@@ -423,14 +419,14 @@ def test_two_layers_in_one_launch_equal_the_two_launches(monkeypatch, B, p, laye
         x = torch.randn(B, 6, 120, generator=g).to(DEV)
         w = torch.randn(B, 100, generator=g).to(DEV) / B
         torch.manual_seed(11)
-        with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
+        with shadow.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
             out = model(x)
             (out.float() * w).sum().backward()
         torch.cuda.synchronize()
         st = model.transformer_encoder._ops_dropout_state[x.device]
         assert st.pending_layer is None and st.pending_bwd is None
         res = out.float().clone(), flat.clone()
-        train.disable_shadow_linears(patched)
+        shadow.disable_shadow_linears(patched)
         TF.unpatch_model(model)
         return res
 
@@ -448,14 +444,14 @@ def test_pair_launches_with_several_workgroups_per_cu(monkeypatch):
     layer's buffers alive until then (without it the caching allocator handed their memory to the second layer's buffers: wrong evaluation
     outputs, caught by test_evaluation_pass_through_the_one_launch_kernels_equals_the_module in full-suite order).  Evaluation-mode
     forwards at several batch sizes with allocator churn in between: pair launch bit-equal to one launch per layer, every time."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import flat_adam, shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     torch.manual_seed(5)
     model = ModelOnePassTransformerWithDiffusion(6, 120, 100, dropout=0.1).to(DEV)
     params = list(model.parameters())
     flat = torch.zeros(sum(q.numel() for q in params), device=DEV)
-    opt = train.FlatClipAdam(params, flat, 1e-3)
-    stash, dst, patched = train.enable_shadow_linears(model, opt, params, flat)
+    opt = flat_adam.FlatClipAdam(params, flat, 1e-3)
+    stash, dst, patched = shadow.enable_shadow_linears(model, opt, params, flat)
     assert TF.patch_model(model, seed=3, direct_param_grads=True)
     model.diffusion._acp.fill_(1.0)                       # (x_noisy = x: the two passes see the same input whatever is drawn)
     model.eval()
@@ -474,7 +470,7 @@ def test_pair_launches_with_several_workgroups_per_cu(monkeypatch):
             keep.append(torch.empty(1000 * (rep + 1) + 8 * B, device=DEV))      # allocator churn: the next pass finds other free blocks
             if rep % 2:
                 keep.pop(0)
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_model(model)
     assert bad == 0, bad
 
@@ -487,7 +483,7 @@ def test_loss_on_the_head_tile_equals_the_loss_launch(monkeypatch, B, p, alpha0,
     parameter gradients to the order of the float atomics that accumulate them (two runs of ONE path differ as much), the running sum
     advanced.  `second`: another term hangs on the predictions (as the FE-residual one does): its bfloat16 gradient reaches the head's
     backward launch as `g2`, summed there with the launch's own (no addition node), and the output layer's weight gradient sees the sum."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF, train
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion, TrainableL1L2Loss, fused_loss
 
     def run(on_tile):
@@ -501,7 +497,7 @@ def test_loss_on_the_head_tile_equals_the_loss_launch(monkeypatch, B, p, alpha0,
         x = torch.randn(B, 6, 120, generator=g).to(DEV)
         y = torch.randn(B, 100, generator=g).to(DEV)
         acc = torch.full((), 2.0, device=DEV)
-        with train.grouped_wgrads(torch.device(DEV), stash, dst):
+        with shadow.grouped_wgrads(torch.device(DEV), stash, dst):
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 if on_tile:
                     assert TF.arm_head_loss(model, y, crit, alpha0, acc)
@@ -519,7 +515,7 @@ def test_loss_on_the_head_tile_equals_the_loss_launch(monkeypatch, B, p, alpha0,
             loss.backward(gradient=torch.ones((), device=DEV))
         torch.cuda.synchronize()
         res = float(loss) + (float(term) if (second and on_tile) else 0.0), float(acc), out.float().clone(), flat.clone()
-        train.disable_shadow_linears(patched)
+        shadow.disable_shadow_linears(patched)
         TF.unpatch_model(model)
         return res
 
@@ -538,7 +534,7 @@ def test_two_models_do_not_take_each_others_head_loss():
     samples: 21 rows (the split-row threshold is 16), one 16-sample head workgroup.  Outputs bit-equal to a run in which A is armed only
     after B's pass, A's loss to the bound of test_loss_on_the_head_tile_equals_the_loss_launch.  (With the spec in a module global, as it
     was, B's head took it -- same target shape -- and A's step fell back to the loss launches: this test failed there.)"""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion, TrainableL1L2Loss
     B = 3
     g = torch.Generator().manual_seed(6)
@@ -556,7 +552,7 @@ def test_two_models_do_not_take_each_others_head_loss():
         (ma, stash, dst, _), (mb, _, _, _) = models
         crit = TrainableL1L2Loss(0.5, torch.tensor(-1.0, device=DEV), torch.tensor(0.4, device=DEV), 0.5).to(DEV)
         acc = torch.zeros((), device=DEV)
-        with train.grouped_wgrads(torch.device(DEV), stash, dst):
+        with shadow.grouped_wgrads(torch.device(DEV), stash, dst):
             with torch.autocast("cuda", dtype=torch.bfloat16):
                 if arm_before_b:
                     assert TF.arm_head_loss(ma, y, crit, 0.5, acc)
@@ -571,7 +567,7 @@ def test_two_models_do_not_take_each_others_head_loss():
         torch.cuda.synchronize()
         res = out_a.float().clone(), out_b.float().clone(), float(loss_a)
         for model, _, _, patched in models:
-            train.disable_shadow_linears(patched)
+            shadow.disable_shadow_linears(patched)
             TF.unpatch_model(model)
         return res
 
@@ -587,7 +583,7 @@ def test_four_layer_encoder_keeps_training_on_fresh_weights(monkeypatch):
     nothing refreshed after patch_model's second call replaced the entry list, and trained on its initial weights).  Three Adam steps at
     lr 1e-2 through the one-launch kernels against the same steps through the separate launches + library products (which read the
     optimiser's bf16 shadow): same dropout streams, so the fourth step's outputs agree to bf16 accumulation order."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     B = 64
 
@@ -610,13 +606,13 @@ def test_four_layer_encoder_keeps_training_on_fresh_weights(monkeypatch):
         for step in range(4):
             flat.zero_()
             torch.manual_seed(11 + step)
-            with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
+            with shadow.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
                 out = model(x)
                 (out.float() * w).sum().backward()
             outs.append(out.float().clone())
             opt.step()
         torch.cuda.synchronize()
-        train.disable_shadow_linears(patched)
+        shadow.disable_shadow_linears(patched)
         TF.unpatch_model(model)
         return outs
 
@@ -792,7 +788,7 @@ def test_fast_path_gradients_against_float64_autograd(monkeypatch, B, cfg):
     (linear) objective -- nothing is left but bf16 rounding and ReLU branches taken on bf16-rounded pre-activations.  Bounds from the
     measured worst cases (profiles/r03_notes.md 6): every parameter <= 3e-2 relative L2 (zero-gradient parameters against their layer's
     scale)."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     monkeypatch.setattr(TF, "KEEP_DRAWS", True)
     torch.manual_seed(5)
@@ -808,7 +804,7 @@ def test_fast_path_gradients_against_float64_autograd(monkeypatch, B, cfg):
     x = torch.randn(B, cfg["n_cases"], cfg["feat_dim"], generator=g).to(DEV)
     w = torch.randn(B, cfg["n_elem"], generator=g).to(DEV) / B
     model.train(); ref.train()
-    with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
+    with shadow.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
         out = model(x)
         (out.float() * w).sum().backward()
     t_k, e_k = model.transformer_encoder._ops_dropout_state[x.device].draws
@@ -827,7 +823,7 @@ def test_fast_path_gradients_against_float64_autograd(monkeypatch, B, cfg):
                 scale = max(scale, float(gref[wn].norm()) / np.sqrt(gref[wn].shape[-1]))
         worst[n] = float((q.grad.double() - gref[n]).norm()) / (scale + 1e-30)
     # the module itself under bf16 autocast (framework encoder, same draws): how far two bf16 evaluations of this network are from float64
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_model(model)
     auto = copy.deepcopy(ref).float()
     for q in auto.parameters():
@@ -858,7 +854,7 @@ def test_fast_path_gradients_of_a_smooth_network_match_float64(monkeypatch, B):
     side of a bf16 rounding -- and every parameter gradient of the one-launch kernels must agree with float64 autograd of the same
     module to bf16 rounding: <= 3 % relative L2 (zero-gradient biases against their weight's scale), no reference to how well the
     framework's own bf16 evaluation does."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     monkeypatch.setattr(TF, "KEEP_DRAWS", True)
     monkeypatch.setattr(TF, "IDENTITY_ACT", True)
@@ -879,7 +875,7 @@ def test_fast_path_gradients_of_a_smooth_network_match_float64(monkeypatch, B):
     x = torch.randn(B, 6, 120, generator=g).to(DEV)
     w = torch.randn(B, 100, generator=g).to(DEV) / B
     model.train(); ref.train()
-    with train.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
+    with shadow.grouped_wgrads(torch.device(DEV), stash, dst), torch.autocast("cuda", dtype=torch.bfloat16):
         out = model(x)
         (out.float() * w).sum().backward()
     t_k, e_k = model.transformer_encoder._ops_dropout_state[x.device].draws
@@ -899,7 +895,7 @@ def test_fast_path_gradients_of_a_smooth_network_match_float64(monkeypatch, B):
             if wn in gref:
                 scale = max(scale, float(gref[wn].norm()) / np.sqrt(gref[wn].shape[-1]))
         worst[n] = float((q.grad.double() - gref[n]).norm()) / (scale + 1e-30)
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_model(model)
     bad = {n: e for n, e in worst.items() if not (np.isfinite(e) and e <= 3e-2)}
     assert not bad, (bad, max(worst.values()))
@@ -1111,7 +1107,7 @@ def test_one_launch_front_end_against_the_framework_ops(B, Nc, d, hid):
 def test_evaluation_pass_through_the_one_launch_kernels_equals_the_module(monkeypatch):
     """model.eval() + no_grad under bf16 autocast: the patched forward runs the same launches with every dropout probability 0 and the
     draws of the front-end launch; against the module's own evaluation forward on those draws."""
-    from openpystruct_amd import tfd_fused as TF, train
+    from openpystruct_amd import shadow, tfd_fused as TF
     from openpystruct_amd.surrogates import ModelOnePassTransformerWithDiffusion
     monkeypatch.setattr(TF, "KEEP_DRAWS", True)
     torch.manual_seed(5)
@@ -1134,7 +1130,7 @@ def test_evaluation_pass_through_the_one_launch_kernels_equals_the_module(monkey
     assert out.dtype == torch.bfloat16 and _rel(out.float(), outr.float()) < 1.5e-2 and _rel(out2.float(), out.float()) > 1e-4
     with torch.autocast("cuda", dtype=torch.bfloat16):               # with gradients enabled the evaluation pass is the module's own
         assert model(x).requires_grad
-    train.disable_shadow_linears(patched)
+    shadow.disable_shadow_linears(patched)
     TF.unpatch_model(model)
 
 

@@ -344,3 +344,18 @@ def test_switch_registry():
     assert p.returncode == 0 and p.stdout.strip() == "[('pinn_norm_fold', '0'), ('tfd_head', '0')]", p.stdout + p.stderr
     p = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, OPS_AMD_SWITCHES="tpyo=0"), capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and "unknown switch" in p.stderr
+
+
+def test_flat_grads_makes_every_grad_a_view_of_one_zeroed_buffer():
+    """flat_adam.flat_grads: every `.grad` a view at the running offset, in parameter order; autograd accumulates into the views in place."""
+    from openpystruct_amd import flat_adam
+    model = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.Linear(4, 2))
+    params = list(model.parameters())
+    flat = flat_adam.flat_grads(model.parameters(), "cpu")          # (a generator is as good as a list)
+    assert flat.dtype == torch.float32 and flat.shape == (sum(q.numel() for q in params),) == (3 * 4 + 4 + 4 * 2 + 2,) and not flat.any()
+    for q, off in zip(params, np.cumsum([0] + [q.numel() for q in params])):
+        assert q.grad.shape == q.shape and q.grad.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr()
+        assert q.grad.data_ptr() == flat.data_ptr() + 4 * int(off)
+    ptrs = [q.grad.data_ptr() for q in params]
+    model(torch.randn(5, 3)).square().sum().backward()
+    assert [q.grad.data_ptr() for q in params] == ptrs and all(q.grad.any() for q in params) and flat.any()

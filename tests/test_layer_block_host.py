@@ -47,24 +47,39 @@ def test_tfd_patch_needs_the_shadow_products():
 
 
 def test_the_collecting_step_exists_only_inside_its_context_and_runs_a_waiting_launch_once():
-    """train.grouped_wgrads is the one place that sets the collecting step: it exists inside the block, is gone after it -- after an exception
+    """shadow.grouped_wgrads is the one place that sets the collecting step: it exists inside the block, is gone after it -- after an exception
     too -- and a launch that waits for the flush (tfd_fused: a deferred layer backward) runs exactly once on a clean exit, while the step is
     still the collecting one, and not at all when the body raised.  (Nothing is queued: the grouped flush itself launches nothing.)"""
     import pytest
-    from openpystruct_amd import train
+    from openpystruct_amd import shadow
     cpu, ran = torch.device("cpu"), []
-    assert train._WGRAD_QUEUE is None
+    assert shadow._WGRAD_QUEUE is None
     stash, dst = [torch.ones(3), None], [torch.zeros(3), torch.zeros(2)]
-    with train.grouped_wgrads(cpu, stash, dst) as step:
-        assert step is train._WGRAD_QUEUE and step is not None and len(step) == 0
-        train.run_before_wgrad_flush(lambda: ran.append(train._WGRAD_QUEUE is step))
+    with shadow.grouped_wgrads(cpu, stash, dst) as step:
+        assert step is shadow._WGRAD_QUEUE and step is not None and len(step) == 0
+        shadow.run_before_wgrad_flush(lambda: ran.append(shadow._WGRAD_QUEUE is step))
         assert ran == []
-    assert ran == [True] and train._WGRAD_QUEUE is None
+    assert ran == [True] and shadow._WGRAD_QUEUE is None
     assert torch.equal(dst[0], torch.ones(3)) and stash == [None, None]          # the live stash entry moved, the stash cleared
     with pytest.raises(ZeroDivisionError):
-        with train.grouped_wgrads(cpu, stash, dst):
-            train.run_before_wgrad_flush(lambda: ran.append("after an exception"))
+        with shadow.grouped_wgrads(cpu, stash, dst):
+            shadow.run_before_wgrad_flush(lambda: ran.append("after an exception"))
             1 / 0
-    assert ran == [True] and train._WGRAD_QUEUE is None
-    with train.grouped_wgrads(cpu, stash, dst, enabled=False) as step:            # not collecting: products launch inside backward
-        assert step is None and train._WGRAD_QUEUE is None
+    assert ran == [True] and shadow._WGRAD_QUEUE is None
+    with shadow.grouped_wgrads(cpu, stash, dst, enabled=False) as step:            # not collecting: products launch inside backward
+        assert step is None and shadow._WGRAD_QUEUE is None
+
+
+def test_the_layer_modules_reach_the_shadow_protocol_without_the_trainer():
+    """In a fresh interpreter tfd_fused, pinn_fused and a collecting block of shadow.py work without train.py; the waiting launch sees `collecting()` true."""
+    import os
+    import subprocess
+    import sys
+    code = ("import sys, torch\nfrom openpystruct_amd import shadow, tfd_fused, pinn_fused\n"
+            "seen, stash, dst = [], [torch.ones(3), None], [torch.zeros(3), torch.zeros(2)]\n"
+            "with shadow.grouped_wgrads(torch.device('cpu'), stash, dst):\n"
+            "    shadow.run_before_wgrad_flush(lambda: seen.append(shadow.collecting()))\n"
+            "assert torch.equal(dst[0], torch.ones(3)) and stash == [None, None] and seen == [True] and not shadow.collecting()\n"
+            "assert 'openpystruct_amd.train' not in sys.modules\nprint('fine')\n")
+    p = subprocess.run([sys.executable, "-c", code], cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "fine" in p.stdout, p.stderr
