@@ -31,7 +31,7 @@ import torch
 
 from . import _cabi
 from .beam import BeamSolution, _check_inputs, _rows, beam_solve
-from .sizing_common import GRADIENTS, _ptr, _sizing_step, _StepState, checked_objective, run_epochs  # noqa: F401  (GRADIENTS: public here)
+from .sizing_common import GRADIENTS, _ptr, _sizing_step, _StepState, checked_objective, replay_epochs, run_epochs  # noqa: F401  (GRADIENTS: public here)
 
 
 @dataclass
@@ -556,25 +556,11 @@ def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25
         if reuse:
             _EPOCH_GRAPHS[key] = (st, graph)
     if graph is not None:
-        # The "any case still active?" poll lags one replay: its answer travels through a pinned flag behind an event, and the
-        # host reads the flag of replay k - 1 after it has queued replay k -- the device never waits for the host (a blocking
-        # poll drained the queue 13 times per 50 000-case shard, ~40 us each); the price is one replay of skipped wavefronts.
+        # the "any case still active?" poll lags one replay (sizing_common.replay_epochs)
         if key not in _POLL_FLAGS:          # (pinned allocations are slow: one pair of flags and events per device and thread)
             _POLL_FLAGS[key] = (torch.zeros(2, dtype=torch.uint8).pin_memory(), [torch.cuda.Event(), torch.cuda.Event()])
-        flags, events = _POLL_FLAGS[key]
-        flags.zero_()
-        k = 0
-        while epochs_done < cfg.max_e:
-            graph.replay()
-            epochs_done += poll_every
-            flags[k & 1: (k & 1) + 1].copy_(st.active.any().to(torch.uint8).reshape(1), non_blocking=True)
-            events[k & 1].record()
-            lag = 0 if os.environ.get("OPS_AMD_SIZING_POLL_LAG", "1") == "0" else 1
-            if k >= lag:
-                events[(k - lag) & 1].synchronize()
-                if int(flags[(k - lag) & 1]) == 0:
-                    break
-            k += 1
+        replay_epochs(graph, cfg.max_e, poll_every, epochs_done, st.active, *_POLL_FLAGS[key],
+                      lag=0 if os.environ.get("OPS_AMD_SIZING_POLL_LAG", "1") == "0" else 1)
     else:
         hist = []
         run_epochs(st.epoch, cfg.max_e, poll_every, st.active, (lambda: hist.append(st.last_loss.clone())) if record_loss else None)

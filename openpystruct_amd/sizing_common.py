@@ -1,6 +1,7 @@
 """What the two sizing loops share on the host (beams: sizing.py, frames: frames.py): the check of the objective's arguments, the one
-launch of the optimiser step (csrc/sizing_step.hip, csrc/sizing_grad.hip: both loops use one step-kernel family) and the eager
-"run epochs, poll `active` every k" loop.  Nothing here knows a beam from a frame."""
+launch of the optimiser step (csrc/sizing_step.hip, csrc/sizing_grad.hip: both loops use one step-kernel family), the eager
+"run epochs, poll `active` every k" loop and the replay loop of a captured poll interval with its lagging poll.  Nothing here knows
+a beam from a frame."""
 from __future__ import annotations
 
 import ctypes
@@ -88,4 +89,25 @@ def run_epochs(epoch: Callable[[], None], n_max: int, poll_every: int, active, a
             after_epoch()
         if done % poll_every == 0 and not bool(active.any()):
             break
+    return done
+
+
+def replay_epochs(graph, n_max: int, poll_every: int, done: int, active: torch.Tensor, flags: torch.Tensor, events, lag: int = 1) -> int:
+    """The captured loop: replay `graph` (`poll_every` epochs) until `n_max` epochs are queued or no row is active; `done` epochs
+    ran before.  The "any row still active?" poll lags `lag` replays: its answer travels through a pinned flag (`flags`, 2 x uint8)
+    behind an event (`events`, 2), and the host reads the flag of replay k - lag after it has queued replay k -- the device never
+    waits for the host (a blocking poll drained the queue 13 times per 50 000-case shard, ~40 us each); the price is one replay of
+    skipped wavefronts.  Returns the number of epochs queued."""
+    flags.zero_()
+    k = 0
+    while done < n_max:
+        graph.replay()
+        done += poll_every
+        flags[k & 1: (k & 1) + 1].copy_(active.any().to(torch.uint8).reshape(1), non_blocking=True)
+        events[k & 1].record()
+        if k >= lag:
+            events[(k - lag) & 1].synchronize()
+            if int(flags[(k - lag) & 1]) == 0:
+                break
+        k += 1
     return done
