@@ -4,8 +4,9 @@ Host side in Python over a C-ABI HIP library; see DESIGN.md and INTEGRATION.md.
 """
 from . import runtime  # noqa: F401  (entry points call runtime.configure() before their first HIP call; importing sets nothing)
 from .beam import BeamSolution, beam_solve, beam_solve_vjp, differentiable_beam_solve, kernel_name  # noqa: F401
-from .frames import (differentiable_frame_solve, frame_dataset_draws, frame_element_load_vjp, frame_sizing_gradient,  # noqa: F401
-                     frame_solve_vjp, generate_frame_dataset, grid_load_cases)
+from .frames import (FrameCaseSolution, FrameFactor, differentiable_frame_solve, frame_dataset_draws, frame_element_load_vjp,  # noqa: F401
+                     frame_factor, frame_resolve, frame_sizing_gradient, frame_solve_cases, frame_solve_cases_vjp, frame_solve_vjp,
+                     generate_frame_dataset, grid_load_cases)
 from .sizing import GRADIENTS, beam_sizing_gradient  # noqa: F401
 from .multicase import generate_multicase_dataset, optimize_designs  # noqa: F401
 from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam_solve / frame_solve, their VJP ops and autograd formulas)
@@ -13,4 +14,5 @@ from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam
 __all__ = ["BeamSolution", "beam_solve", "beam_solve_vjp", "differentiable_beam_solve", "kernel_name",
            "frame_solve_vjp", "differentiable_frame_solve", "GRADIENTS", "beam_sizing_gradient", "frame_sizing_gradient",
            "frame_element_load_vjp", "grid_load_cases", "frame_dataset_draws", "generate_frame_dataset", "optimize_designs",
-           "generate_multicase_dataset"]
+           "generate_multicase_dataset", "FrameFactor", "FrameCaseSolution", "frame_factor", "frame_resolve", "frame_solve_cases",
+           "frame_solve_cases_vjp"]

@@ -30,7 +30,8 @@ HEADERS = [os.path.join(CSRC, "lane_common.hpp"), os.path.join(CSRC, "library.hp
            os.path.join(ROOT, "include", "openpystruct_amd_sizing_grad.h"), os.path.join(CSRC, "frame_sizing_math.hpp"),
            os.path.join(ROOT, "include", "openpystruct_amd_frame_sizing.h"), os.path.join(CSRC, "frame_loads.hpp"),
            os.path.join(ROOT, "include", "openpystruct_amd_frame_loads.h"), os.path.join(CSRC, "frame_stream.hpp"),
-           os.path.join(CSRC, "sizing_multicase_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_sizing_multicase.h")]
+           os.path.join(CSRC, "sizing_multicase_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_sizing_multicase.h"),
+           os.path.join(CSRC, "frame_resolve.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_frame_cases.h")]
 ARCH = "gfx950"
 # Per-file flags.  beam_fat.hip: its kernels take their leading arguments as plain scalars and pointers (beam_io.hpp, RowsHead)
 # so that the hardware can hand them to every wave in SGPRs at launch; the compiler does that for up to 14 dwords when asked.

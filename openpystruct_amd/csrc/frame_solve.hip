@@ -32,6 +32,7 @@
 #include <atomic>
 
 #include "../../include/openpystruct_amd.h"
+#include "../../include/openpystruct_amd_frame_cases.h"
 #include "library.hpp"
 
 namespace opsamd {
@@ -578,6 +579,7 @@ constexpr int FRAME_WIDE_MAX_KD = 1024;      // frame_wide_kernel's backward swe
 #include "frame_wave.hpp"
 #include "frame_pack.hpp"
 #include "frame_coop.hpp"
+#include "frame_resolve.hpp"
 
 using namespace opsamd;
 
@@ -891,4 +893,114 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
   }
   hipLaunchKernelGGL(frame_solve_kernel, dim3((unsigned)B), dim3((unsigned)T), lds_bytes, s, p, pp_use);
   return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Several load cases per frame on one kept factorisation (include/openpystruct_amd_frame_cases.h, frame_resolve.hpp).
+// The kept buffer: [assembly plan | a zeroed elem_w [ne_bound, 2] for the force recovery of the re-solves | B factor slots of the wave kernel].
+// ------------------------------------------------------------------------------------------------------
+static bool keep_serves(int n_eq, int half_bandwidth) {
+  return half_bandwidth <= 55 && 4 * fw_lds_doubles(n_eq, fw_width(eff_kd(half_bandwidth))) * sizeof(double) <= LDS_MAX;
+}
+static size_t keep_zero_w_bytes(int n_eq) { return ((size_t)ne_bound(n_eq) * 2 * sizeof(double) + 255) & ~(size_t)255; }
+static size_t keep_bytes(int B, int n_eq, int kd) {
+  return plan_region_bytes(n_eq, FW_G, FW_EPG) + keep_zero_w_bytes(n_eq) + (size_t)B * fw_frame_doubles(n_eq, kd) * sizeof(double);
+}
+
+extern "C" size_t ops_frame_factor_workspace_bytes(int B, int n_eq, int half_bandwidth) {
+  if (B <= 0 || n_eq < 1 || half_bandwidth < 0 || !keep_serves(n_eq, half_bandwidth)) return 0;
+  return keep_bytes(B, n_eq, eff_kd(half_bandwidth));
+}
+
+template <int W>
+static hipError_t launch_wave_keep(const FrameParams& p, void* buf, hipStream_t s, int devid) {
+  hipError_t e = set_lds_limit_once<frame_wave_kernel<W, true>>(devid, (int)LDS_MAX);
+  if (e != hipSuccess) return e;
+  const size_t lds = 4 * fw_lds_doubles(p.n_eq, W) * sizeof(double);
+  FwPlan pl;
+  char* zero_w = (char*)frame_plan(p, buf, s, false, W, FW_G, FW_EPG, &pl);
+  e = hipMemsetAsync(zero_w, 0, keep_zero_w_bytes(p.n_eq), s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((frame_wave_kernel<W, true>), dim3((unsigned)((p.B + 3) / 4)), dim3(256), lds, s, p, (double*)(zero_w + keep_zero_w_bytes(p.n_eq)), pl);
+  return hipGetLastError();
+}
+
+extern "C" int ops_frame_factor_solve_f64(int B, int n_nodes, int n_elems, int n_eq, int half_bandwidth,
+                                          const double* elem_geo, const double* elem_EA, const double* elem_E,
+                                          const double* elem_w, const int32_t* elem_eq, const int32_t* node_eq,
+                                          const double* I, const double* loads, long loads_bstride, double* disp,
+                                          double* forces, double* V, double* M, int32_t* status, void* factor,
+                                          size_t factor_bytes, void* stream) {
+  if (B < 0 || n_nodes < 2 || n_elems < 1 || n_eq < 1 || half_bandwidth < 0) return OPS_AMD_ERR_INVALID_ARG;
+  if (loads_bstride != 0 && loads_bstride != 3L * n_nodes) return OPS_AMD_ERR_INVALID_ARG;
+  if (B == 0) return OPS_AMD_OK;
+  if (!elem_geo || !elem_EA || !elem_E || !elem_w || !elem_eq || !node_eq || !I || !loads || !disp || !forces || !V || !M || !factor)
+    return OPS_AMD_ERR_INVALID_ARG;
+  if (!keep_serves(n_eq, half_bandwidth)) return OPS_AMD_ERR_UNSUPPORTED;
+  const int kd = eff_kd(half_bandwidth);
+  if (factor_bytes < keep_bytes(B, n_eq, kd) || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
+  int devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
+  FrameParams p{B, n_nodes, n_elems, n_eq, kd, elem_geo, elem_EA, elem_E, elem_w, elem_eq, node_eq,
+                I, loads, loads_bstride, disp, forces, V, M, status};
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  switch (fw_width(kd)) {
+    case 36: e = launch_wave_keep<36>(p, factor, s, devid); break;
+    case 52: e = launch_wave_keep<52>(p, factor, s, devid); break;
+    default: e = launch_wave_keep<56>(p, factor, s, devid); break;
+  }
+  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
+  return OPS_AMD_OK;
+}
+
+template <int W, int NR>
+static hipError_t launch_resolve(const FrameParams& p, int C, const int32_t* factor_status, const void* buf, hipStream_t s, int devid) {
+  const hipError_t e = set_lds_limit_once<frame_resolve_kernel<W, NR>>(devid, (int)LDS_MAX);
+  if (e != hipSuccess) return e;
+  const FwPlan pl = fw_plan_at(const_cast<void*>(buf), p.n_eq, p.Ne, FW_G, FW_EPG);
+  const char* zero_w = (const char*)buf + plan_region_bytes(p.n_eq, FW_G, FW_EPG);
+  FrameParams q = p;
+  q.elem_w = (const double*)zero_w;
+  const int npass = (C + NR - 1) / NR;
+  hipLaunchKernelGGL((frame_resolve_kernel<W, NR>), dim3((unsigned)((long)p.B * npass)), dim3(64), fr_lds_doubles(p.n_eq, NR) * sizeof(double), s,
+                     q, C, npass, factor_status, (const double*)(zero_w + keep_zero_w_bytes(p.n_eq)), pl);
+  return hipGetLastError();
+}
+// right-hand sides per pass: all of them up to two, four beyond (their LDS fits wherever the keeping solve's four waves do)
+template <int W>
+static hipError_t launch_resolve_nr(const FrameParams& p, int C, const int32_t* factor_status, const void* buf, hipStream_t s, int devid) {
+  if (C == 1) return launch_resolve<W, 1>(p, C, factor_status, buf, s, devid);
+  if (C == 2) return launch_resolve<W, 2>(p, C, factor_status, buf, s, devid);
+  return launch_resolve<W, 4>(p, C, factor_status, buf, s, devid);
+}
+
+extern "C" int ops_frame_resolve_f64(int B, int C, int n_nodes, int n_elems, int n_eq, int half_bandwidth,
+                                     const double* elem_geo, const double* elem_EA, const double* elem_E,
+                                     const int32_t* elem_eq, const int32_t* node_eq, const double* I,
+                                     const double* rhs, long rhs_bstride, const int32_t* factor_status,
+                                     double* disp, double* forces, double* V, double* M, int32_t* status,
+                                     const void* factor, size_t factor_bytes, void* stream) {
+  if (B < 0 || C < 0 || n_nodes < 2 || n_elems < 1 || n_eq < 1 || half_bandwidth < 0) return OPS_AMD_ERR_INVALID_ARG;
+  if (rhs_bstride != 0 && rhs_bstride != 3L * n_nodes * C) return OPS_AMD_ERR_INVALID_ARG;
+  if (B == 0 || C == 0) return OPS_AMD_OK;
+  if (!elem_geo || !elem_EA || !elem_E || !elem_eq || !node_eq || !I || !rhs || !factor_status || !disp || !forces || !V || !M || !status || !factor)
+    return OPS_AMD_ERR_INVALID_ARG;
+  if (!keep_serves(n_eq, half_bandwidth)) return OPS_AMD_ERR_UNSUPPORTED;
+  const int kd = eff_kd(half_bandwidth);
+  if (factor_bytes < keep_bytes(B, n_eq, kd) || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
+  if ((long)B * ((C + 3) / 4 + 1) > 0x7fffffffL || (long)B * C > 0x7fffffffL) return OPS_AMD_ERR_INVALID_ARG;    // one workgroup per (frame, pass)
+  int devid = 0;
+  if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
+  FrameParams p{B, n_nodes, n_elems, n_eq, kd, elem_geo, elem_EA, elem_E, nullptr, elem_eq, node_eq,
+                I, rhs, rhs_bstride, disp, forces, V, M, status};
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  switch (fw_width(kd)) {
+    case 36: e = launch_resolve_nr<36>(p, C, factor_status, factor, s, devid); break;
+    case 52: e = launch_resolve_nr<52>(p, C, factor_status, factor, s, devid); break;
+    default: e = launch_resolve_nr<56>(p, C, factor_status, factor, s, devid); break;
+  }
+  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
+  return OPS_AMD_OK;
 }

@@ -215,8 +215,9 @@ __device__ __forceinline__ void fw_prepare(const FwState<W>& st, int j, int lane
   bad |= (j < n) & !(d > 0.0);                              // (called unconditionally, also for j = n: no branch in the step)
 }
 
-// one factorisation step; S = j mod W at compile time; `rd` = 1 / d_j on entry, 1 / d_(j+1) on return
-template <int W, int S>
+// one factorisation step; S = j mod W at compile time; `rd` = 1 / d_j on entry, 1 / d_(j+1) on return.  KEEP (frame_resolve.hpp): the lane
+// of the pivot row leaves 1 / d_j in the last slot of column j of L (j * W + W - 1: W >= kd + 1, so no entry of L ever sits there)
+template <int W, int S, bool KEEP = false>
 __device__ __forceinline__ void fw_step(FwState<W>& st, int j, int lane, int n, int kd, double* __restrict__ colbuf,
                                         double* __restrict__ Lc, double* __restrict__ xs, double& rd, int& bad) {
   const int rel = (lane - j) & 63, R = j + rel;
@@ -235,6 +236,7 @@ __device__ __forceinline__ void fw_step(FwState<W>& st, int j, int lane, int n, 
   if (inwin) Lc[(size_t)j * W + (rel - 1)] = l;             // column j of L: one coalesced store
 #endif
   if (rel == 0) xs[j] = zj * rdj;                           // w_j = z_j / d_j
+  if constexpr (KEEP) { if (rel == 0 && j < n) Lc[(size_t)j * W + (W - 1)] = rdj; }
   st.y = __builtin_fma(-l, zj, st.y);
   // reg[(S + t) mod W] -= l * A[j + t][j], t = 2 .. W - 1: two columns per 16-byte broadcast read.  (The compiler keeps three
   // reads in flight; an explicit read-ahead of 5 .. 25 reads, at two or three waves per SIMD, measured slower: r03_notes 4.)
@@ -328,7 +330,7 @@ __device__ __forceinline__ void fw_backward(const double* __restrict__ rows, dou
   }
 }
 
-template <int W>
+template <int W, bool KEEP = false>
 __device__ __forceinline__ void frame_wave_body(const FrameParams& p, double* __restrict__ wsf, double* __restrict__ lds, int lane, long b,
                                                 const FwPlan& pl) {
   constexpr int G = FW_G;
@@ -424,7 +426,7 @@ __device__ __forceinline__ void frame_wave_body(const FrameParams& p, double* __
     {                                                                                 \
       const int j = j0 + (S_);                                                        \
       if constexpr ((S_) % 4 == 0) if (j > 0 && (j % G) == 0 && j < n) boundary(j);   /* j0 % 4 == 0 */ \
-      fw_step<W, (S_)>(st, j, lane, n, kd, colbuf, rows, xs, rd, bad);                \
+      fw_step<W, (S_), KEEP>(st, j, lane, n, kd, colbuf, rows, xs, rd, bad);          \
     }
 #define FW_STEP4(S_)                                                                  \
     if constexpr ((S_) < W) {                                                         \
@@ -453,7 +455,7 @@ __device__ __forceinline__ void frame_wave_body(const FrameParams& p, double* __
 #endif
 constexpr int fw_waves(int W) { return W == 36 ? FW_WAVES_36 : W <= 52 ? 3 : FW_WAVES_56; }   // (56-wide at three waves: 16 B of scratch, -4 %)   // measured: only the 52-wide window gains (170 -> 168 VGPRs: 3 waves)
 
-template <int W>
+template <int W, bool KEEP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fw_waves(W))))
 void frame_wave_kernel(const FrameParams p, double* __restrict__ ws, const FwPlan pl) {
   extern __shared__ double lds[];
@@ -464,7 +466,7 @@ void frame_wave_kernel(const FrameParams p, double* __restrict__ ws, const FwPla
   // and the loop around the body cost 30 bytes of scratch and 4 % of the time.)
   const long b = (long)blockIdx.x * 4 + wave;
   if (b >= p.B) return;
-  frame_wave_body<W>(p, ws + b * fw_frame_doubles(p.n_eq, p.kd), lds + (size_t)wave * fw_lds_doubles(p.n_eq, W), lane, b, pl);
+  frame_wave_body<W, KEEP>(p, ws + b * fw_frame_doubles(p.n_eq, p.kd), lds + (size_t)wave * fw_lds_doubles(p.n_eq, W), lane, b, pl);
 }
 
 }  // namespace opsamd

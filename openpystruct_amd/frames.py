@@ -386,6 +386,212 @@ def frame_element_load_vjp(topo: FrameTopology, lam: torch.Tensor, g_forces: Opt
     return g_w
 
 
+class FrameCaseSolution(NamedTuple):
+    """`FrameSolution` with a case axis behind the batch axis."""
+    disp: torch.Tensor      # [B, C, Nn, 3]
+    forces: torch.Tensor    # [B, C, Ne, 6]
+    V: torch.Tensor         # [B, C, Ne]     forces[..., 1]
+    M: torch.Tensor         # [B, C, Ne]     forces[..., 2]
+    status: torch.Tensor    # [B, C] int32
+
+
+class FrameFactor:
+    """The factorisation K(I) = L D L^T of B frames, kept on the device by `frame_factor` for `frame_resolve`.
+    `topo`; `I` [B,Ne]: the CALLER'S tensor, not a copy -- the force recovery of every re-solve reads it, so it must hold the values
+    that were factorised for as long as the factor is used; `workspace`: the kept buffer (uint8); `solution`: the `FrameSolution` of
+    the keeping solve, under the topology's own loads; `status` [B] int32 = `solution.status` (non-zero: that frame's factorisation
+    failed and every re-solve of it is NaN).  Buffers that re-solves need beyond their outputs are kept here by shape."""
+
+    def __init__(self, topo: FrameTopology, I: torch.Tensor, workspace: torch.Tensor, solution: FrameSolution):
+        self.topo, self.I, self.workspace, self.solution, self.status = topo, I, workspace, solution, solution.status
+        self._scratch = {}
+
+    def _buffer(self, name: str, shape: tuple) -> torch.Tensor:
+        t = self._scratch.get((name, shape))
+        if t is None:
+            t = self._scratch[(name, shape)] = torch.empty(shape, dtype=torch.float64, device=self.I.device)
+        return t
+
+
+def frame_factor(topo: FrameTopology, I: torch.Tensor) -> FrameFactor:
+    """Solves the B frames under the topology's own loads, as `frame_solve(topo, I)` does (equal to its tolerances, not bit for bit:
+    always the wave-per-frame kernel), and KEEPS every frame's factorisation: (n_eq + 4) * W doubles per frame, W = 36 / 52 / 56 for
+    half bandwidths up to 35 / 51 / 55.  Served: half bandwidth <= 55 and frames whose four waves fit the LDS of a compute unit;
+    anything else is a ValueError (`frame_solve` serves every shape).  `I` is kept by reference (see `FrameFactor`)."""
+    if torch.is_tensor(I) and (I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne):
+        raise ValueError(f"I must be contiguous float64 [B, {topo.Ne}]")
+    I = _checked("I", I, torch.float64, (None, topo.Ne), gpu_for="frame_factor", in_place=True)
+    lib = _cabi.load()
+    B, dev = I.shape[0], I.device
+    nbytes = int(lib.ops_frame_factor_workspace_bytes(max(B, 1), topo.n_eq, topo.kd))
+    if nbytes == 0:
+        raise ValueError(f"frame_factor keeps the factor of the wave-per-frame kernel only: half bandwidth <= 55 (this topology: {topo.kd}) and "
+                         f"four waves' LDS within 160 KB (n_eq = {topo.n_eq}); use frame_solve, which serves every shape")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    sol = _empty_solution(topo, B, dev)
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_factor_solve_f64(
+            B, topo.Nn, topo.Ne, topo.n_eq, topo.kd, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+            topo.d_w.data_ptr(), topo.d_elem_eq.data_ptr(), topo.d_node_eq.data_ptr(), I.data_ptr(), topo.d_loads.data_ptr(), 0,
+            sol.disp.data_ptr(), sol.forces.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), sol.status.data_ptr(),
+            ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream)
+    _cabi.check(rc, "ops_frame_factor_solve_f64")
+    return FrameFactor(topo, I, ws, sol)
+
+
+def _empty_case_solution(topo: FrameTopology, B: int, C: int, dev) -> FrameCaseSolution:
+    f64 = dict(dtype=torch.float64, device=dev)
+    return FrameCaseSolution(torch.empty((B, C, topo.Nn, 3), **f64), torch.empty((B, C, topo.Ne, 6), **f64),
+                             torch.empty((B, C, topo.Ne), **f64), torch.empty((B, C, topo.Ne), **f64),
+                             torch.empty((B, C), dtype=torch.int32, device=dev))
+
+
+def _checked_cases(name: str, t, B: int, tail: tuple, dev, gpu_for: str, shape_only: bool = False) -> torch.Tensor:
+    """A per-case input: float64 [B,C,*tail] or [C,*tail] (shared by the frames) on `dev`, contiguous.  Shape and dtype first
+    (ValueError), then where it lives (anything but a GPU tensor: RuntimeError)."""
+    dims = ", ".join(str(n) for n in tail)
+    ok = torch.is_tensor(t) and t.dtype == torch.float64 and t.dim() in (len(tail) + 1, len(tail) + 2) and tuple(t.shape[-len(tail):]) == tail
+    if not ok or (t.dim() == len(tail) + 2 and t.shape[0] != B):
+        raise ValueError(f"{name} must be float64 [{B}, C, {dims}] or [C, {dims}]")
+    if shape_only:
+        return t
+    if not t.is_cuda or not dev.type == "cuda":
+        raise RuntimeError(f"{gpu_for} needs GPU tensors: openpystruct_amd has no CPU fallback")
+    if t.device != dev:
+        raise ValueError(f"{name} must be on {dev}, where the factor is")
+    return t.contiguous()
+
+
+def _resolve_launch(factor: FrameFactor, C: int, rhs: torch.Tensor, rhs_bs: int, out: FrameCaseSolution) -> None:
+    """ops_frame_resolve_f64 on the current stream: K(I_b) x = rhs[b, c], forces without element loads, into `out`."""
+    lib = _cabi.load()
+    topo, I = factor.topo, factor.I
+    with torch.cuda.device(I.device):
+        rc = lib.ops_frame_resolve_f64(
+            I.shape[0], C, topo.Nn, topo.Ne, topo.n_eq, topo.kd, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+            topo.d_elem_eq.data_ptr(), topo.d_node_eq.data_ptr(), I.data_ptr(), rhs.data_ptr(), rhs_bs, factor.status.data_ptr(),
+            out.disp.data_ptr(), out.forces.data_ptr(), out.V.data_ptr(), out.M.data_ptr(), out.status.data_ptr(),
+            factor.workspace.data_ptr(), factor.workspace.numel(), torch.cuda.current_stream(I.device).cuda_stream)
+    _cabi.check(rc, "ops_frame_resolve_f64")
+
+
+def frame_resolve(factor: FrameFactor, loads: torch.Tensor, element_loads: Optional[torch.Tensor] = None,
+                  out: Optional[FrameCaseSolution] = None) -> FrameCaseSolution:
+    """C load cases per frame on the kept factorisation, by substitution alone.  `loads`: float64 [B,C,Nn,3], or
+    [C,Nn,3] shared by the frames; `element_loads`: float64 [B,C,Ne,2] or [C,Ne,2] (wy, wx), None = the topology's `wy` / `wx` in
+    every case, as in `frame_solve`.  Three launches on the current stream, as `frame_solve(..., element_loads=)`: the right-hand
+    sides with the consistent loads, ONE re-solve launch for all B * C rows, the correction of the forces.  Case (b, c) depends on
+    frame b's factor and its own loads alone -- not on B, C or its position; a frame whose factorisation failed is NaN with status 1
+    in every case.  With `out` (a `FrameCaseSolution` of this shape) nothing is allocated after the first call of a shape: the
+    right-hand sides, and the replica of a shared `element_loads` (the correction of the forces runs on all B * C rows) or of
+    shared `loads` beside per-frame `element_loads` (one copy launch each), live in buffers kept on the factor."""
+    topo, I = factor.topo, factor.I
+    B, dev = I.shape[0], I.device
+    for name, t, tail in (("loads", loads, (topo.Nn, 3)), ("element_loads", element_loads, (topo.Ne, 2))):      # every shape before any device
+        if t is not None:
+            _checked_cases(name, t, B, tail, dev, "frame_resolve", shape_only=True)
+    if element_loads is not None and element_loads.shape[-3] != loads.shape[-3]:
+        raise ValueError(f"element_loads has {element_loads.shape[-3]} cases, loads has {loads.shape[-3]}")
+    loads = _checked_cases("loads", loads, B, (topo.Nn, 3), dev, "frame_resolve")
+    C = loads.shape[-3]
+    w = None if element_loads is None else _checked_cases("element_loads", element_loads, B, (topo.Ne, 2), dev, "frame_resolve")
+    if out is None:
+        out = _empty_case_solution(topo, B, C, dev)
+    else:
+        want = _empty_case_solution(topo, 0, C, dev)
+        for name, t, ref in zip(FrameCaseSolution._fields, out, want):
+            _checked(f"out.{name}", t, ref.dtype, (B,) + tuple(ref.shape[1:]), dev, in_place=True)
+    if B == 0 or C == 0:
+        return out
+    lib = _cabi.load()
+    adj = _adjoint_tables(topo)
+    # the rows the two streaming kernels work on: all B * C, or the C shared ones where nothing differs between the frames
+    shared = loads.dim() == 3 and (w is None or w.dim() == 3)
+    if loads.dim() == 3 and not shared:
+        loads = factor._buffer("loads_rows", (B, C, topo.Nn, 3)).copy_(loads.expand(B, C, topo.Nn, 3))
+    w_rows, wbs = (topo.d_w, 0) if w is None else (w, 2 * topo.Ne)
+    if w is not None and w.dim() == 3:            # the correction of the forces runs on all B * C rows
+        w_rows = factor._buffer("w_rows", (B, C, topo.Ne, 2)).copy_(w.expand(B, C, topo.Ne, 2))
+    rows = C if shared else B * C
+    rhs = factor._buffer("rhs", (rows, topo.Nn, 3))
+    w_rhs = w if (shared and w is not None) else w_rows
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.ops_frame_load_rhs_f64(rows, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(),
+                                        loads.data_ptr(), 3 * topo.Nn, w_rhs.data_ptr(), wbs, rhs.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_load_rhs_f64")
+    _resolve_launch(factor, C, rhs, 0 if shared else C * topo.Nn * 3, out)
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_load_forces_f64(B * C, topo.Ne, topo.d_geo.data_ptr(), w_rows.data_ptr(), wbs, out.status.data_ptr(),
+                                           out.forces.data_ptr(), out.V.data_ptr(), out.M.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_load_forces_f64")
+    return out
+
+
+def frame_solve_cases(topo: FrameTopology, I: torch.Tensor, loads: torch.Tensor,
+                      element_loads: Optional[torch.Tensor] = None) -> FrameCaseSolution:
+    """`frame_resolve(frame_factor(topo, I), loads, element_loads)`: B designs under C load cases each with ONE factorisation per
+    design, where `frame_solve` on the B * C rows (I repeated per case) factorises K(I) C times.
+    Measured (one MI355X, medians of three rounds, profiles/frame_cases_timing.json), time of `frame_solve` on the
+    rows over the time of this call at C = 1 / 2 / 4 / 8: 15 x 16 x 3072 designs 0.67 / 1.11 / 1.72 / 2.27, 10 x 10 x 4096 0.66 / 1.13 /
+    1.59 / 2.22, 5 x 5 x 8192 0.30 / 0.47 / 0.80 / 1.11.  So it LOSES at C = 1 (a factorisation plus a substitution that reads the
+    factor back) and on small frames up to C = 4, where `frame_solve` runs the packed kernel and this call the wave-per-frame one;
+    nothing here chooses between the two for the caller."""
+    return frame_resolve(frame_factor(topo, I), loads, element_loads)
+
+
+def frame_solve_cases_vjp(factor: FrameFactor, sol: FrameCaseSolution, g_disp: Optional[torch.Tensor] = None,
+                          g_forces: Optional[torch.Tensor] = None, gV: Optional[torch.Tensor] = None, gM: Optional[torch.Tensor] = None):
+    """Vector-Jacobian product of `frame_resolve`: from its solution `sol` and the cotangents of disp [B,C,Nn,3],
+    forces [B,C,Ne,6], V and M [B,C,Ne] (None = zero, bit for bit) returns (gI [B,Ne], g_loads [B,C,Nn,3], g_element_loads
+    [B,C,Ne,2]).  The adjoint displacements of all B * C rows come from ONE re-solve launch on the kept factor -- no factorisation:
+    the adjoint right-hand side (on the rows, with `I` repeated per case: the one copy this makes), the re-solve, the contraction
+    and the element-load VJP on the rows, then gI as the sum over the case axis in index order.  g_loads and g_element_loads are
+    per (frame, case): an input shared by the frames takes their sum over the frames.  Rows of failed frames are NaN."""
+    topo, I = factor.topo, factor.I
+    B, dev = I.shape[0], I.device
+    disp = _checked("sol.disp", sol.disp, torch.float64, (B, None, topo.Nn, 3), dev)
+    C = disp.shape[1]
+    st_fwd = _checked("sol.status", sol.status, torch.int32, (B, C), dev)
+    g_disp = _checked("g_disp", g_disp, torch.float64, (B, C, topo.Nn, 3), dev, optional=True)
+    g_forces = _checked("g_forces", g_forces, torch.float64, (B, C, topo.Ne, 6), dev, optional=True)
+    gV, gM = (_checked(k, v, torch.float64, (B, C, topo.Ne), dev, optional=True) for k, v in (("gV", gV), ("gM", gM)))
+    if not I.is_cuda:
+        raise RuntimeError("frame_solve_cases_vjp needs GPU tensors: openpystruct_amd has no CPU fallback")
+    lib = _cabi.load()
+    f64 = dict(dtype=torch.float64, device=dev)
+    gI = torch.empty((B, topo.Ne), **f64)
+    g_w = torch.empty((B, C, topo.Ne, 2), **f64)
+    lam = _empty_case_solution(topo, B, C, dev)               # disp = lambda; the adjoint's forces, V, M are not used
+    if B == 0 or C == 0:
+        return gI.zero_(), lam.disp, g_w
+    adj = _adjoint_tables(topo)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    R = B * C
+    I_rows = I.repeat_interleave(C, 0)
+    rhs = torch.empty((B, C, topo.Nn, 3), **f64)
+    gI_rows = torch.empty((B, C, topo.Ne), **f64)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.ops_frame_adjoint_rhs_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+                                           adj.conn.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), I_rows.data_ptr(), ptr(g_disp),
+                                           ptr(g_forces), ptr(gV), ptr(gM), rhs.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_adjoint_rhs_f64")
+    _resolve_launch(factor, C, rhs, C * topo.Nn * 3, lam)
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_grad_contract_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(),
+                                             disp.data_ptr(), lam.disp.data_ptr(), ptr(g_forces), ptr(gV), ptr(gM), st_fwd.data_ptr(),
+                                             lam.status.data_ptr(), gI_rows.data_ptr(), stream)
+        _cabi.check(rc, "ops_frame_grad_contract_f64")
+        rc = lib.ops_frame_load_vjp_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.conn.data_ptr(), lam.disp.data_ptr(), ptr(g_forces),
+                                        ptr(gV), ptr(gM), st_fwd.data_ptr(), lam.status.data_ptr(), g_w.data_ptr(), stream)
+    _cabi.check(rc, "ops_frame_load_vjp_f64")
+    gI.copy_(gI_rows[:, 0])
+    for c in range(1, C):                                      # the case axis in index order
+        gI += gI_rows[:, c]
+    return gI, lam.disp, g_w
+
+
 def differentiable_frame_solve(topo: FrameTopology, I: torch.Tensor, loads: Optional[torch.Tensor] = None,
                                element_loads: Optional[torch.Tensor] = None) -> FrameSolution:
     """`frame_solve` through the registered operator `openpystruct_amd::frame_solve` (torch_op.py): gradients reach I and, when
