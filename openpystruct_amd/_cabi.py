@@ -20,6 +20,7 @@ EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpy
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_loads.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_multicase.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_cases.h"),
+                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_designs.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_grad.h"))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
@@ -133,8 +134,12 @@ def _read_abi(path: str = "", known_structs: dict = None) -> types.SimpleNamespa
 
 _abi = _read_abi()
 EXPORTS = tuple(_abi.functions)     # every symbol include/openpystruct_amd.h declares
-# prototypes and the argument structs that are new with them (they may name the main header's structs, not redeclare them)
-_extensions = {path: _read_abi(path, _abi.structs) for path in EXTENSION_HEADER_PATHS}
+# prototypes and the argument structs that are new with them (they may name the structs of the main header and of the extension
+# headers listed before them, not redeclare them)
+_extensions, _known_structs = {}, dict(_abi.structs)
+for _path in EXTENSION_HEADER_PATHS:
+    _extensions[_path] = _read_abi(_path, _known_structs)
+    _known_structs.update(_extensions[_path].structs)
 for _path, _ext in _extensions.items():
     if _ext.defines or set(_ext.functions) & set(EXPORTS):
         raise ValueError(f"{_path}: an extension header declares new entry points and their argument structs, nothing else")

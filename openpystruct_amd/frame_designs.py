@@ -1,0 +1,280 @@
+"""Multi-load-case frame sizing: ONE design (one set of element inertias) under C load cases, on the exact gradient, with ONE
+factorisation per design and epoch.
+
+`optimize_frames(gradient="total")` sizes every (frame, load) row on its own: two factorisations per row and epoch, and C different
+designs for what is one structure under wind from either side, gravity alone and their combinations.  Here the C cases share a
+design and the factorisation of §9k (`frame_factor`, `frame_resolve`):
+
+    L(I) = sum_e I_e + sum_c w_c P_c(I)        (aggregate="sum")         P_c: moment + shear (+ sway, deflection) penalty of case c,
+    L(I) = sum_e I_e + max_c P_c(I)            (aggregate="max")         M, V, ux, uy functions of I through the solve
+
+Rows are design-major: case c of design g is row g*C + c of every [G,C,...] array; the inertias exist once per design.  An epoch is
+six launches -- the keeping solve on I64, the forward re-solve of all G*C rows, the correction of their forces for the element loads,
+the adjoint right-hand sides (csrc/frame_designs.hip), the adjoint re-solve, the design step (same file: the gradient of every case
+formed in registers, aggregated, Adam, one early stop per design).
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _cabi
+from . import frames
+from .frames import FrameCaseSolution, FrameConfig, FrameFactor, FrameTopology
+from .multicase import AGGREGATES
+from .sizing_common import _ptr, checked_objective, run_epochs
+
+
+class FrameDesigns(NamedTuple):
+    I: torch.Tensor                  # [G, Ne] float32: the designs after their last step
+    solution: FrameCaseSolution      # [G, C, ...]: every design's LAST solve (on the inertias that step started from)
+    epochs: torch.Tensor             # [G] int32
+    governing: torch.Tensor          # [G] int32: the case with the largest (weighted) penalty at the last epoch
+    case_penalty: torch.Tensor       # [G, C] float32: P_c at the last epoch
+
+
+def _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit) -> "_cabi.FrameSizingObjective":
+    _, aS, s_lim, aD, d_lim = checked_objective("total", (("sway", alpha_sway, sway_limit), ("deflection", alpha_deflection, deflection_limit)))
+    return _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
+
+
+def _checked_aggregate(aggregate: str, weights, C: int) -> tuple:
+    """(the aggregate's index, weights as a float64 numpy [C] or None), checked as `multicase.MultiCaseState` checks them."""
+    if aggregate not in AGGREGATES:
+        raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+    if aggregate == "max" and weights is not None:
+        raise ValueError('aggregate="max" takes no weights: the governing case is the largest unweighted penalty')
+    if weights is not None:
+        w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+        if w.shape != (C,) or not np.isfinite(w).all() or (w < 0).any():
+            raise ValueError(f"weights must be {C} finite non-negative numbers")
+        weights = w
+    return AGGREGATES.index(aggregate), weights
+
+
+def _checked_limits(topo: FrameTopology, C: int) -> None:
+    most = _cabi.load().ops_frame_design_max_cases()
+    if C < 1 or C > most:
+        raise ValueError(f"{C} load cases: the design step serves 1 to {most}")
+    if topo.Ne > 512:
+        raise ValueError(f"frame design sizing serves up to 512 elements per frame (the design step kernel), got {topo.Ne}")
+
+
+def _factor_bytes(topo: FrameTopology, G: int) -> int:
+    nbytes = int(_cabi.load().ops_frame_factor_workspace_bytes(max(G, 1), topo.n_eq, topo.kd))
+    if nbytes == 0:
+        raise ValueError(f"frame_factor does not serve this topology: it keeps the factor of the wave-per-frame kernel only, half bandwidth <= 55 "
+                         f"(this topology: {topo.kd}) and four waves' LDS within 160 KB (n_eq = {topo.n_eq})")
+    return nbytes
+
+
+def _factor_launch(factor: FrameFactor) -> None:
+    """ops_frame_factor_solve_f64 on the current stream into the factor's own buffers (`frame_factor` without its allocations)."""
+    topo, I, sol = factor.topo, factor.I, factor.solution
+    with torch.cuda.device(I.device):
+        rc = _cabi.load().ops_frame_factor_solve_f64(
+            I.shape[0], topo.Nn, topo.Ne, topo.n_eq, topo.kd, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+            topo.d_w.data_ptr(), topo.d_elem_eq.data_ptr(), topo.d_node_eq.data_ptr(), I.data_ptr(), topo.d_loads.data_ptr(), 0,
+            sol.disp.data_ptr(), sol.forces.data_ptr(), sol.V.data_ptr(), sol.M.data_ptr(), sol.status.data_ptr(),
+            factor.workspace.data_ptr(), factor.workspace.numel(), torch.cuda.current_stream(I.device).cuda_stream)
+    _cabi.check(rc, "ops_frame_factor_solve_f64")
+
+
+class _DesignState:
+    """What the design step updates in place [G, ...] and what steps 4 to 6 of an epoch pass between them [G, C, ...]."""
+
+    def __init__(self, topo: FrameTopology, I: torch.Tensor, I64: torch.Tensor, C: int, hp, obj, aggregate: int, weights, with_grad: bool):
+        G, Ne = I.shape
+        dev = I.device
+        f64, f32, i32 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.float32, torch.int32))
+        self.topo, self.C, self.hp, self.obj, self.aggregate = topo, C, hp, obj, aggregate
+        self.I, self.I64 = I, I64
+        self.exp_avg, self.exp_avg_sq = torch.zeros((G, Ne), **f32), torch.zeros((G, Ne), **f32)
+        self.best, self.last = torch.full((G,), float("inf"), **f32), torch.zeros((G,), **f32)
+        self.patience_cnt, self.epochs = torch.zeros((G,), **i32), torch.zeros((G,), **i32)
+        self.active = torch.ones((G,), dtype=torch.uint8, device=dev)
+        self.case_penalty, self.governing = torch.zeros((G, C), **f32), torch.zeros((G,), **i32)
+        self.weights = None if weights is None else torch.as_tensor(weights, **f64)
+        self.rhs = torch.empty((G, C, topo.Nn, 3), **f64)
+        self.lam = frames._empty_case_solution(topo, G, C, dev)           # disp = lambda; the adjoint's forces, V, M are not used
+        self.loss_extra = torch.zeros((G, C), **f64) if obj.alpha_sway + obj.alpha_deflection > 0.0 else None
+        self.grad = torch.empty((G, Ne), **f64) if with_grad else None
+        sched = np.zeros((max(int(hp.max_epochs), 1), 2), dtype=np.float32)
+        _cabi.load().ops_sizing_schedule_f32(ctypes.byref(hp), sched.ctypes.data)
+        self.schedule = torch.as_tensor(sched, device=dev)
+
+    def gradient_and_step(self, factor: FrameFactor, fwd: FrameCaseSolution) -> None:
+        """Steps 4 to 6 of an epoch on the current stream: the adjoint right-hand sides of all G*C rows, their re-solve on the kept
+        factor, the design step.  No checks, no allocation."""
+        lib = _cabi.load()
+        topo, C, I = self.topo, self.C, self.I
+        G, dev = I.shape[0], I.device
+        adj = frames._adjoint_tables(topo)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = lib.ops_frame_design_rhs_f64(G, C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
+                                              adj.ptr.data_ptr(), adj.idx.data_ptr(), self.I64.data_ptr(), fwd.disp.data_ptr(),
+                                              fwd.V.data_ptr(), fwd.M.data_ptr(), ctypes.byref(self.hp), ctypes.byref(self.obj),
+                                              self.active.data_ptr(), self.rhs.data_ptr(), _ptr(self.loss_extra), stream)
+        _cabi.check(rc, "ops_frame_design_rhs_f64")
+        frames._resolve_launch(factor, C, self.rhs, C * topo.Nn * 3, self.lam)
+        with torch.cuda.device(dev):
+            rc = lib.ops_frame_design_step_f32(
+                G, C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(), I.data_ptr(), self.I64.data_ptr(),
+                fwd.disp.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(), self.lam.disp.data_ptr(), _ptr(self.loss_extra),
+                fwd.status.data_ptr(), self.lam.status.data_ptr(), _ptr(self.weights), self.aggregate,
+                *(t.data_ptr() for t in (self.exp_avg, self.exp_avg_sq, self.best, self.patience_cnt, self.epochs, self.active, self.last,
+                                         self.case_penalty, self.governing)),
+                _ptr(self.grad), ctypes.byref(self.hp), self.schedule.data_ptr(), stream)
+        _cabi.check(rc, "ops_frame_design_step_f32")
+
+
+def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loads: Optional[torch.Tensor] = None, *,
+                           n_designs: Optional[int] = None, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
+                           aggregate: str = "sum", weights: Optional[Sequence[float]] = None, alpha_sway: float = 0.0,
+                           sway_limit: Optional[float] = None, alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None,
+                           max_epochs: Optional[int] = None, poll_every: int = 25, loss_history: Optional[list] = None) -> FrameDesigns:
+    """Size G frame designs, each under its C load cases, on the exact gradient of the aggregated loss.
+    `loads`: float64 [G,C,Nn,3], or [C,Nn,3] shared by the designs (then `n_designs` or `I0` [G,Ne] says how many there are);
+    `element_loads`: float64 [G,C,Ne,2] or [C,Ne,2] (wy, wx), None = the topology's `wy` / `wx` in every case, as in `frame_resolve`.
+    `aggregate`: "sum" (`weights` w_c, default all 1) or "max" (the worst case governs; no weights).  The penalties are those of
+    `optimize_frames(gradient="total")`, per load case.  Adam without a scheduler, the clamp and the early stop of `optimize_frames`,
+    once per design on its aggregated loss.  Six launches and ONE factorisation per epoch (the rows path: five launches and two
+    factorisations per ROW); every buffer is allocated before the loop; `poll_every` as in `optimize_frames`.  `loss_history`: a
+    list that receives every epoch's design loss [G].  Served: half bandwidth <= 55 (`frame_factor`), C <= 64, Ne <= 512.
+    Returns `FrameDesigns` (I, the last solve of every design and case, epochs, governing case, case penalties)."""
+    cfg = cfg or FrameConfig()
+    obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
+    # every shape before any device
+    if torch.is_tensor(loads) and loads.dim() == 4:
+        G = int(loads.shape[0])
+    elif I0 is not None and torch.is_tensor(I0) and I0.dim() == 2:
+        G = int(I0.shape[0])
+    elif n_designs is not None:
+        G = int(n_designs)
+    else:
+        raise ValueError("loads shared by the designs ([C, Nn, 3]) need n_designs or I0 to say how many designs there are")
+    if n_designs is not None and int(n_designs) != G:
+        raise ValueError(f"n_designs = {n_designs}, but loads / I0 are for {G} designs")
+    dev = topo.device
+    frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, "optimize_frame_designs", shape_only=True)
+    C = int(loads.shape[-3])
+    if element_loads is not None:
+        frames._checked_cases("element_loads", element_loads, G, (topo.Ne, 2), dev, "optimize_frame_designs", shape_only=True)
+        if element_loads.shape[-3] != C:
+            raise ValueError(f"element_loads has {element_loads.shape[-3]} cases, loads has {C}")
+    if I0 is not None and (not torch.is_tensor(I0) or tuple(I0.shape) != (G, topo.Ne)):
+        raise ValueError(f"I0 must be [{G}, {topo.Ne}]")
+    _checked_limits(topo, C)
+    agg, w_c = _checked_aggregate(aggregate, weights, C)
+    nbytes = _factor_bytes(topo, G)
+    # then where everything lives: with the loads, on the topology's device
+    if loads.is_cuda and topo.device.type == "cuda" and topo.device.index in (None, loads.device.index):
+        dev = loads.device
+    loads = frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, "optimize_frame_designs")
+    w = None if element_loads is None else frames._checked_cases("element_loads", element_loads, G, (topo.Ne, 2), dev, "optimize_frame_designs")
+    if I0 is not None and not I0.is_cuda:
+        raise RuntimeError("optimize_frame_designs needs GPU tensors: openpystruct_amd has no CPU fallback")
+
+    lib = _cabi.load()
+    Nn, Ne = topo.Nn, topo.Ne
+    f64 = dict(dtype=torch.float64, device=dev)
+    n_max = max_epochs if max_epochs is not None else cfg.num_epochs
+    hp = frames._sizing_params(cfg, n_max)
+    I = I0.to(dtype=torch.float32, device=dev).clone() if I0 is not None else torch.full((G, Ne), cfg.I0, dtype=torch.float32, device=dev)
+    st = _DesignState(topo, I, I.double(), C, hp, obj, agg, w_c, with_grad=False)
+    factor = FrameFactor(topo, st.I64, torch.empty(nbytes, dtype=torch.uint8, device=dev), frames._empty_solution(topo, G, dev))
+    fwd = frames._empty_case_solution(topo, G, C, dev)
+    if G == 0:
+        return FrameDesigns(I, fwd, st.epochs, st.governing, st.case_penalty)
+    # the cases' right-hand sides with the consistent element loads: they do not depend on I (frame_resolve's rows, formed once)
+    adj = frames._adjoint_tables(topo)
+    shared = loads.dim() == 3 and (w is None or w.dim() == 3)
+    if loads.dim() == 3 and not shared:
+        loads = loads.expand(G, C, Nn, 3).contiguous()
+    w_rows, wbs = (topo.d_w, 0) if w is None else (w, 2 * Ne)
+    if w is not None and w.dim() == 3:            # the correction of the forces runs on all G * C rows
+        w_rows = w.expand(G, C, Ne, 2).contiguous()
+    rows = C if shared else G * C
+    fwd_rhs = torch.empty((rows, Nn, 3), **f64)
+    w_rhs = w if (shared and w is not None) else w_rows
+    with torch.cuda.device(dev):
+        rc = lib.ops_frame_load_rhs_f64(rows, Nn, Ne, topo.d_geo.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), loads.data_ptr(),
+                                        3 * Nn, w_rhs.data_ptr(), wbs, fwd_rhs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _cabi.check(rc, "ops_frame_load_rhs_f64")
+    rbs = 0 if shared else C * Nn * 3
+    has_w = w is not None or bool(np.any(topo.wy != 0.0) or np.any(topo.wx != 0.0))
+
+    def forward():
+        _factor_launch(factor)                    # its own solution (the topology's loads) is not used
+        frames._resolve_launch(factor, C, fwd_rhs, rbs, fwd)
+        if has_w:
+            with torch.cuda.device(dev):
+                rc = lib.ops_frame_load_forces_f64(G * C, Ne, topo.d_geo.data_ptr(), w_rows.data_ptr(), wbs, fwd.status.data_ptr(),
+                                                   fwd.forces.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(),
+                                                   torch.cuda.current_stream(dev).cuda_stream)
+            _cabi.check(rc, "ops_frame_load_forces_f64")
+
+    def epoch():
+        forward()
+        st.gradient_and_step(factor, fwd)
+
+    run_epochs(epoch, n_max, poll_every, st.active, (lambda: loss_history.append(st.last.clone())) if loss_history is not None else None)
+    forward()                                     # I64 froze when a design stopped: every design's last solve, all C cases
+    torch.cuda.synchronize(dev)
+    return FrameDesigns(I, fwd, st.epochs, st.governing, st.case_penalty)
+
+
+def frame_design_gradient(factor: FrameFactor, sol: FrameCaseSolution, hp, *, aggregate: str = "sum",
+                          weights: Optional[Sequence[float]] = None, alpha_sway: float = 0.0, sway_limit: Optional[float] = None,
+                          alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
+    """dL/dI [G,Ne] (float64) of the aggregated design objective from a caller's `frame_factor(topo, I)` and the solution `sol` of
+    `frame_resolve(factor, ...)`: steps 4 to 6 of an epoch of `optimize_frame_designs` -- the adjoint right-hand sides, ONE re-solve
+    on the kept factor, the design step -- with the step's state in scratch tensors: nothing of the caller's is written.  `hp`: a
+    `FrameConfig` or an `ops_sizing_params`.  Returns (grad, loss_extra [G,C] -- the value of the displacement terms per case, None
+    when both alphas are 0 --, governing [G] int32).  "sum": grad = 1 + sum_c w_c dP_c/dI; "max": 1 + dP_c*/dI of the governing
+    case.  Rows of a design with a failed factorisation (or, under "sum", any failed case) are NaN."""
+    topo, I64 = factor.topo, factor.I
+    obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
+    if not torch.is_tensor(I64) or I64.dtype != torch.float64 or I64.dim() != 2 or I64.shape[1] != topo.Ne:
+        raise ValueError(f"factor.I must be float64 [G, {topo.Ne}]")
+    G, dev = I64.shape[0], I64.device
+    for name, t, tail, dt in (("sol.disp", sol.disp, (topo.Nn, 3), torch.float64), ("sol.V", sol.V, (topo.Ne,), torch.float64),
+                              ("sol.M", sol.M, (topo.Ne,), torch.float64), ("sol.status", sol.status, (), torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 2 + len(tail) or t.shape[0] != G or tuple(t.shape[2:]) != tail or \
+                t.shape[1] != sol.disp.shape[1] or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous {str(dt).split('.')[-1]} [{G}, C{''.join(', ' + str(n) for n in tail)}]")
+    C = int(sol.disp.shape[1])
+    _checked_limits(topo, C)
+    agg, w_c = _checked_aggregate(aggregate, weights, C)
+    if not I64.is_cuda or any(not t.is_cuda for t in (sol.disp, sol.V, sol.M, sol.status)):
+        raise RuntimeError("frame_design_gradient needs GPU tensors: openpystruct_amd has no CPU fallback")
+    hp = frames._sizing_params(hp) if isinstance(hp, FrameConfig) else hp
+    st = _DesignState(topo, I64.float(), I64.clone(), C, hp, obj, agg, w_c, with_grad=True)
+    if G:
+        st.gradient_and_step(factor, sol)
+    return st.grad, st.loss_extra, st.governing
+
+
+def generate_frame_design_dataset(num_bays: int, num_stories: int, n_designs: int, n_load_cases: int, cfg: Optional[FrameConfig] = None,
+                                  lateral_range=(0.5e4, 2e4), vertical_range=(-2e4, -0.5e4), seed: int = 0, aggregate: str = "sum",
+                                  weights: Optional[Sequence[float]] = None, max_epochs: Optional[int] = None, **objective) -> dict:
+    """`generate_frame_dataset` for designs under several load cases: `n_designs` designs of the reference's num_bays x num_stories
+    frame, each under `n_load_cases` wind and gravity loads -- `frame_dataset_draws(n_designs * n_load_cases)` through
+    `grid_load_cases`, design-major -- sized in one batch by `optimize_frame_designs` (`objective`: its penalty keywords).  Returns
+    CPU tensors: I [G,Ne] float32, lateral, vertical [G,C] float64, V, M [G,C,Ne] and disp [G,C,Nn,3] float64 (the last solve's),
+    epochs [G] int32, status [G,C] int32, governing [G] int32, case_penalty [G,C] float32."""
+    cfg = cfg or FrameConfig()
+    G, C = int(n_designs), int(n_load_cases)
+    topo = frames.grid_frame(num_bays, num_stories, cfg)
+    lateral, vertical = frames.frame_dataset_draws(G * C, lateral_range, vertical_range, seed)
+    loads, w = frames.grid_load_cases(topo, lateral, vertical)
+    r = optimize_frame_designs(topo, loads.reshape(G, C, topo.Nn, 3), w.reshape(G, C, topo.Ne, 2), n_designs=G, cfg=cfg, aggregate=aggregate,
+                               weights=weights, max_epochs=max_epochs, **objective)
+    sol = r.solution
+    return dict(I=r.I.cpu(), lateral=torch.as_tensor(lateral).reshape(G, C), vertical=torch.as_tensor(vertical).reshape(G, C),
+                V=sol.V.cpu(), M=sol.M.cpu(), disp=sol.disp.cpu(), epochs=r.epochs.cpu(), status=sol.status.cpu(),
+                governing=r.governing.cpu(), case_penalty=r.case_penalty.cpu())
