@@ -10,10 +10,12 @@ from .frames import (FrameCaseSolution, FrameFactor, differentiable_frame_solve,
 from .sizing import GRADIENTS, beam_sizing_gradient  # noqa: F401
 from .multicase import generate_multicase_dataset, optimize_designs  # noqa: F401
 from .frame_designs import FrameDesigns, frame_design_gradient, generate_frame_design_dataset, optimize_frame_designs  # noqa: F401
+from .design_loss import DesignObjective, design_gap, design_objective, design_objective_term  # noqa: F401
 from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam_solve / frame_solve, their VJP ops and autograd formulas)
 
 __all__ = ["BeamSolution", "beam_solve", "beam_solve_vjp", "differentiable_beam_solve", "kernel_name",
            "frame_solve_vjp", "differentiable_frame_solve", "GRADIENTS", "beam_sizing_gradient", "frame_sizing_gradient",
            "frame_element_load_vjp", "grid_load_cases", "frame_dataset_draws", "generate_frame_dataset", "optimize_designs",
            "generate_multicase_dataset", "FrameFactor", "FrameCaseSolution", "frame_factor", "frame_resolve", "frame_solve_cases",
-           "frame_solve_cases_vjp", "FrameDesigns", "optimize_frame_designs", "frame_design_gradient", "generate_frame_design_dataset"]
+           "frame_solve_cases_vjp", "FrameDesigns", "optimize_frame_designs", "frame_design_gradient", "generate_frame_design_dataset",
+           "DesignObjective", "design_objective", "design_objective_term", "design_gap"]

@@ -21,6 +21,7 @@ EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpy
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_multicase.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_cases.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_designs.h"),
+                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_design_loss.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_grad.h"))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
@@ -162,6 +163,7 @@ BayesMcArgs = _struct("ops_bayes_mc_args")
 _extension_structs = {name: cls for _ext in _extensions.values() for name, cls in _ext.structs.items()}
 SizingObjective = _extension_structs["ops_sizing_objective"]
 FrameSizingObjective = _extension_structs["ops_frame_sizing_objective"]
+DesignLossArgs = _extension_structs["ops_design_loss_args"]
 # every OPS_AMD_X / OPS_X of the header as X: OK, ERR_*, FIX_*, ABI_VERSION, FRAME_REUSE_PLAN, MLP_*, BAYES_*, WGRAD_MAX_GROUP, ADAM_*, ...
 for _name, _value in _abi.defines.items():
     _short = _name[len("OPS_AMD_"):] if _name.startswith("OPS_AMD_") else _name[len("OPS_"):]

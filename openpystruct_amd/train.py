@@ -30,8 +30,9 @@ import copy
 import os
 import sys
 import time
+import types
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Union
 
 import torch
 import torch.distributed as dist
@@ -348,6 +349,27 @@ class PhysicsTerm:
     wy: float
 
 
+@dataclass
+class DesignTerm:
+    """Optional design-objective term (design_loss.py), given to `train_surrogate(..., physics=...)` in place of a
+    `PhysicsTerm`: weight * mean over the batch of L(I_pred) / ref, the sizing objective of the predicted design under the sample's
+    `cfg.n_cases` load cases (`data.Fy_cases_train`), differentiated through the solve.  `normalise`: ref is the objective of the
+    sample's own label (computed once at setup), so the term is the mean optimality ratio; otherwise ref = 1.  `hp`: a
+    `SizingConfig` or an `ops_sizing_params`; `aggregate`, `weights`, `alpha_deflection`, `deflection_limit` as in
+    `optimize_designs`.  Every group of the data must share the geometry `x` and one support set `fix`.  GPU only."""
+    weight: float
+    x: torch.Tensor        # [N] node coordinates
+    E: float
+    fix: torch.Tensor      # [N] uint8
+    wy: float
+    hp: object
+    aggregate: str = "sum"
+    weights: Optional[Sequence[float]] = None
+    alpha_deflection: float = 0.0
+    deflection_limit: Optional[float] = None
+    normalise: bool = True
+
+
 def r2_score(y_true: torch.Tensor, y_pred: torch.Tensor) -> float:
     """sklearn.metrics.r2_score on the raveled arrays (PINN:851)."""
     yt, yp = y_true.double().reshape(-1), y_pred.double().reshape(-1)
@@ -435,6 +457,79 @@ class _PhysicsInputs:
         else:
             v_p, t_p = pin[1], pin[2]
         return term.weight * fe_residual_loss(I_p, v_p, t_p, self.x, self.E, self.fix, pin[0], self.wy).float()
+
+
+class _DesignInputs:
+    """The design-objective term's device-side inputs -- the groups' load cases, the labels' own objective, the checked argument tuple
+    -- behind the interface of `_PhysicsInputs`.  Always the fused form: only the ROW INDICES travel, the launches gather by them."""
+
+    fused = True
+
+    def __init__(self, term: DesignTerm, kind: str, cfg, data: SurrogateData, device, g_idx, loss_acc):
+        from . import design_loss
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("the design-objective term needs a GPU: openpystruct_amd has no CPU fallback")
+        if data.Fy_cases_train is None:
+            raise ValueError("the design-objective term needs data.Fy_cases_train (records with force_nodes and force_values)")
+        self.term, self.nel, self.g_idx, self.loss_acc = term, cfg.nelem, g_idx, loss_acc
+        Fy = data.Fy_cases_train.to(device=device, dtype=torch.float64).contiguous()
+        if Fy.dim() != 3 or Fy.shape[1] != cfg.n_cases or Fy.shape[2] != cfg.nelem + 1:
+            raise ValueError(f"data.Fy_cases_train must be [G, {cfg.n_cases}, {cfg.nelem + 1}], got {tuple(Fy.shape)}")
+        for split, X in (("training", data.X_train), ("validation", data.X_val)):
+            _check_shared_bridge(term, data, X, cfg.n_cases, split)
+        sI = data.scalers_Y["I"]
+        # (the scaler's two rows on the device, in the launches' dtype: nothing is copied or cast inside a captured step)
+        sI = types.SimpleNamespace(scale_=sI.scale_.to(device=device, dtype=torch.float32).contiguous(),
+                                   mean_=sI.mean_.to(device=device, dtype=torch.float32).contiguous(),
+                                   inverse_transform=lambda t, s=sI: s.inverse_transform(t))
+        kw = dict(aggregate=term.aggregate, weights=term.weights, alpha_deflection=term.alpha_deflection,
+                  deflection_limit=term.deflection_limit)
+        ref = None
+        if term.normalise:       # the optimiser's own objective of every training label, un-standardised
+            I_lab = sI.inverse_transform(data.Y_train[:, :cfg.nelem].to(device).float()).clamp_min(design_loss.I_MIN).double()
+            ref = design_loss.design_objective(I_lab, term.x, term.E, term.fix, Fy, term.wy, term.hp, n_load_cases=cfg.n_cases, **kw).value
+            if not bool((torch.isfinite(ref) & (ref > 0)).all()):
+                raise ValueError("the objective of a training label is not finite and positive: the term cannot be normalised by it")
+            ref = ref.contiguous()
+        self.ref = ref
+        self.spec = design_loss._term_spec(device, cfg.nelem, sI, None, Fy, term.x, term.E, term.fix, term.wy, term.hp, term.weight,
+                                           ref=ref, acc=loss_acc, **kw)
+        self.term_sum = torch.zeros((), dtype=torch.float32, device=device)      # the run's total of the term's step values
+
+    def inputs(self, rows, out=None):
+        if self.g_idx is not None:       # the front-end launch leaves the step's rows in g_idx
+            return (self.g_idx[:rows.numel()],)
+        if out is None:
+            return (rows,)
+        out[0].copy_(rows)
+        return out
+
+    def loss(self, preds, pin):
+        from . import design_loss
+        spec = self.spec[:2] + (pin[0],) + self.spec[3:]
+        value = design_loss._DesignObjectiveTerm.apply(preds, spec)
+        self.term_sum.add_(value.detach())
+        return value
+
+
+def _check_shared_bridge(term: "DesignTerm", data: SurrogateData, X: torch.Tensor, n_cases: int, split: str) -> None:
+    """ValueError unless every case of every group of X has the geometry `term.x` and ONE set of roller positions: the term's
+    launches read one shared x [N] and fix [N]."""
+    ml = data.max_lengths
+    X3 = X.reshape(X.shape[0], n_cases, -1)
+    if X3.shape[0] == 0:
+        return
+    o = ml["roller_x"] + ml["force_x"] + ml["force_values"]
+    rollers, nodes = X3[..., :ml["roller_x"]], X3[..., o:o + ml["node_positions"]]
+    if bool((rollers != rollers[:1, :1]).any()):
+        raise ValueError(f"the design-objective term needs ONE support set: the roller positions differ between the {split} groups")
+    if bool((nodes != nodes[:1, :1]).any()):
+        raise ValueError(f"the design-objective term needs ONE geometry: the node positions differ between the {split} groups")
+    x = torch.as_tensor(term.x, dtype=torch.float64).reshape(-1).cpu()
+    got = data.scalers_inputs["node_positions"].inverse_transform(nodes[0, 0].float().cpu()).double()
+    if got.numel() != x.numel() or not torch.allclose(got, x, rtol=1e-5, atol=1e-5 * float(x.abs().max())):
+        raise ValueError(f"the design-objective term's x is not the geometry of the {split} records")
 
 
 class _Step:
@@ -666,7 +761,11 @@ def _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use
     # lives in `g_order`, `g_cursor` is advanced by the launch itself (reset per epoch).
     st.fuse_gather = False
     st.g_order = st.g_cursor = st.g_noise = st.g_idx = None
-    fused_phys = on_gpu and switches.get("fused_physics") == "1"      # A/B switch: 0 = physics.fe_residual_loss from framework ops
+    design = isinstance(physics, DesignTerm)
+    if design and not on_gpu:
+        raise RuntimeError("the design-objective term needs a GPU: openpystruct_amd has no CPU fallback")
+    # A/B switch: 0 = physics.fe_residual_loss from framework ops (the design-objective term has the fused form only)
+    fused_phys = on_gpu and (design or switches.get("fused_physics") == "1")
     # the loss launch adds every step's value to the epoch's running sum itself (zeroed per epoch): no add node per step
     # (with the fused physics term both launches add into the same running sum: the epoch's total of data loss + term)
     st.loss_acc = loss_acc = torch.zeros((), dtype=torch.float32, device=device) if (
@@ -683,7 +782,10 @@ def _setup_step(kind, data, cfg, device, autocast_dtype, sync_bn, log, seed, use
         st.g_noise = torch.zeros((), device=device)
         st.g_idx = torch.zeros(max(cfg.batch_size, 1), dtype=torch.int64, device=device)
         tfd_fused.arm_gather(model, Xtr, Ytr, st.g_order, st.g_cursor, st.g_idx, st.g_noise, st.engine_seed)
-    st.physics = _PhysicsInputs(physics, kind, cfg, data, device, fused_phys, st.g_idx, loss_acc) if physics is not None else None
+    st.physics = None
+    if physics is not None:
+        st.physics = (_DesignInputs(physics, kind, cfg, data, device, st.g_idx, loss_acc) if design else
+                      _PhysicsInputs(physics, kind, cfg, data, device, fused_phys, st.g_idx, loss_acc))
     if on_gpu and engine is None and switches.get("adam_zero") == "1":
         opt.zero_grads = True            # `flat` starts zeroed (allocation) and every update leaves it zeroed
     # batch assembly in one launch (csrc/input_prep.hip): gather + noise + cast straight into the graph's input buffer
@@ -778,6 +880,8 @@ class _CapturedStep:
                     self.graph_t, self.s_loss_t = got
         torch.cuda.current_stream(device).wait_stream(side)
         st.model.load_state_dict(snap[0]); st.opt.load_state_dict(snap[1])     # the warm-up steps never happened
+        if isinstance(st.physics, _DesignInputs):
+            st.physics.term_sum.zero_()
         st.opt.refresh_shadow()
         if engine is not None:
             engine.repack_now()
@@ -1076,7 +1180,7 @@ def _run_epochs(st: _Step, n_epochs: int, batch_order, log):
 
 def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *, autocast_dtype=torch.bfloat16,
                      sync_bn: bool = False, max_epochs: Optional[int] = None, log=None, seed: int = 0,
-                     use_graph: Optional[bool] = None, physics: Optional[PhysicsTerm] = None,
+                     use_graph: Optional[bool] = None, physics: Union[PhysicsTerm, DesignTerm, None] = None,
                      init_fn=None, batch_order=None) -> Dict[str, object]:
     """Trains on THIS rank's `data` shard; uses DDP when torch.distributed is initialised with world_size > 1.
     Returns history, best state dict, validation R^2 (I only) and per-epoch times.
@@ -1114,6 +1218,11 @@ def _train_surrogate(kind: str, data: SurrogateData, cfg=None, device="cuda", *,
     #  set in loader order, inertias un-standardised and clipped to [0, 1e10], r2_score on the raveled arrays)
     out = {"model": model, "history": hist, "best_val": best_val, "best_state": best_state, "r2_val_I": r2_score(t, p),
            "val_pred_I": p, "val_true_I": t, "epochs": len(hist["train"]), "steps_per_epoch": st.nb_tr}
+    if isinstance(physics, DesignTerm):
+        # the metric a user of the surrogate cares about: how far the predicted designs are from the labels in objective
+        from .design_loss import design_gap
+        out["design_gap_val"] = design_gap(model, data, physics, "val")
+        out["design_term_sum"] = float(st.physics.term_sum)
     if st.fp16_scaler is not None:
         out["grad_scaler"] = {"scale": st.fp16_scaler["scale"], "skipped_steps": st.fp16_scaler["skipped"], "steps": st.fp16_scaler["steps"]}
     if st.dp:
