@@ -10,6 +10,9 @@ from .frames import (FrameCaseSolution, FrameFactor, differentiable_frame_solve,
 from .sizing import GRADIENTS, beam_sizing_gradient  # noqa: F401
 from .multicase import generate_multicase_dataset, optimize_designs  # noqa: F401
 from .frame_designs import FrameDesigns, frame_design_gradient, generate_frame_design_dataset, optimize_frame_designs  # noqa: F401
+from .frame_groups import (DiscreteDesigns, FrameDesignValues, GroupedFrameDesigns, MemberGroups, evaluate_frame_designs,  # noqa: F401
+                           frame_group_gradient, generate_grouped_frame_design_dataset, member_groups, optimize_grouped_frame_designs,
+                           snap_to_catalogue, story_groups)
 from .design_loss import DesignObjective, design_gap, design_objective, design_objective_term  # noqa: F401
 from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam_solve / frame_solve, their VJP ops and autograd formulas)
 
@@ -18,4 +21,6 @@ __all__ = ["BeamSolution", "beam_solve", "beam_solve_vjp", "differentiable_beam_
            "frame_element_load_vjp", "grid_load_cases", "frame_dataset_draws", "generate_frame_dataset", "optimize_designs",
            "generate_multicase_dataset", "FrameFactor", "FrameCaseSolution", "frame_factor", "frame_resolve", "frame_solve_cases",
            "frame_solve_cases_vjp", "FrameDesigns", "optimize_frame_designs", "frame_design_gradient", "generate_frame_design_dataset",
-           "DesignObjective", "design_objective", "design_objective_term", "design_gap"]
+           "DesignObjective", "design_objective", "design_objective_term", "design_gap", "MemberGroups", "member_groups", "story_groups",
+           "GroupedFrameDesigns", "DiscreteDesigns", "FrameDesignValues", "optimize_grouped_frame_designs", "frame_group_gradient",
+           "evaluate_frame_designs", "snap_to_catalogue", "generate_grouped_frame_design_dataset"]

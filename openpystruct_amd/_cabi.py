@@ -22,6 +22,7 @@ EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpy
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_cases.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_designs.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_design_loss.h"),
+                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_groups.h"),
                           os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_grad.h"))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")

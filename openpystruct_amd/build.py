@@ -25,6 +25,7 @@ SOURCES = [os.path.join(CSRC, "beam_solve.hip"), os.path.join(CSRC, "beam_fat.hi
            os.path.join(CSRC, "bayes_mlp.hip"), os.path.join(CSRC, "beam_vjp.hip"), os.path.join(CSRC, "frame_vjp.hip"), os.path.join(CSRC, "sizing_grad.hip"),
            os.path.join(CSRC, "frame_sizing_grad.hip"), os.path.join(CSRC, "frame_loads.hip"),
            os.path.join(CSRC, "sizing_multicase.hip"), os.path.join(CSRC, "frame_designs.hip"), os.path.join(CSRC, "design_loss.hip"),
+           os.path.join(CSRC, "frame_groups.hip"),
            os.path.join(CSRC, "library.hip")]
 HEADERS = [os.path.join(CSRC, "lane_common.hpp"), os.path.join(CSRC, "library.hpp"), os.path.join(CSRC, "repack_tiles.hpp"), os.path.join(CSRC, "beam_math.hpp"), os.path.join(CSRC, "beam_adjoint.hpp"), os.path.join(CSRC, "beam_io.hpp"), os.path.join(CSRC, "call_counter.hpp"), os.path.join(CSRC, "dropout_stream.hpp"), os.path.join(CSRC, "input_noise.hpp"), os.path.join(CSRC, "sizing_math.hpp"), os.path.join(CSRC, "frame_wave.hpp"), os.path.join(CSRC, "frame_pack.hpp"), os.path.join(CSRC, "frame_coop.hpp"), os.path.join(CSRC, "frame_adjoint.hpp"), os.path.join(ROOT, "include", "openpystruct_amd.h"),
            os.path.join(ROOT, "include", "openpystruct_amd_frame_vjp.h"), os.path.join(CSRC, "sizing_grad_math.hpp"),
@@ -34,7 +35,8 @@ HEADERS = [os.path.join(CSRC, "lane_common.hpp"), os.path.join(CSRC, "library.hp
            os.path.join(CSRC, "sizing_multicase_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_sizing_multicase.h"),
            os.path.join(CSRC, "frame_resolve.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_frame_cases.h"),
            os.path.join(CSRC, "frame_designs_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_frame_designs.h"),
-           os.path.join(CSRC, "design_loss_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_design_loss.h")]
+           os.path.join(CSRC, "design_loss_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_design_loss.h"),
+           os.path.join(ROOT, "include", "openpystruct_amd_frame_groups.h")]
 ARCH = "gfx950"
 # Per-file flags.  beam_fat.hip: its kernels take their leading arguments as plain scalars and pointers (beam_io.hpp, RowsHead)
 # so that the hardware can hand them to every wave in SGPRs at launch; the compiler does that for up to 14 dwords when asked.

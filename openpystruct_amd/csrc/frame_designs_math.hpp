@@ -6,7 +6,8 @@
 //   functions of sizing_grad_math.hpp and frame_adjoint.hpp called in the same order, so with -ffp-contract=off every value rounds
 //   as theirs does;
 //   per design, device only: frame_design_step is multicase_design of sizing_multicase_math.hpp, statement for statement, with the
-//   gradient of a case formed in registers (fd_elem_grad) where that function reads a row of `grad`.
+//   gradient of a case formed in registers (fd_elem_grad) where that function reads a row of `grad`.  Its parts -- the walk over the
+//   cases (fd_design_walk), Adam on one variable, the early stop -- are also those of the group step (csrc/frame_groups.hip).
 #pragma once
 
 #include "frame_sizing_math.hpp"
@@ -127,26 +128,38 @@ __device__ __forceinline__ void fd_case_grad(int lane, int Ne, const FrameDesign
   }
 }
 
-// SUM: the weighted sum (aggregate 0); else the worst case (aggregate 1)
-template <int K, bool SUM>
-__device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, const FrameDesignArgs& a) {
+// what the walk over the cases leaves of a design: its loss, governing case and early-stop state, and per lane the float64
+// gradient of its K elements, aggregated over the cases, before it is rounded
+template <int K>
+struct FdWalk {
+  int t_ep, cnt, gov;
+  float best, loss;
+  double g64[K];
+};
+
+// The walk of one design over its C cases, shared by the design step (one variable per element) and the group step
+// (csrc/frame_groups.hip: one variable per group of elements): penalties, loss, governing case and the per-element gradient.
+// SUM: the weighted sum (aggregate 0); else the worst case (aggregate 1).  inertia32(ee): the float32 inertia of element ee, kept in
+// I32; after_walk(): the caller's loads that may fly under the last reductions (Adam's moments)
+template <int K, bool SUM, class Inertia32, class AfterWalk>
+__device__ __forceinline__ void fd_design_walk(int lane, long g, int Ne, const FrameDesignArgs& a, float (&I32)[K], Inertia32 inertia32,
+                                               AfterWalk after_walk, FdWalk<K>& w_) {
   const SizingArgs& s = a.s;
   const ops_sizing_params& hp = s.hp;
   const int C = a.C;
   constexpr bool sum = SUM;
   const long row0 = g * C;
   // the design's state: what the walk needs now, Adam's two moments after it (load_case's loads, the moments later)
-  CaseRegs<K> r;
-  r.t = s.epochs_run[g];
-  r.best = s.best_loss[g];
-  r.cnt = s.patience_cnt[g];
+  w_.t_ep = s.epochs_run[g];
+  w_.best = s.best_loss[g];
+  w_.cnt = s.patience_cnt[g];
   // the element's end nodes and the design's float64 inertia, once for all cases (a lane past Ne reads element 0 and stores nothing)
   int n1[K], n2[K];
   double I64[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int e = lane + 64 * k, ee = e < Ne ? e : 0;
-    r.I[k] = s.I[g * Ne + ee];
+    I32[k] = inertia32(ee);
     n1[k] = a.conn[2 * ee];
     n2[k] = a.conn[2 * ee + 1];
     I64[k] = s.I64[g * Ne + ee];
@@ -154,7 +167,6 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
   FdCaseRegs<K> cur;
   fd_load_case<K, SUM>(lane, row0, 0, Ne, a, n1, n2, cur);
 
-  const int t_ep = r.t;
   const float twoE = (float)(2.0 * hp.E), Gf = (float)hp.G;
 
   // the design's own terms: the two denominators of every element.  At K < 8 the compiler forms them, and what the gradient derives
@@ -162,7 +174,7 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
   // and spill, so there the inertias pass through an empty statement and everything is formed again in every case -- the same
   // expressions on the same numbers either way
   auto inertia = [&](int k) {
-    float Ie = r.I[k];
+    float Ie = I32[k];
     if constexpr (K == 8) __asm__ volatile("" : "+v"(Ie));
     return Ie;
   };
@@ -171,7 +183,7 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
   float lsum_I = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k)
-    if (lane + 64 * k < Ne) lsum_I += r.I[k];
+    if (lane + 64 * k < Ne) lsum_I += I32[k];
   const float sum_I = wave_sum(lsum_I);
 
   // the walk over the cases.  Per case: everything a lane forms from its own elements (the two partial sums, the gradient), then
@@ -227,36 +239,89 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
 #pragma unroll 1
   for (int c = 0; c + 1 < C; ++c) one_case(c, std::false_type{});
   one_case(C - 1, std::true_type{});
-#pragma unroll
-  for (int k = 0; k < K; ++k) {                   // Adam's moments: in flight under the last reductions
-    const int e = lane + 64 * k;
-    const long o = g * Ne + (e < Ne ? e : 0);
-    r.m[k] = s.exp_avg[o];
-    r.v[k] = s.exp_avg_sq[o];
-  }
-  double g64[K];
+  after_walk();                                   // Adam's moments: in flight under the last reductions
   if constexpr (sum) {
     const double once = wsum - 1.0;               // every case's gradient carries the weight term's 1
 #pragma unroll
-    for (int k = 0; k < K; ++k) g64[k] = gacc[k] - once;
+    for (int k = 0; k < K; ++k) w_.g64[k] = gacc[k] - once;
   } else {
     loss = sum_I + top;
     fd_load_case<K, true>(lane, row0 + gov, gov, Ne, a, n1, n2, cur);      // the governing row, read now that it is known
-    fd_case_grad<K>(lane, Ne, a, I64, cur, [&](int k, double gk) { g64[k] = gk; });
+    fd_case_grad<K>(lane, Ne, a, I64, cur, [&](int k, double gk) { w_.g64[k] = gk; });
   }
+  w_.loss = loss;
+  w_.gov = gov;
+}
 
-  // Adam, clamp (step_case).  The step sizes are formed here, after the walk: pow() in double needs the registers a case occupies
-  float step_size, bc2s;
+// Adam's step sizes of epoch t_ep (step_case).  Formed after the walk: pow() in double needs the registers a case occupies
+struct FdAdam { float step_size, bc2s, omb1, omb2; };
+
+__device__ __forceinline__ FdAdam fd_adam_sizes(const SizingArgs& s, int t_ep) {
+  const ops_sizing_params& hp = s.hp;
+  FdAdam z;
   if (s.schedule) {
-    step_size = s.schedule[2 * t_ep];
-    bc2s = s.schedule[2 * t_ep + 1];
+    z.step_size = s.schedule[2 * t_ep];
+    z.bc2s = s.schedule[2 * t_ep + 1];
   } else {
     const float lr_t = (float)(hp.lr * pow(hp.gamma, (double)t_ep));
     const float bc1 = (float)(1.0 - pow(hp.beta1, (double)(t_ep + 1)));
-    bc2s = (float)sqrt(1.0 - pow(hp.beta2, (double)(t_ep + 1)));
-    step_size = lr_t / bc1;
+    z.bc2s = (float)sqrt(1.0 - pow(hp.beta2, (double)(t_ep + 1)));
+    z.step_size = lr_t / bc1;
   }
-  const float omb1 = (float)(1.0 - hp.beta1), omb2 = (float)(1.0 - hp.beta2);
+  z.omb1 = (float)(1.0 - hp.beta1);
+  z.omb2 = (float)(1.0 - hp.beta2);
+  return z;
+}
+
+// Adam and the clamp on one variable (step_case): x with gradient gk and moments m, v -> its new value; the new moments in ea, es
+__device__ __forceinline__ float fd_adam_var(const ops_sizing_params& hp, const FdAdam& z, float x, float gk, float m, float v, float& ea,
+                                             float& es) {
+  ea = (float)hp.beta1 * m + z.omb1 * gk;
+  es = (float)hp.beta2 * v + z.omb2 * gk * gk;
+  const float denom = sqrtf(es) / z.bc2s + (float)hp.adam_eps;
+  float xn = x - z.step_size * (ea / denom);
+  return fmaxf(xn, (float)hp.clamp_min);
+}
+
+// early stopping, one decision per design: updates best and cnt of `w`, true when the design stops
+template <int K>
+__device__ __forceinline__ bool fd_early_stop(const ops_sizing_params& hp, FdWalk<K>& w) {
+  if (w.loss < w.best - (float)hp.tolerance) { w.best = w.loss; w.cnt = 0; } else { w.cnt += 1; }
+  return (w.cnt >= hp.patience) || (w.t_ep + 1 >= hp.max_epochs);
+}
+
+// the design's scalars, by one lane
+template <int K>
+__device__ __forceinline__ void fd_store_design(int lane, long g, const FrameDesignArgs& a, const FdWalk<K>& w, bool stop) {
+  const SizingArgs& s = a.s;
+  if (lane == 0) {
+    s.best_loss[g] = w.best;
+    s.patience_cnt[g] = w.cnt;
+    s.epochs_run[g] = w.t_ep + 1;
+    s.last_loss[g] = w.loss;
+    if (a.governing) a.governing[g] = w.gov;
+    if (stop) s.active[g] = 0;
+  }
+}
+
+template <int K, bool SUM>
+__device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, const FrameDesignArgs& a) {
+  const SizingArgs& s = a.s;
+  const ops_sizing_params& hp = s.hp;
+  float I32[K], m[K], v[K];
+  FdWalk<K> w;
+  fd_design_walk<K, SUM>(lane, g, Ne, a, I32, [&](int ee) { return s.I[g * Ne + ee]; }, [&]() {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int e = lane + 64 * k;
+      const long o = g * Ne + (e < Ne ? e : 0);
+      m[k] = s.exp_avg[o];
+      v[k] = s.exp_avg_sq[o];
+    }
+  }, w);
+
+  // Adam, clamp (step_case)
+  const FdAdam z = fd_adam_sizes(s, w.t_ep);
   float Inew[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -264,25 +329,16 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
     Inew[k] = 0.f;
     if (e < Ne) {
       const long o = g * Ne + e;
-      const float Ie = r.I[k];
-      const float gk = (float)g64[k];
-      if (a.grad_out) a.grad_out[o] = g64[k];
-      const float ea = (float)hp.beta1 * r.m[k] + omb1 * gk;
-      const float es = (float)hp.beta2 * r.v[k] + omb2 * gk * gk;
+      if (a.grad_out) a.grad_out[o] = w.g64[k];
+      float ea, es;
+      const float In = fd_adam_var(hp, z, I32[k], (float)w.g64[k], m[k], v[k], ea, es);
       s.exp_avg[o] = ea;
       s.exp_avg_sq[o] = es;
-      const float denom = sqrtf(es) / bc2s + (float)hp.adam_eps;
-      float In = Ie - step_size * (ea / denom);
-      In = fmaxf(In, (float)hp.clamp_min);
       s.I[o] = In;
       Inew[k] = In;
     }
   }
-  // early stopping, one decision per design
-  float best = r.best;
-  int cnt = r.cnt;
-  if (loss < best - (float)hp.tolerance) { best = loss; cnt = 0; } else { cnt += 1; }
-  const bool stop = (cnt >= hp.patience) || (t_ep + 1 >= hp.max_epochs);
+  const bool stop = fd_early_stop(hp, w);
   if (!stop) {
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -290,14 +346,7 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
       if (e < Ne) s.I64[g * Ne + e] = (double)Inew[k];   // what the next factorisation reads, once per design
     }
   }
-  if (lane == 0) {
-    s.best_loss[g] = best;
-    s.patience_cnt[g] = cnt;
-    s.epochs_run[g] = t_ep + 1;
-    s.last_loss[g] = loss;
-    if (a.governing) a.governing[g] = gov;
-    if (stop) s.active[g] = 0;
-  }
+  fd_store_design(lane, g, a, w, stop);
 }
 
 }  // namespace opsamd

@@ -52,12 +52,7 @@ __device__ __forceinline__ double fw_readlane(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
 }
-// LDS operations of one wave execute in order; this pins the compiler and lands earlier reads
-__device__ __forceinline__ void fw_fence() {
-  __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-  __asm__ volatile("" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-}
+// (fw_fence, the ordering of one wave's LDS operations: lane_common.hpp)
 
 // ---- assembly plan: the topology-only part of the assembly, built once per call ----
 // Row R of the band is  sum over its incident element entries (e, r, q):  ka[e][r][q] + I_e * kb[e][r][q]  at column slot

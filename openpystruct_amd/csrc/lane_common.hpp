@@ -27,6 +27,14 @@ __device__ __forceinline__ T wave_sum(T v) {
   return v;
 }
 
+// LDS operations of one wave execute in order; this pins the compiler and lands earlier reads (the frame kernels' hand-over between
+// the lanes of one wave: frame_wave.hpp, frame_resolve.hpp, frame_groups.hip)
+__device__ __forceinline__ void fw_fence() {
+  __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
+  __asm__ volatile("" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
 // Sums NV doubles over a workgroup of NW waves (s_red: [NW][NV] doubles of LDS, free after the first barrier); ALL: every thread gets the
 // totals, otherwise thread 0 only
 template <int NW, bool ALL, int NV>

@@ -16,6 +16,7 @@ formed in registers, aggregated, Adam, one early stop per design).
 from __future__ import annotations
 
 import ctypes
+import types
 from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -86,13 +87,15 @@ def _factor_launch(factor: FrameFactor) -> None:
 class _DesignState:
     """What the design step updates in place [G, ...] and what steps 4 to 6 of an epoch pass between them [G, C, ...]."""
 
-    def __init__(self, topo: FrameTopology, I: torch.Tensor, I64: torch.Tensor, C: int, hp, obj, aggregate: int, weights, with_grad: bool):
+    def __init__(self, topo: FrameTopology, I: torch.Tensor, I64: torch.Tensor, C: int, hp, obj, aggregate: int, weights, with_grad: bool,
+                 n_vars: Optional[int] = None):
         G, Ne = I.shape
+        Nv = Ne if n_vars is None else n_vars         # the variables Adam steps on: the elements, or their groups (frame_groups.py)
         dev = I.device
         f64, f32, i32 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.float32, torch.int32))
         self.topo, self.C, self.hp, self.obj, self.aggregate = topo, C, hp, obj, aggregate
         self.I, self.I64 = I, I64
-        self.exp_avg, self.exp_avg_sq = torch.zeros((G, Ne), **f32), torch.zeros((G, Ne), **f32)
+        self.exp_avg, self.exp_avg_sq = torch.zeros((G, Nv), **f32), torch.zeros((G, Nv), **f32)
         self.best, self.last = torch.full((G,), float("inf"), **f32), torch.zeros((G,), **f32)
         self.patience_cnt, self.epochs = torch.zeros((G,), **i32), torch.zeros((G,), **i32)
         self.active = torch.ones((G,), dtype=torch.uint8, device=dev)
@@ -101,35 +104,127 @@ class _DesignState:
         self.rhs = torch.empty((G, C, topo.Nn, 3), **f64)
         self.lam = frames._empty_case_solution(topo, G, C, dev)           # disp = lambda; the adjoint's forces, V, M are not used
         self.loss_extra = torch.zeros((G, C), **f64) if obj.alpha_sway + obj.alpha_deflection > 0.0 else None
-        self.grad = torch.empty((G, Ne), **f64) if with_grad else None
+        self.grad = torch.empty((G, Nv), **f64) if with_grad else None
         sched = np.zeros((max(int(hp.max_epochs), 1), 2), dtype=np.float32)
         _cabi.load().ops_sizing_schedule_f32(ctypes.byref(hp), sched.ctypes.data)
         self.schedule = torch.as_tensor(sched, device=dev)
 
+    def adjoint_rhs(self, fwd: FrameCaseSolution) -> None:
+        """Step 4 of an epoch on the current stream: the adjoint right-hand sides (and the hinge values) of all G*C rows."""
+        topo, C, I = self.topo, self.C, self.I
+        dev = I.device
+        adj = frames._adjoint_tables(topo)
+        with torch.cuda.device(dev):
+            rc = _cabi.load().ops_frame_design_rhs_f64(
+                I.shape[0], C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(), adj.ptr.data_ptr(),
+                adj.idx.data_ptr(), self.I64.data_ptr(), fwd.disp.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(), ctypes.byref(self.hp),
+                ctypes.byref(self.obj), self.active.data_ptr(), self.rhs.data_ptr(), _ptr(self.loss_extra),
+                torch.cuda.current_stream(dev).cuda_stream)
+        _cabi.check(rc, "ops_frame_design_rhs_f64")
+
     def gradient_and_step(self, factor: FrameFactor, fwd: FrameCaseSolution) -> None:
         """Steps 4 to 6 of an epoch on the current stream: the adjoint right-hand sides of all G*C rows, their re-solve on the kept
         factor, the design step.  No checks, no allocation."""
-        lib = _cabi.load()
-        topo, C, I = self.topo, self.C, self.I
-        G, dev = I.shape[0], I.device
-        adj = frames._adjoint_tables(topo)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = lib.ops_frame_design_rhs_f64(G, C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
-                                              adj.ptr.data_ptr(), adj.idx.data_ptr(), self.I64.data_ptr(), fwd.disp.data_ptr(),
-                                              fwd.V.data_ptr(), fwd.M.data_ptr(), ctypes.byref(self.hp), ctypes.byref(self.obj),
-                                              self.active.data_ptr(), self.rhs.data_ptr(), _ptr(self.loss_extra), stream)
-        _cabi.check(rc, "ops_frame_design_rhs_f64")
-        frames._resolve_launch(factor, C, self.rhs, C * topo.Nn * 3, self.lam)
-        with torch.cuda.device(dev):
-            rc = lib.ops_frame_design_step_f32(
-                G, C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(), I.data_ptr(), self.I64.data_ptr(),
-                fwd.disp.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(), self.lam.disp.data_ptr(), _ptr(self.loss_extra),
-                fwd.status.data_ptr(), self.lam.status.data_ptr(), _ptr(self.weights), self.aggregate,
+        self.adjoint_rhs(fwd)
+        frames._resolve_launch(factor, self.C, self.rhs, self.C * self.topo.Nn * 3, self.lam)
+        self.step(fwd, self.lam.disp, self.lam.status)
+
+    def _step_tail(self, fwd: FrameCaseSolution, lam: torch.Tensor, status_adj: Optional[torch.Tensor]) -> tuple:
+        """The arguments of a step entry from `disp` on: the same in ops_frame_design_step_f32 and ops_frame_group_step_f32."""
+        return (fwd.disp.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(), lam.data_ptr(), _ptr(self.loss_extra), fwd.status.data_ptr(),
+                _ptr(status_adj), _ptr(self.weights), self.aggregate,
                 *(t.data_ptr() for t in (self.exp_avg, self.exp_avg_sq, self.best, self.patience_cnt, self.epochs, self.active, self.last,
                                          self.case_penalty, self.governing)),
-                _ptr(self.grad), ctypes.byref(self.hp), self.schedule.data_ptr(), stream)
+                _ptr(self.grad), ctypes.byref(self.hp), self.schedule.data_ptr(), torch.cuda.current_stream(self.I.device).cuda_stream)
+
+    def step(self, fwd: FrameCaseSolution, lam: torch.Tensor, status_adj: Optional[torch.Tensor]) -> None:
+        """The design step on the current stream (`lam` [G,C,Nn,3]: the adjoint displacements)."""
+        topo, I = self.topo, self.I
+        with torch.cuda.device(I.device):
+            rc = _cabi.load().ops_frame_design_step_f32(
+                I.shape[0], self.C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), frames._adjoint_tables(topo).conn.data_ptr(),
+                I.data_ptr(), self.I64.data_ptr(), *self._step_tail(fwd, lam, status_adj))
         _cabi.check(rc, "ops_frame_design_step_f32")
+
+
+def _checked_problem(topo: FrameTopology, loads, element_loads, n_designs, V0, v_name: str, n_vars: int, aggregate: str, weights,
+                     who: str) -> types.SimpleNamespace:
+    """The arguments of a designs run, checked in the order every entry keeps: every shape before any device, then where everything
+    lives (with the loads, on the topology's device).  `V0`: the optional start [G, n_vars] (I0, or X0 of the grouped loop).
+    -> G, C, dev, loads, w (the checked tensors), agg, w_c (`_checked_aggregate`), nbytes (`_factor_bytes`)."""
+    if torch.is_tensor(loads) and loads.dim() == 4:
+        G = int(loads.shape[0])
+    elif V0 is not None and torch.is_tensor(V0) and V0.dim() == 2:
+        G = int(V0.shape[0])
+    elif n_designs is not None:
+        G = int(n_designs)
+    else:
+        raise ValueError(f"loads shared by the designs ([C, Nn, 3]) need n_designs or {v_name} to say how many designs there are")
+    if n_designs is not None and int(n_designs) != G:
+        raise ValueError(f"n_designs = {n_designs}, but loads / {v_name} are for {G} designs")
+    dev = topo.device
+    frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, who, shape_only=True)
+    C = int(loads.shape[-3])
+    if element_loads is not None:
+        frames._checked_cases("element_loads", element_loads, G, (topo.Ne, 2), dev, who, shape_only=True)
+        if element_loads.shape[-3] != C:
+            raise ValueError(f"element_loads has {element_loads.shape[-3]} cases, loads has {C}")
+    if V0 is not None and (not torch.is_tensor(V0) or tuple(V0.shape) != (G, n_vars)):
+        raise ValueError(f"{v_name} must be [{G}, {n_vars}]")
+    _checked_limits(topo, C)
+    agg, w_c = _checked_aggregate(aggregate, weights, C)
+    nbytes = _factor_bytes(topo, G)
+    if loads.is_cuda and topo.device.type == "cuda" and topo.device.index in (None, loads.device.index):
+        dev = loads.device
+    loads = frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, who)
+    w = None if element_loads is None else frames._checked_cases("element_loads", element_loads, G, (topo.Ne, 2), dev, who)
+    if V0 is not None and not V0.is_cuda:
+        raise RuntimeError(f"{who} needs GPU tensors: openpystruct_amd has no CPU fallback")
+    return types.SimpleNamespace(G=G, C=C, dev=dev, loads=loads, w=w, agg=agg, w_c=w_c, nbytes=nbytes)
+
+
+class _Forward:
+    """Steps 1 to 3 of an epoch -- the keeping solve on I64, the forward re-solve of all G*C rows, the correction of their forces for
+    the element loads -- with every buffer allocated here, once: `factor`, `fwd`, and the cases' right-hand sides with the consistent
+    element loads, which do not depend on I (frame_resolve's rows, formed once).  Calling it launches the three on the current stream."""
+
+    def __init__(self, topo: FrameTopology, I64: torch.Tensor, q: types.SimpleNamespace):
+        lib = _cabi.load()
+        G, C, dev, loads, w = q.G, q.C, q.dev, q.loads, q.w
+        Nn, Ne = topo.Nn, topo.Ne
+        self.topo, self.G, self.C, self.dev = topo, G, C, dev
+        self.factor = FrameFactor(topo, I64, torch.empty(q.nbytes, dtype=torch.uint8, device=dev), frames._empty_solution(topo, G, dev))
+        self.fwd = frames._empty_case_solution(topo, G, C, dev)
+        if G == 0:
+            return
+        adj = frames._adjoint_tables(topo)
+        shared = loads.dim() == 3 and (w is None or w.dim() == 3)
+        if loads.dim() == 3 and not shared:
+            loads = loads.expand(G, C, Nn, 3).contiguous()
+        self.w_rows, self.wbs = (topo.d_w, 0) if w is None else (w, 2 * Ne)
+        if w is not None and w.dim() == 3:            # the correction of the forces runs on all G * C rows
+            self.w_rows = w.expand(G, C, Ne, 2).contiguous()
+        rows = C if shared else G * C
+        self.fwd_rhs = torch.empty((rows, Nn, 3), dtype=torch.float64, device=dev)
+        w_rhs = w if (shared and w is not None) else self.w_rows
+        with torch.cuda.device(dev):
+            rc = lib.ops_frame_load_rhs_f64(rows, Nn, Ne, topo.d_geo.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), loads.data_ptr(),
+                                            3 * Nn, w_rhs.data_ptr(), self.wbs, self.fwd_rhs.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream)
+        _cabi.check(rc, "ops_frame_load_rhs_f64")
+        self.rbs = 0 if shared else C * Nn * 3
+        self.has_w = w is not None or bool(np.any(topo.wy != 0.0) or np.any(topo.wx != 0.0))
+
+    def __call__(self) -> None:
+        topo, fwd, dev = self.topo, self.fwd, self.dev
+        _factor_launch(self.factor)               # its own solution (the topology's loads) is not used
+        frames._resolve_launch(self.factor, self.C, self.fwd_rhs, self.rbs, fwd)
+        if self.has_w:
+            with torch.cuda.device(dev):
+                rc = _cabi.load().ops_frame_load_forces_f64(self.G * self.C, topo.Ne, topo.d_geo.data_ptr(), self.w_rows.data_ptr(), self.wbs,
+                                                            fwd.status.data_ptr(), fwd.forces.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(),
+                                                            torch.cuda.current_stream(dev).cuda_stream)
+            _cabi.check(rc, "ops_frame_load_forces_f64")
 
 
 def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loads: Optional[torch.Tensor] = None, *,
@@ -148,84 +243,24 @@ def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loa
     Returns `FrameDesigns` (I, the last solve of every design and case, epochs, governing case, case penalties)."""
     cfg = cfg or FrameConfig()
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
-    # every shape before any device
-    if torch.is_tensor(loads) and loads.dim() == 4:
-        G = int(loads.shape[0])
-    elif I0 is not None and torch.is_tensor(I0) and I0.dim() == 2:
-        G = int(I0.shape[0])
-    elif n_designs is not None:
-        G = int(n_designs)
-    else:
-        raise ValueError("loads shared by the designs ([C, Nn, 3]) need n_designs or I0 to say how many designs there are")
-    if n_designs is not None and int(n_designs) != G:
-        raise ValueError(f"n_designs = {n_designs}, but loads / I0 are for {G} designs")
-    dev = topo.device
-    frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, "optimize_frame_designs", shape_only=True)
-    C = int(loads.shape[-3])
-    if element_loads is not None:
-        frames._checked_cases("element_loads", element_loads, G, (topo.Ne, 2), dev, "optimize_frame_designs", shape_only=True)
-        if element_loads.shape[-3] != C:
-            raise ValueError(f"element_loads has {element_loads.shape[-3]} cases, loads has {C}")
-    if I0 is not None and (not torch.is_tensor(I0) or tuple(I0.shape) != (G, topo.Ne)):
-        raise ValueError(f"I0 must be [{G}, {topo.Ne}]")
-    _checked_limits(topo, C)
-    agg, w_c = _checked_aggregate(aggregate, weights, C)
-    nbytes = _factor_bytes(topo, G)
-    # then where everything lives: with the loads, on the topology's device
-    if loads.is_cuda and topo.device.type == "cuda" and topo.device.index in (None, loads.device.index):
-        dev = loads.device
-    loads = frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, "optimize_frame_designs")
-    w = None if element_loads is None else frames._checked_cases("element_loads", element_loads, G, (topo.Ne, 2), dev, "optimize_frame_designs")
-    if I0 is not None and not I0.is_cuda:
-        raise RuntimeError("optimize_frame_designs needs GPU tensors: openpystruct_amd has no CPU fallback")
-
-    lib = _cabi.load()
-    Nn, Ne = topo.Nn, topo.Ne
-    f64 = dict(dtype=torch.float64, device=dev)
+    q = _checked_problem(topo, loads, element_loads, n_designs, I0, "I0", topo.Ne, aggregate, weights, "optimize_frame_designs")
+    G, C, dev = q.G, q.C, q.dev
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
     hp = frames._sizing_params(cfg, n_max)
-    I = I0.to(dtype=torch.float32, device=dev).clone() if I0 is not None else torch.full((G, Ne), cfg.I0, dtype=torch.float32, device=dev)
-    st = _DesignState(topo, I, I.double(), C, hp, obj, agg, w_c, with_grad=False)
-    factor = FrameFactor(topo, st.I64, torch.empty(nbytes, dtype=torch.uint8, device=dev), frames._empty_solution(topo, G, dev))
-    fwd = frames._empty_case_solution(topo, G, C, dev)
+    I = I0.to(dtype=torch.float32, device=dev).clone() if I0 is not None else torch.full((G, topo.Ne), cfg.I0, dtype=torch.float32, device=dev)
+    st = _DesignState(topo, I, I.double(), C, hp, obj, q.agg, q.w_c, with_grad=False)
+    fw = _Forward(topo, st.I64, q)
     if G == 0:
-        return FrameDesigns(I, fwd, st.epochs, st.governing, st.case_penalty)
-    # the cases' right-hand sides with the consistent element loads: they do not depend on I (frame_resolve's rows, formed once)
-    adj = frames._adjoint_tables(topo)
-    shared = loads.dim() == 3 and (w is None or w.dim() == 3)
-    if loads.dim() == 3 and not shared:
-        loads = loads.expand(G, C, Nn, 3).contiguous()
-    w_rows, wbs = (topo.d_w, 0) if w is None else (w, 2 * Ne)
-    if w is not None and w.dim() == 3:            # the correction of the forces runs on all G * C rows
-        w_rows = w.expand(G, C, Ne, 2).contiguous()
-    rows = C if shared else G * C
-    fwd_rhs = torch.empty((rows, Nn, 3), **f64)
-    w_rhs = w if (shared and w is not None) else w_rows
-    with torch.cuda.device(dev):
-        rc = lib.ops_frame_load_rhs_f64(rows, Nn, Ne, topo.d_geo.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), loads.data_ptr(),
-                                        3 * Nn, w_rhs.data_ptr(), wbs, fwd_rhs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _cabi.check(rc, "ops_frame_load_rhs_f64")
-    rbs = 0 if shared else C * Nn * 3
-    has_w = w is not None or bool(np.any(topo.wy != 0.0) or np.any(topo.wx != 0.0))
-
-    def forward():
-        _factor_launch(factor)                    # its own solution (the topology's loads) is not used
-        frames._resolve_launch(factor, C, fwd_rhs, rbs, fwd)
-        if has_w:
-            with torch.cuda.device(dev):
-                rc = lib.ops_frame_load_forces_f64(G * C, Ne, topo.d_geo.data_ptr(), w_rows.data_ptr(), wbs, fwd.status.data_ptr(),
-                                                   fwd.forces.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(),
-                                                   torch.cuda.current_stream(dev).cuda_stream)
-            _cabi.check(rc, "ops_frame_load_forces_f64")
+        return FrameDesigns(I, fw.fwd, st.epochs, st.governing, st.case_penalty)
 
     def epoch():
-        forward()
-        st.gradient_and_step(factor, fwd)
+        fw()
+        st.gradient_and_step(fw.factor, fw.fwd)
 
     run_epochs(epoch, n_max, poll_every, st.active, (lambda: loss_history.append(st.last.clone())) if loss_history is not None else None)
-    forward()                                     # I64 froze when a design stopped: every design's last solve, all C cases
+    fw()                                          # I64 froze when a design stopped: every design's last solve, all C cases
     torch.cuda.synchronize(dev)
-    return FrameDesigns(I, fwd, st.epochs, st.governing, st.case_penalty)
+    return FrameDesigns(I, fw.fwd, st.epochs, st.governing, st.case_penalty)
 
 
 def frame_design_gradient(factor: FrameFactor, sol: FrameCaseSolution, hp, *, aggregate: str = "sum",
