@@ -13,17 +13,12 @@ import re
 import types
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
-HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd.h")
-# additions to the C ABI that change no declaration of HEADER_PATH (and so not OPS_AMD_ABI_VERSION) have headers of their own
-EXTENSION_HEADER_PATHS = (os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_vjp.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_sizing.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_loads.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_multicase.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_cases.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_designs.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_design_loss.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_frame_groups.h"),
-                          os.path.join(os.path.dirname(_PKG), "include", "openpystruct_amd_sizing_grad.h"))
+_INCLUDE = os.path.join(os.path.dirname(_PKG), "include")
+HEADER_PATH = os.path.join(_INCLUDE, "openpystruct_amd.h")
+# additions to the C ABI that change no declaration of HEADER_PATH (and so not OPS_AMD_ABI_VERSION) have headers of their own, read in
+# this order: a header may name the structs of the headers before it
+EXTENSION_HEADER_PATHS = tuple(os.path.join(_INCLUDE, f"openpystruct_amd_{name}.h") for name in (
+    "frame_vjp", "frame_sizing", "frame_loads", "sizing_multicase", "frame_cases", "frame_designs", "design_loss", "frame_groups", "sizing_grad"))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
 

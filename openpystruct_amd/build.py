@@ -17,26 +17,12 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib", "libopenpystruct_amd.so")
-SOURCES = [os.path.join(CSRC, "beam_solve.hip"), os.path.join(CSRC, "beam_fat.hip"), os.path.join(CSRC, "sizing_step.hip"),
-           os.path.join(CSRC, "beam_residual.hip"), os.path.join(CSRC, "frame_solve.hip"),
-           os.path.join(CSRC, "stencil_bn.hip"), os.path.join(CSRC, "flat_adam.hip"),
-           os.path.join(CSRC, "fused_loss.hip"), os.path.join(CSRC, "fused_bn.hip"), os.path.join(CSRC, "input_prep.hip"),
-           os.path.join(CSRC, "mlp_block.hip"), os.path.join(CSRC, "seq_block.hip"), os.path.join(CSRC, "seq_layer.hip"), os.path.join(CSRC, "mem_bench.hip"), os.path.join(CSRC, "case_draw.hip"),
-           os.path.join(CSRC, "bayes_mlp.hip"), os.path.join(CSRC, "beam_vjp.hip"), os.path.join(CSRC, "frame_vjp.hip"), os.path.join(CSRC, "sizing_grad.hip"),
-           os.path.join(CSRC, "frame_sizing_grad.hip"), os.path.join(CSRC, "frame_loads.hip"),
-           os.path.join(CSRC, "sizing_multicase.hip"), os.path.join(CSRC, "frame_designs.hip"), os.path.join(CSRC, "design_loss.hip"),
-           os.path.join(CSRC, "frame_groups.hip"),
-           os.path.join(CSRC, "library.hip")]
-HEADERS = [os.path.join(CSRC, "lane_common.hpp"), os.path.join(CSRC, "library.hpp"), os.path.join(CSRC, "repack_tiles.hpp"), os.path.join(CSRC, "beam_math.hpp"), os.path.join(CSRC, "beam_adjoint.hpp"), os.path.join(CSRC, "beam_io.hpp"), os.path.join(CSRC, "call_counter.hpp"), os.path.join(CSRC, "dropout_stream.hpp"), os.path.join(CSRC, "input_noise.hpp"), os.path.join(CSRC, "sizing_math.hpp"), os.path.join(CSRC, "frame_wave.hpp"), os.path.join(CSRC, "frame_pack.hpp"), os.path.join(CSRC, "frame_coop.hpp"), os.path.join(CSRC, "frame_adjoint.hpp"), os.path.join(ROOT, "include", "openpystruct_amd.h"),
-           os.path.join(ROOT, "include", "openpystruct_amd_frame_vjp.h"), os.path.join(CSRC, "sizing_grad_math.hpp"),
-           os.path.join(ROOT, "include", "openpystruct_amd_sizing_grad.h"), os.path.join(CSRC, "frame_sizing_math.hpp"),
-           os.path.join(ROOT, "include", "openpystruct_amd_frame_sizing.h"), os.path.join(CSRC, "frame_loads.hpp"),
-           os.path.join(ROOT, "include", "openpystruct_amd_frame_loads.h"), os.path.join(CSRC, "frame_stream.hpp"),
-           os.path.join(CSRC, "sizing_multicase_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_sizing_multicase.h"),
-           os.path.join(CSRC, "frame_resolve.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_frame_cases.h"),
-           os.path.join(CSRC, "frame_designs_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_frame_designs.h"),
-           os.path.join(CSRC, "design_loss_math.hpp"), os.path.join(ROOT, "include", "openpystruct_amd_design_loss.h"),
-           os.path.join(ROOT, "include", "openpystruct_amd_frame_groups.h")]
+# one object per file; library.hip (the library's own state, no kernels) last
+SOURCES = [os.path.join(CSRC, name) for name in (
+    "beam_solve.hip", "beam_fat.hip", "sizing_step.hip", "beam_residual.hip", "frame_solve.hip", "stencil_bn.hip", "flat_adam.hip",
+    "fused_loss.hip", "fused_bn.hip", "input_prep.hip", "mlp_block.hip", "seq_block.hip", "seq_layer.hip", "mem_bench.hip", "case_draw.hip",
+    "bayes_mlp.hip", "beam_vjp.hip", "frame_vjp.hip", "sizing_grad.hip", "frame_sizing_grad.hip", "frame_loads.hip", "sizing_multicase.hip",
+    "frame_designs.hip", "design_loss.hip", "frame_groups.hip", "library.hip")]
 ARCH = "gfx950"
 # Per-file flags.  beam_fat.hip: its kernels take their leading arguments as plain scalars and pointers (beam_io.hpp, RowsHead)
 # so that the hardware can hand them to every wave in SGPRs at launch; the compiler does that for up to 14 dwords when asked.

@@ -303,12 +303,6 @@ __global__ __launch_bounds__(256) void mc_moments_kernel(int S, long M, int N, c
 
 using namespace opsamd;
 
-static int bayes_check() {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
-}
-
 static int bayes_layers(int nlayers, const ops_bayes_layer* layers, int eps_mode, bool fold, BayesLayers* L, long* most) {
   if (nlayers < 1 || nlayers > OPS_BAYES_MAX_LAYERS || !layers) return OPS_AMD_ERR_INVALID_ARG;
   if (eps_mode != OPS_BAYES_EPS_DRAW && eps_mode != OPS_BAYES_EPS_WRITE && eps_mode != OPS_BAYES_EPS_READ) return OPS_AMD_ERR_INVALID_ARG;
@@ -337,7 +331,7 @@ extern "C" int ops_bayes_sample_f32(int nlayers, const ops_bayes_layer* layers, 
   long nb = (most + 255) / 256;
   nb = nb > 512 ? 512 : nb;
   hipLaunchKernelGGL(bayes_sample_kernel, dim3((unsigned)nb, (unsigned)nlayers), dim3(256), 0, (hipStream_t)stream, L, seed, counter, eps_mode);
-  return bayes_check();
+  return launch_status();
 }
 
 extern "C" int ops_bayes_grad_fold_f32(int nlayers, const ops_bayes_layer* layers, unsigned long long seed, const unsigned long long* counter,
@@ -352,7 +346,7 @@ extern "C" int ops_bayes_grad_fold_f32(int nlayers, const ops_bayes_layer* layer
   nb = nb > 512 ? 512 : nb;
   hipLaunchKernelGGL(bayes_fold_kernel, dim3((unsigned)nb, (unsigned)nlayers), dim3(256), 0, (hipStream_t)stream, L, seed, counter, eps_mode,
                      kl_scale, prior_mu, inv_pv);
-  return bayes_check();
+  return launch_status();
 }
 
 static size_t mc_lin1_lds(int K) { return sizeof(float) * ((size_t)MC_JT * (K + 1) + MC_JT + (size_t)MC_RT * (K + 1)); }
@@ -376,12 +370,12 @@ extern "C" int ops_bayes_mlp_mc_f32(const ops_bayes_mc_args* a, void* stream) {
   // (set on every launch: the attribute belongs to the device current at the call, and the call costs nothing next to the launch)
   hipError_t e = hipFuncSetAttribute((const void*)bayes_mc_lin1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l1);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*)bayes_mc_lin2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
+  if (e != hipSuccess) return launch_status(e);
   hipLaunchKernelGGL(bayes_mc_lin1_kernel, dim3((unsigned)((a->H + MC_JT - 1) / MC_JT), (unsigned)a->S), dim3(MC_THREADS), l1, (hipStream_t)stream, *a);
-  const int rc = bayes_check();
+  const int rc = launch_status();
   if (rc != OPS_AMD_OK) return rc;
   hipLaunchKernelGGL(bayes_mc_lin2_kernel, dim3((unsigned)((a->N + MC_NT - 1) / MC_NT), (unsigned)a->S), dim3(MC_THREADS), l2, (hipStream_t)stream, *a);
-  return bayes_check();
+  return launch_status();
 }
 
 extern "C" int ops_mc_moments_f32(int S, long M, int N, const float* preds, const float* scale, const float* center, float* mean, float* std,
@@ -390,5 +384,5 @@ extern "C" int ops_mc_moments_f32(int S, long M, int N, const float* preds, cons
   long nb = (M + 255) / 256;
   nb = nb > 2048 ? 2048 : nb;
   hipLaunchKernelGGL(mc_moments_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, S, M, N, preds, scale, center, mean, std);
-  return bayes_check();
+  return launch_status();
 }

@@ -14,6 +14,7 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -329,7 +330,7 @@ extern "C" int ops_beam_residual_f64(int B, int Ne, const double* x, long x_bstr
   const long n = (long)B * (Ne + 1);
   hipLaunchKernelGGL(beam_residual_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, v, theta,
                      Fy, wy, wy_bstride, rv, rt);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int ops_beam_residual_vjp_f64(int B, int Ne, const double* x, long x_bstride, const double* E, long E_bstride,
@@ -346,7 +347,7 @@ extern "C" int ops_beam_residual_vjp_f64(int B, int Ne, const double* x, long x_
   hipLaunchKernelGGL(beam_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, gv, gt, scratch_v, scratch_t);
   hipLaunchKernelGGL(beam_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, scratch_v, scratch_t, dv, dt);
   hipLaunchKernelGGL(beam_dI_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, s, p, scratch_v, scratch_t, v, theta, dI);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 static int phys_args(const ops_physics_loss_args* q, PhysArgs& a) {
@@ -370,7 +371,7 @@ extern "C" int ops_physics_loss_fwd(const ops_physics_loss_args* q, void* stream
   const int nwg = (int)(((long)a.B * (a.Ne + 1) + 255) / 256);
   hipLaunchKernelGGL(phys_loss_fwd_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(phys_loss_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, nwg);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 extern "C" int ops_physics_loss_bwd(const ops_physics_loss_args* q, void* stream) {
   PhysArgs a;
@@ -379,5 +380,5 @@ extern "C" int ops_physics_loss_bwd(const ops_physics_loss_args* q, void* stream
   if (!a.dpreds) return OPS_AMD_ERR_INVALID_ARG;
   const int nwg = (int)(((long)a.B * (a.Ne + 1) + 255) / 256);
   hipLaunchKernelGGL(phys_loss_bwd_kernel, dim3((unsigned)nwg), dim3(256), 0, (hipStream_t)stream, a, nwg);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }

@@ -652,11 +652,7 @@ static int solve_impl(int B, int Ne, const double* x, long x_bstride, const doub
   else if (t->P == 64 && t->M == 4) err = launch<64, 4>(p, shared, s);
   else if (t->P == 64 && t->M == 8) err = launch<64, 8>(p, shared, s);
   else if (t->P == 64 && t->M == 16) err = launch<64, 16>(p, shared, s);
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return launch_status(err);
 }
 
 int ops_beam_solve_batched_f64(int B, int Ne, const double* x, long x_bstride, const double* E, long E_bstride,
@@ -684,7 +680,8 @@ int ops_beam_sizing_epoch_f32(int B, int Ne, const double* x, long x_bstride, co
   if (Ne > 128) return OPS_AMD_ERR_UNSUPPORTED;       // two elements per lane in the fused step
   if (!I || !I_last || !exp_avg || !exp_avg_sq || !best_loss || !patience_cnt || !epochs_run || !active || !last_loss || !hp)
     return OPS_AMD_ERR_INVALID_ARG;
-  const SizingArgs sz{I, nullptr, I_last, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, nullptr, nullptr, *hp, schedule};
+  SizingArgs sz = sizing_args(I, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, hp);
+  sz.I_last = I_last; sz.schedule = schedule;
   // the fused kernel carries the cases' optimiser state in registers next to the solve: the 16-lane tiling (three waves
   // per SIMD) beats the 8-lane one at every batch size here (2e5 cases: 0.095 vs 0.104 s), unlike the plain solve
   if (tiling == 0 && Ne + 1 <= 16 * 7) {

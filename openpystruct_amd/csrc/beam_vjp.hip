@@ -172,9 +172,5 @@ extern "C" int ops_beam_solve_vjp_f64(int B, int Ne, const double* x, long x_bst
   else if (t->P == 64 && t->M == 4) err = launch_vjp<64, 4>(p, s);
   else if (t->P == 64 && t->M == 8) err = launch_vjp<64, 8>(p, s);
   else err = launch_vjp<64, 16>(p, s);
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return launch_status(err);
 }

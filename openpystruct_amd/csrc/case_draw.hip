@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "../../include/openpystruct_amd.h"
 #include "dropout_stream.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -142,5 +143,5 @@ extern "C" int ops_sizing_draw_cases_f64(long B, unsigned long long first_case, 
   a.L_min = L_min; a.L_max = L_max; a.max_force = max_force; a.min_force = min_force;
   a.Ls = L; a.r_nodes = roller_nodes; a.nr = n_rollers; a.f_nodes = force_nodes; a.kf = n_forces; a.f_vals = force_values; a.fix = fix; a.Fy = Fy;
   hipLaunchKernelGGL(case_draw_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }

@@ -15,6 +15,7 @@
 #include "../../include/openpystruct_amd_design_loss.h"
 #include "design_loss_math.hpp"
 #include "lane_common.hpp"
+#include "sizing_math.hpp"
 
 namespace opsamd {
 
@@ -167,7 +168,7 @@ static int design_args(const ops_design_loss_args* a) {
   if (!a || a->B < 0 || a->C < 1 || a->Ne < 1 || a->G < 0) return OPS_AMD_ERR_INVALID_ARG;
   if (a->aggregate != 0 && a->aggregate != 1) return OPS_AMD_ERR_INVALID_ARG;
   if (a->aggregate == 1 && a->weights) return OPS_AMD_ERR_INVALID_ARG;
-  if (a->Ne > 512 || a->C > kDesignMaxCases) return OPS_AMD_ERR_UNSUPPORTED;
+  if (a->Ne > kSizingMaxElems || a->C > kDesignMaxCases) return OPS_AMD_ERR_UNSUPPORTED;
   if (a->preds && a->ldp < a->Ne) return OPS_AMD_ERR_INVALID_ARG;
   if ((a->rows || a->ref || a->Fy_src) && a->G < 1 && a->B > 0) return OPS_AMD_ERR_INVALID_ARG;
   if (!a->rows && (a->ref || a->Fy_src) && a->G < a->B) return OPS_AMD_ERR_INVALID_ARG;
@@ -188,7 +189,7 @@ extern "C" int ops_design_loss_prep(const ops_design_loss_args* q, void* stream)
   if (!q->preds || !q->I_scale || !q->I_mean || !q->I_rows || !q->Fy_src || !q->Fy_rows) return OPS_AMD_ERR_INVALID_ARG;
   const long n = (long)q->B * (q->Ne + 1);
   hipLaunchKernelGGL(design_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *q);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int ops_design_loss_finish(const ops_design_loss_args* q, const ops_sizing_params* hp, void* stream) {
@@ -209,5 +210,5 @@ extern "C" int ops_design_loss_finish(const ops_design_loss_args* q, const ops_s
   else if (q->Ne <= 256) hipLaunchKernelGGL(design_finish_kernel<4>, dim3(grid), dim3(256), 0, s, *q, kc);
   else hipLaunchKernelGGL(design_finish_kernel<8>, dim3(grid), dim3(256), 0, s, *q, kc);
   if (q->value) hipLaunchKernelGGL(design_value_kernel, dim3(1), dim3(256), 0, s, *q);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }

@@ -18,6 +18,7 @@
 #include "../../include/openpystruct_amd.h"
 #include "repack_tiles.hpp"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -154,7 +155,7 @@ static int adam_step(long n, float* params, const float* grads, float* exp_avg, 
     const int tot = tj.first[2 * rp->nmat];
     hipLaunchKernelGGL(repack_tiles_kernel, dim3((unsigned)((tot + 3) / 4)), dim3(256), 0, s, params, *rp, tj);
   }
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int ops_flat_clip_adam_step_f32(long n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const float* lr,

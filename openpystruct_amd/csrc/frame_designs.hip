@@ -16,8 +16,6 @@
 
 namespace opsamd {
 
-constexpr int kFrameDesignMaxCases = 64;
-
 struct FrameDesignRhsParams : FrameStreamTopo {      // B: the G * C rows
   int C;
   const double* I;                 // [G,Ne]
@@ -59,12 +57,6 @@ __global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_design_rhs_kernel(co
   }
 }
 
-template <int W>
-static int launch_design_rhs(const FrameDesignRhsParams& p, void* stream) {
-  constexpr int RPW = 64 / W;
-  return frame_stream_launch(frame_design_rhs_kernel<W>, p, (((long)p.B + RPW - 1) / RPW) * 64, stream);
-}
-
 template <int K, bool SUM>
 __global__ __launch_bounds__(256) void frame_design_step_kernel(int G, int Ne, const FrameDesignArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -86,27 +78,19 @@ extern "C" int ops_frame_design_rhs_f64(int G, int C, int n_nodes, int n_elems, 
                                         const ops_sizing_params* hp, const ops_frame_sizing_objective* obj,
                                         const uint8_t* active, double* rhs, double* loss_extra, void* stream) {
   if (G < 0 || C < 1 || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
-  if (n_elems > 512 || C > kFrameDesignMaxCases || (long)G * C > 0x7fffffffL) return OPS_AMD_ERR_UNSUPPORTED;
+  if (n_elems > kSizingMaxElems || C > kFrameDesignMaxCases || (long)G * C > 0x7fffffffL) return OPS_AMD_ERR_UNSUPPORTED;
   if (G == 0) return OPS_AMD_OK;
   if (!elem_geo || !elem_EA || !elem_E || !node_elem_ptr || !node_elem_idx || !I64 || !disp || !V || !M || !hp || !obj || !rhs)
     return OPS_AMD_ERR_INVALID_ARG;
-  if (!(obj->alpha_sway >= 0.0) || !(obj->alpha_deflection >= 0.0)) return OPS_AMD_ERR_INVALID_ARG;
-  if (obj->alpha_sway > 0.0 && !(obj->sway_limit > 0.0)) return OPS_AMD_ERR_INVALID_ARG;
-  if (obj->alpha_deflection > 0.0 && !(obj->deflection_limit > 0.0)) return OPS_AMD_ERR_INVALID_ARG;
-  if (obj->alpha_sway + obj->alpha_deflection > 0.0 && !loss_extra) return OPS_AMD_ERR_INVALID_ARG;
+  if (const int rc = frame_sizing_obj_check(obj, loss_extra); rc != OPS_AMD_OK) return rc;
   FrameDesignRhsParams p{};
   p.B = G * C; p.Nn = n_nodes; p.Ne = n_elems; p.C = C;
   p.elem_geo = elem_geo; p.elem_EA = elem_EA; p.elem_E = elem_E;
   p.node_elem_ptr = node_elem_ptr; p.node_elem_idx = node_elem_idx;
   p.I = I64; p.disp = disp; p.V = V; p.M = M;
-  p.o = frame_sizing_obj(hp->alpha_moment, hp->alpha_shear, hp->E, hp->bend_eps, hp->G, hp->area_coef, obj->alpha_sway,
-                         obj->sway_limit, obj->alpha_deflection, obj->deflection_limit);
+  p.o = frame_sizing_obj(hp, obj->alpha_sway, obj->sway_limit, obj->alpha_deflection, obj->deflection_limit);
   p.active = active; p.rhs = rhs; p.loss_extra = loss_extra;
-  if (n_nodes <= 4) return launch_design_rhs<4>(p, stream);
-  if (n_nodes <= 8) return launch_design_rhs<8>(p, stream);
-  if (n_nodes <= 16) return launch_design_rhs<16>(p, stream);
-  if (n_nodes <= 32) return launch_design_rhs<32>(p, stream);
-  return launch_design_rhs<64>(p, stream);
+  return frame_rhs_width(n_nodes, [&](auto W) { return frame_stream_launch(frame_design_rhs_kernel<W>, p, frame_rhs_threads(p.B, W), stream); });
 }
 
 extern "C" int ops_frame_design_step_f32(int G, int C, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
@@ -117,30 +101,16 @@ extern "C" int ops_frame_design_step_f32(int G, int C, int n_nodes, int n_elems,
                                          int32_t* patience_cnt, int32_t* epochs_run, uint8_t* active, float* last_loss,
                                          float* case_penalty, int32_t* governing, double* grad_out, const ops_sizing_params* hp,
                                          const float* schedule, void* stream) {
-  if (G < 0 || C < 1 || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
-  if (aggregate != 0 && aggregate != 1) return OPS_AMD_ERR_INVALID_ARG;
-  if (aggregate == 1 && weights) return OPS_AMD_ERR_INVALID_ARG;
-  if (n_elems > 512 || C > kFrameDesignMaxCases || (long)G * C > 0x7fffffffL) return OPS_AMD_ERR_UNSUPPORTED;
-  if (G == 0) return OPS_AMD_OK;
-  if (!elem_geo || !elem_E || !conn || !I || !I64 || !disp || !V || !M || !lambda || !exp_avg || !exp_avg_sq || !best_loss ||
-      !patience_cnt || !epochs_run || !active || !last_loss || !hp)
-    return OPS_AMD_ERR_INVALID_ARG;
-  const unsigned grid = (unsigned)((G + 3) / 4);
-  // the objective without its hinges, as ops_frame_sizing_grad_f64 forms it: they reach the gradient through lambda alone
-  const SizingObj o = frame_sizing_obj(hp->alpha_moment, hp->alpha_shear, hp->E, hp->bend_eps, hp->G, hp->area_coef, 0.0, 0.0, 0.0, 0.0).sway;
-  const FrameDesignArgs a{{I, I64, nullptr, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, nullptr,
-                           nullptr, *hp, schedule},
-                          C, aggregate, n_nodes, o, elem_geo, elem_E, conn, disp, lambda, V, M, loss_extra, status_fwd, status_adj,
-                          weights, case_penalty, governing, grad_out};
-  const int K = n_elems <= 64 ? 1 : n_elems <= 128 ? 2 : n_elems <= 256 ? 4 : 8;
+  FrameDesignArgs a{};
+  const int rc = frame_design_args(G, C, n_nodes, n_elems, elem_geo, elem_E, conn, I, I64, disp, V, M, lambda, loss_extra, status_fwd,
+                                   status_adj, weights, aggregate, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active,
+                                   last_loss, case_penalty, governing, grad_out, hp, schedule, &a);
+  if (rc != OPS_AMD_OK || G == 0) return rc;
+  // K as a value and a table of template-ids, not the dispatch with a lambda: the order in which the eight kernels are named here
+  // is their order in the code object, and that is kept
+  const int K = sizing_lane_elems(n_elems);
   void (*kernel)(int, int, const FrameDesignArgs) = nullptr;
   if (aggregate == 0) kernel = K == 1 ? frame_design_step_kernel<1, true> : K == 2 ? frame_design_step_kernel<2, true> : K == 4 ? frame_design_step_kernel<4, true> : frame_design_step_kernel<8, true>;
   else kernel = K == 1 ? frame_design_step_kernel<1, false> : K == 2 ? frame_design_step_kernel<2, false> : K == 4 ? frame_design_step_kernel<4, false> : frame_design_step_kernel<8, false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, G, n_elems, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return launch_wave_rows(kernel, G, stream, G, n_elems, a);
 }

@@ -349,5 +349,37 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
   fd_store_design(lane, g, a, w, stop);
 }
 
+// ---- host side: what ops_frame_design_step_f32 and ops_frame_group_step_f32 (csrc/frame_groups.hip) check and fill alike ----
+
+constexpr int kFrameDesignMaxCases = 64;
+
+// The design step's refusals, in its order, and its arguments in *a.  OPS_AMD_OK with G == 0: nothing to launch, *a not filled.
+inline int frame_design_args(int G, int C, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E, const int32_t* conn,
+                             float* I, double* I64, const double* disp, const double* V, const double* M, const double* lambda,
+                             const double* loss_extra, const int32_t* status_fwd, const int32_t* status_adj, const double* weights,
+                             int aggregate, float* exp_avg, float* exp_avg_sq, float* best_loss, int32_t* patience_cnt,
+                             int32_t* epochs_run, uint8_t* active, float* last_loss, float* case_penalty, int32_t* governing,
+                             double* grad_out, const ops_sizing_params* hp, const float* schedule, FrameDesignArgs* a) {
+  if (G < 0 || C < 1 || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
+  if (aggregate != 0 && aggregate != 1) return OPS_AMD_ERR_INVALID_ARG;
+  if (aggregate == 1 && weights) return OPS_AMD_ERR_INVALID_ARG;
+  if (n_elems > kSizingMaxElems || C > kFrameDesignMaxCases || (long)G * C > 0x7fffffffL) return OPS_AMD_ERR_UNSUPPORTED;
+  if (G == 0) return OPS_AMD_OK;
+  if (!elem_geo || !elem_E || !conn || !I || !I64 || !disp || !V || !M || !lambda || !exp_avg || !exp_avg_sq || !best_loss ||
+      !patience_cnt || !epochs_run || !active || !last_loss || !hp)
+    return OPS_AMD_ERR_INVALID_ARG;
+  // the objective without its hinges, as ops_frame_sizing_grad_f64 forms it: they reach the gradient through lambda alone
+  *a = FrameDesignArgs{};
+  a->s = sizing_args(I, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, hp);
+  a->s.I64 = I64; a->s.schedule = schedule;
+  a->C = C; a->aggregate = aggregate; a->Nn = n_nodes;
+  a->o = frame_sizing_obj(hp, 0.0, 0.0, 0.0, 0.0).sway;
+  a->elem_geo = elem_geo; a->elem_E = elem_E; a->conn = conn;
+  a->disp = disp; a->lambda = lambda; a->V = V; a->M = M; a->loss_extra = loss_extra;
+  a->status_fwd = status_fwd; a->status_adj = status_adj; a->weights = weights;
+  a->case_penalty = case_penalty; a->governing = governing; a->grad_out = grad_out;
+  return OPS_AMD_OK;
+}
+
 }  // namespace opsamd
 #endif

@@ -138,32 +138,19 @@ extern "C" int ops_frame_group_step_f32(int G, int C, int n_nodes, int n_elems, 
                                         float* exp_avg_sq, float* best_loss, int32_t* patience_cnt, int32_t* epochs_run, uint8_t* active,
                                         float* last_loss, float* case_penalty, int32_t* governing, double* grad_out,
                                         const ops_sizing_params* hp, const float* schedule, void* stream) {
-  if (G < 0 || C < 1 || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
-  if (n_groups < 1 || n_groups > n_elems) return OPS_AMD_ERR_INVALID_ARG;
-  if (aggregate != 0 && aggregate != 1) return OPS_AMD_ERR_INVALID_ARG;
-  if (aggregate == 1 && weights) return OPS_AMD_ERR_INVALID_ARG;
-  if (n_elems > 512 || C > ops_frame_design_max_cases() || (long)G * C > 0x7fffffffL) return OPS_AMD_ERR_UNSUPPORTED;
-  if (G == 0) return OPS_AMD_OK;
-  if (!elem_geo || !elem_E || !conn || !elem_group || !group_ptr || !group_elems || !X || !I || !I64 || !disp || !V || !M || !lambda ||
-      !exp_avg || !exp_avg_sq || !best_loss || !patience_cnt || !epochs_run || !active || !last_loss || !hp)
-    return OPS_AMD_ERR_INVALID_ARG;
-  const unsigned grid = (unsigned)((G + 3) / 4);
-  // the objective without its hinges, as ops_frame_design_step_f32 forms it
-  const SizingObj o = frame_sizing_obj(hp->alpha_moment, hp->alpha_shear, hp->E, hp->bend_eps, hp->G, hp->area_coef, 0.0, 0.0, 0.0, 0.0).sway;
-  const FrameGroupArgs a{{{I, I64, nullptr, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, nullptr, nullptr,
-                           *hp, schedule},
-                          C, aggregate, n_nodes, o, elem_geo, elem_E, conn, disp, lambda, V, M, loss_extra, status_fwd, status_adj,
-                          weights, case_penalty, governing, grad_out},
-                         n_groups, elem_group, group_ptr, group_elems, X};
-  const int K = n_elems <= 64 ? 1 : n_elems <= 128 ? 2 : n_elems <= 256 ? 4 : 8;
+  if (n_groups < 1 || n_groups > n_elems) return OPS_AMD_ERR_INVALID_ARG;      // then the design step's refusals, in its order
+  FrameGroupArgs a{};
+  const int rc = frame_design_args(G, C, n_nodes, n_elems, elem_geo, elem_E, conn, I, I64, disp, V, M, lambda, loss_extra, status_fwd,
+                                   status_adj, weights, aggregate, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active,
+                                   last_loss, case_penalty, governing, grad_out, hp, schedule, &a.d);
+  if (rc != OPS_AMD_OK || G == 0) return rc;
+  if (!elem_group || !group_ptr || !group_elems || !X) return OPS_AMD_ERR_INVALID_ARG;
+  a.Ng = n_groups; a.elem_group = elem_group; a.group_ptr = group_ptr; a.group_elems = group_elems; a.X = X;
+  // K as a value and a table of template-ids, not the dispatch with a lambda: the order in which the eight kernels are named here
+  // is their order in the code object, and that is kept
+  const int K = sizing_lane_elems(n_elems);
   void (*kernel)(int, int, const FrameGroupArgs) = nullptr;
   if (aggregate == 0) kernel = K == 1 ? frame_group_step_kernel<1, true> : K == 2 ? frame_group_step_kernel<2, true> : K == 4 ? frame_group_step_kernel<4, true> : frame_group_step_kernel<8, true>;
   else kernel = K == 1 ? frame_group_step_kernel<1, false> : K == 2 ? frame_group_step_kernel<2, false> : K == 4 ? frame_group_step_kernel<4, false> : frame_group_step_kernel<8, false>;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, G, n_elems, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return launch_wave_rows(kernel, G, stream, G, n_elems, a);
 }

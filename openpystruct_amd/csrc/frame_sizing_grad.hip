@@ -72,17 +72,6 @@ __global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_sizing_grad_kernel(c
   });
 }
 
-// a wavefront (64 threads) per 64 / G frames: frame_stream_launch's one thread per row with 64 rows to a group of frames
-template <int G>
-static int launch_rhs(const FrameSizingParams& p, void* stream) {
-  constexpr int FPW = 64 / G;
-  return frame_stream_launch(frame_sizing_rhs_kernel<G>, p, (((long)p.B + FPW - 1) / FPW) * 64, stream);
-}
-
-static FrameSizingObj objective(const ops_sizing_params* hp, double aS, double s_lim, double aD, double d_lim) {
-  return frame_sizing_obj(hp->alpha_moment, hp->alpha_shear, hp->E, hp->bend_eps, hp->G, hp->area_coef, aS, s_lim, aD, d_lim);
-}
-
 }  // namespace opsamd
 
 using namespace opsamd;
@@ -96,22 +85,15 @@ extern "C" int ops_frame_sizing_rhs_f64(int B, int n_nodes, int n_elems, const d
   if (B == 0) return OPS_AMD_OK;
   if (!elem_geo || !elem_EA || !elem_E || !node_elem_ptr || !node_elem_idx || !I || !disp || !V || !M || !hp || !obj || !rhs)
     return OPS_AMD_ERR_INVALID_ARG;
-  if (!(obj->alpha_sway >= 0.0) || !(obj->alpha_deflection >= 0.0)) return OPS_AMD_ERR_INVALID_ARG;
-  if (obj->alpha_sway > 0.0 && !(obj->sway_limit > 0.0)) return OPS_AMD_ERR_INVALID_ARG;
-  if (obj->alpha_deflection > 0.0 && !(obj->deflection_limit > 0.0)) return OPS_AMD_ERR_INVALID_ARG;
-  if (obj->alpha_sway + obj->alpha_deflection > 0.0 && !loss_extra) return OPS_AMD_ERR_INVALID_ARG;
+  if (const int rc = frame_sizing_obj_check(obj, loss_extra); rc != OPS_AMD_OK) return rc;
   FrameSizingParams p{};
   p.B = B; p.Nn = n_nodes; p.Ne = n_elems;
   p.elem_geo = elem_geo; p.elem_EA = elem_EA; p.elem_E = elem_E;
   p.node_elem_ptr = node_elem_ptr; p.node_elem_idx = node_elem_idx;
   p.I = I; p.disp = disp; p.V = V; p.M = M;
-  p.o = objective(hp, obj->alpha_sway, obj->sway_limit, obj->alpha_deflection, obj->deflection_limit);
+  p.o = frame_sizing_obj(hp, obj->alpha_sway, obj->sway_limit, obj->alpha_deflection, obj->deflection_limit);
   p.active = active; p.rhs = rhs; p.loss_extra = loss_extra;
-  if (n_nodes <= 4) return launch_rhs<4>(p, stream);
-  if (n_nodes <= 8) return launch_rhs<8>(p, stream);
-  if (n_nodes <= 16) return launch_rhs<16>(p, stream);
-  if (n_nodes <= 32) return launch_rhs<32>(p, stream);
-  return launch_rhs<64>(p, stream);
+  return frame_rhs_width(n_nodes, [&](auto W) { return frame_stream_launch(frame_sizing_rhs_kernel<W>, p, frame_rhs_threads(B, W), stream); });
 }
 
 extern "C" int ops_frame_sizing_grad_f64(int B, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
@@ -126,7 +108,7 @@ extern "C" int ops_frame_sizing_grad_f64(int B, int n_nodes, int n_elems, const 
   p.B = B; p.Nn = n_nodes; p.Ne = n_elems;
   p.elem_geo = elem_geo; p.elem_E = elem_E; p.conn = conn;
   p.I = I; p.disp = disp; p.V = V; p.M = M; p.lambda = lambda;
-  p.o = objective(hp, 0.0, 0.0, 0.0, 0.0);      // the hinges reach the gradient through lambda alone
+  p.o = frame_sizing_obj(hp, 0.0, 0.0, 0.0, 0.0);      // the hinges reach the gradient through lambda alone
   p.active = active; p.status_fwd = status_fwd; p.status_adj = status_adj; p.grad = grad;
   return frame_stream_launch(frame_sizing_grad_kernel, p, (long)B * n_elems, stream);
 }

@@ -66,3 +66,41 @@ FA_HD double fs_elem_grad(const FrameSizingObj& o, int n_nodes, int n_elems, con
 }
 
 }  // namespace opsamd
+
+#if defined(__HIPCC__)
+// ---- host side of the entries that take the objective (frame_sizing_grad.hip, frame_designs.hip, frame_groups.hip) ----
+#include <type_traits>
+
+#include "../../include/openpystruct_amd_frame_sizing.h"
+
+namespace opsamd {
+
+// the objective from the C structs; (0, 0, 0, 0): without its hinges, which reach a gradient through lambda alone
+inline FrameSizingObj frame_sizing_obj(const ops_sizing_params* hp, double aS, double s_lim, double aD, double d_lim) {
+  return frame_sizing_obj(hp->alpha_moment, hp->alpha_shear, hp->E, hp->bend_eps, hp->G, hp->area_coef, aS, s_lim, aD, d_lim);
+}
+
+// what an adjoint right-hand-side entry refuses of its objective: a weight below zero (or NaN), a weighted hinge without a
+// positive limit, or without `loss_extra` to take its value
+inline int frame_sizing_obj_check(const ops_frame_sizing_objective* obj, const double* loss_extra) {
+  if (!(obj->alpha_sway >= 0.0) || !(obj->alpha_deflection >= 0.0)) return OPS_AMD_ERR_INVALID_ARG;
+  if (obj->alpha_sway > 0.0 && !(obj->sway_limit > 0.0)) return OPS_AMD_ERR_INVALID_ARG;
+  if (obj->alpha_deflection > 0.0 && !(obj->deflection_limit > 0.0)) return OPS_AMD_ERR_INVALID_ARG;
+  if (obj->alpha_sway + obj->alpha_deflection > 0.0 && !loss_extra) return OPS_AMD_ERR_INVALID_ARG;
+  return OPS_AMD_OK;
+}
+
+// f(std::integral_constant<int, W>) with W the lanes per row of the right-hand-side kernels: the smallest of 4 .. 64 that is
+// >= min(n_nodes, 64).  frame_rhs_threads: a wavefront per 64 / W rows, as frame_stream_launch's count of one thread per row
+inline long frame_rhs_threads(int B, int W) { return (((long)B + 64 / W - 1) / (64 / W)) * 64; }
+template <class F>
+int frame_rhs_width(int n_nodes, F f) {
+  if (n_nodes <= 4) return f(std::integral_constant<int, 4>{});
+  if (n_nodes <= 8) return f(std::integral_constant<int, 8>{});
+  if (n_nodes <= 16) return f(std::integral_constant<int, 16>{});
+  if (n_nodes <= 32) return f(std::integral_constant<int, 32>{});
+  return f(std::integral_constant<int, 64>{});
+}
+
+}  // namespace opsamd
+#endif

@@ -844,13 +844,13 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
   const int kd = eff_kd(half_bandwidth);
   const size_t lds_bytes = frame_lds_resident_bytes(n_eq, kd);
   int devid = 0;
-  if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
+  if (const int rc = current_device(&devid); rc != OPS_AMD_OK) return rc;
   {
     hipError_t e = set_lds_limit_once<frame_solve_kernel>(devid, (int)LDS_MAX);
     if (e == hipSuccess) e = set_lds_limit_once<frame_assemble_kernel>(devid, (int)LDS_MAX);
     if (e == hipSuccess) e = set_lds_limit_once<frame_factor_big_kernel>(devid, (int)LDS_MAX);
     if (e == hipSuccess) e = set_lds_limit_once<frame_wide_kernel>(devid, (int)LDS_MAX);
-    if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
+    if (e != hipSuccess) return launch_status(e);
   }
   FrameParams p{B, n_nodes, n_elems, n_eq, kd, elem_geo, elem_EA, elem_E, elem_w, elem_eq, node_eq,
                 I, loads, loads_bstride, disp, forces, V, M, status};
@@ -868,13 +868,11 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
     if (!workspace || workspace_bytes < need) return OPS_AMD_ERR_INVALID_ARG;
     hipLaunchKernelGGL(frame_assemble_kernel, dim3((unsigned)B), dim3(256), ((size_t)slab * ld + (size_t)n3) * sizeof(double), s, p, (double*)workspace, (int)slab);
     hipLaunchKernelGGL(frame_wide_kernel, dim3((unsigned)B), dim3(1024), lds_wide, s, p, (double*)workspace);
-    return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+    return launch_status();
   }
   if (fam == FAM_PACK || fam == FAM_COOP || fam == FAM_WAVE) {
     if (!workspace || workspace_bytes < need || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
-    const hipError_t e = launch_tuned(fam, kd, p, workspace, s, reuse_plan, devid);
-    if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-    return OPS_AMD_OK;
+    return launch_status(launch_tuned(fam, kd, p, workspace, s, reuse_plan, devid));
   }
   const bool resident = lds_bytes <= LDS_MAX;
   int T, pp_use;
@@ -889,10 +887,10 @@ extern "C" int ops_frame_solve_batched_f64_ex(int B, int n_nodes, int n_elems, i
     const size_t lds_asm = ((size_t)FRAME_SLAB_MAX * ld + (size_t)n3) * sizeof(double);
     hipLaunchKernelGGL(frame_assemble_kernel, dim3((unsigned)B), dim3(256), lds_asm, s, p, (double*)workspace, FRAME_SLAB_MAX);
     hipLaunchKernelGGL(frame_factor_big_kernel, dim3((unsigned)B), dim3((unsigned)T), lds2, s, p, (double*)workspace, pp_use);
-    return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+    return launch_status();
   }
   hipLaunchKernelGGL(frame_solve_kernel, dim3((unsigned)B), dim3((unsigned)T), lds_bytes, s, p, pp_use);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -940,7 +938,7 @@ extern "C" int ops_frame_factor_solve_f64(int B, int n_nodes, int n_elems, int n
   const int kd = eff_kd(half_bandwidth);
   if (factor_bytes < keep_bytes(B, n_eq, kd) || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
   int devid = 0;
-  if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
+  if (const int rc = current_device(&devid); rc != OPS_AMD_OK) return rc;
   FrameParams p{B, n_nodes, n_elems, n_eq, kd, elem_geo, elem_EA, elem_E, elem_w, elem_eq, node_eq,
                 I, loads, loads_bstride, disp, forces, V, M, status};
   hipStream_t s = (hipStream_t)stream;
@@ -950,8 +948,7 @@ extern "C" int ops_frame_factor_solve_f64(int B, int n_nodes, int n_elems, int n
     case 52: e = launch_wave_keep<52>(p, factor, s, devid); break;
     default: e = launch_wave_keep<56>(p, factor, s, devid); break;
   }
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return launch_status(e);
 }
 
 template <int W, int NR>
@@ -991,7 +988,7 @@ extern "C" int ops_frame_resolve_f64(int B, int C, int n_nodes, int n_elems, int
   if (factor_bytes < keep_bytes(B, n_eq, kd) || n_elems > ne_bound(n_eq)) return OPS_AMD_ERR_INVALID_ARG;
   if ((long)B * ((C + 3) / 4 + 1) > 0x7fffffffL || (long)B * C > 0x7fffffffL) return OPS_AMD_ERR_INVALID_ARG;    // one workgroup per (frame, pass)
   int devid = 0;
-  if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return OPS_AMD_ERR_LAUNCH;
+  if (const int rc = current_device(&devid); rc != OPS_AMD_OK) return rc;
   FrameParams p{B, n_nodes, n_elems, n_eq, kd, elem_geo, elem_EA, elem_E, nullptr, elem_eq, node_eq,
                 I, rhs, rhs_bstride, disp, forces, V, M, status};
   hipStream_t s = (hipStream_t)stream;
@@ -1001,6 +998,5 @@ extern "C" int ops_frame_resolve_f64(int B, int C, int n_nodes, int n_elems, int
     case 52: e = launch_resolve_nr<52>(p, C, factor_status, factor, s, devid); break;
     default: e = launch_resolve_nr<56>(p, C, factor_status, factor, s, devid); break;
   }
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return launch_status(e);
 }

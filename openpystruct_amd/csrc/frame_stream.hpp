@@ -48,12 +48,7 @@ int frame_stream_launch(void (*kernel)(const Params), const Params& p, long rows
   const long need = (rows + FRAME_STREAM_BLOCK - 1) / FRAME_STREAM_BLOCK;
   const unsigned grid = (unsigned)(need < FRAME_STREAM_MAX_GRID ? need : FRAME_STREAM_MAX_GRID);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(FRAME_STREAM_BLOCK), 0, (hipStream_t)stream, p);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return launch_status();
 }
 
 }  // namespace opsamd

@@ -28,6 +28,7 @@
 #include "dropout_stream.hpp"
 #include "call_counter.hpp"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -274,7 +275,7 @@ extern "C" int ops_fused_bn_act_fwd(int B, int F, const void* x1, const void* x2
   const FbArgs a{B, F, x1, x2, x3, act_is_bf16, gamma, beta, eps, momentum, training, running_mean, running_var, num_batches_tracked,
                  slope, use_act, p_drop, seed, call_counter, y, z_save, mean_save, rstd_save, mask};
   hipLaunchKernelGGL(fused_bn_fwd_kernel, dim3((unsigned)((F + FB_CW - 1) / FB_CW)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int ops_fused_bn_act_bwd(int B, int F, const void* dy, int act_is_bf16, const void* z, const float* mean, const float* rstd,
@@ -285,5 +286,5 @@ extern "C" int ops_fused_bn_act_bwd(int B, int F, const void* dy, int act_is_bf1
   if (p_drop > 0.0f && !mask) return OPS_AMD_ERR_INVALID_ARG;
   const FbBwdArgs a{B, F, dy, act_is_bf16, z, mean, rstd, gamma, beta, slope, use_act, p_drop, mask, dz, dgamma, dbeta};
   hipLaunchKernelGGL(fused_bn_bwd_kernel, dim3((unsigned)((F + FB_CW - 1) / FB_CW)), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }

@@ -13,6 +13,7 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -115,5 +116,5 @@ extern "C" int ops_surrogate_loss_grad_sum_f32(int B, int C, int nI, int nD, con
                      max_constraint, box_weight, rel_penalty, 1e-8f, grad, (double*)workspace);
   hipLaunchKernelGGL(fused_loss_finish_kernel, dim3(1), dim3(64), 0, s, B, C, nI, nD, (const double*)workspace, G, alpha, alpha0, box_weight,
                      rel_penalty, loss, loss_sum);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }

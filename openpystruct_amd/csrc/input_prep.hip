@@ -10,6 +10,7 @@
 #include "call_counter.hpp"
 #include "input_noise.hpp"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -78,5 +79,5 @@ extern "C" int ops_gather_rows_noise_targets_f32(int B, long F, const float* X, 
     hipLaunchKernelGGL(opsamd::gather_noise_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, F, X, idx, sigma, seed, counter, out, out_is_bf16, Y, C, Yout);
   else
     hipLaunchKernelGGL(opsamd::gather_noise_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, F, X, idx, sigma, seed, counter, out, out_is_bf16, Y, C, Yout);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return opsamd::launch_status();
 }

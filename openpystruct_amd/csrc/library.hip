@@ -1,8 +1,10 @@
 // Library-wide host state: the last error (ops_amd_last_error), the ABI version, and the library options -- ops_amd_set_option is the one place
-// a caller (tests, A/B scripts) steers the dispatch; no environment variable is read.  No kernels.
+// a caller (tests, A/B scripts) steers the dispatch; no environment variable is read.  library.hpp's launch_status and
+// launch_refused, the one place that returns OPS_AMD_ERR_LAUNCH, store their message here.  No kernels.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdio>
 #include <string_view>
 
 #include "../../include/openpystruct_amd.h"
@@ -21,6 +23,16 @@ void set_last_error(const char* msg) {
   int k = 0;
   for (; msg && msg[k] && k < 255; ++k) g_last_error[k] = msg[k];
   g_last_error[k] = 0;
+}
+
+int current_device(int* devid) {
+  const hipError_t e = hipGetDevice(devid);
+  if (e != hipSuccess) {
+    char why[256];
+    snprintf(why, sizeof(why), "hipGetDevice failed: %s", hipGetErrorString(e));
+    return launch_refused(why);
+  }
+  return *devid >= 0 && *devid < 64 ? OPS_AMD_OK : launch_refused("device index outside 0..63");
 }
 
 int deterministic_mode() { return g_deterministic.load(std::memory_order_relaxed); }

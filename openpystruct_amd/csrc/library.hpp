@@ -4,9 +4,19 @@
 
 #include <atomic>
 
+#include "../../include/openpystruct_amd.h"
+
 namespace opsamd {
 
 void set_last_error(const char* msg);   // what ops_amd_last_error() reports (per thread)
+
+// The one epilogue of an entry that launches: every OPS_AMD_ERR_LAUNCH of the library is returned through one of these, so the code
+// never comes without its message.  hipSuccess: OPS_AMD_OK and the stored message untouched; else HIP's text for `e` is stored.
+// Inline over set_last_error: a file built alone (mlp_block.hip under MB_EXP) needs that one symbol and no more, as before.
+inline int launch_refused(const char* why) { set_last_error(why); return OPS_AMD_ERR_LAUNCH; }      // a launch the entry would not make
+inline int launch_status(hipError_t e) { return e != hipSuccess ? launch_refused(hipGetErrorString(e)) : OPS_AMD_OK; }
+inline int launch_status() { return launch_status(hipGetLastError()); }
+int current_device(int* devid);         // OPS_AMD_OK and the current device's index, or the refusal: hipGetDevice failed, an index outside 0 .. 63
 
 // library options (ops_amd_set_option / ops_amd_get_option)
 int deterministic_mode();               // "deterministic": fixed-order reductions in the Transformer-Diffusion step's gradient launches

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/openpystruct_amd.h"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -46,5 +47,5 @@ extern "C" int ops_hbm_copy16(const void* src, void* dst, size_t bytes, int non_
     hipLaunchKernelGGL(opsamd::copy16_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const opsamd::v4u*)src, (opsamd::v4u*)dst, n16);
   else
     hipLaunchKernelGGL(opsamd::copy16_kernel<0>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const opsamd::v4u*)src, (opsamd::v4u*)dst, n16);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return opsamd::launch_status();
 }

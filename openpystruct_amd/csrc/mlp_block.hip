@@ -846,9 +846,7 @@ extern "C" int ops_mlp_strip_launch(const ops_mlp_strip_args* args, void* stream
     default: MB_LAUNCH(-1, 0, 0); break;
   }
 #undef MB_LAUNCH
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return launch_status();
 }
 
 static int wgrad_launch(int nprob, const ops_mlp_wgrad_problem* problems, const WgradNorm* nm, int32_t* nparts, void* stream) {
@@ -873,9 +871,7 @@ static int wgrad_launch(int nprob, const ops_mlp_wgrad_problem* problems, const 
   } else {
     hipLaunchKernelGGL(mlp_wgrad_kernel<false>, dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, tb, WgradNorm{});
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return launch_status();
 }
 
 extern "C" int ops_mlp_wgrad_group(int nprob, const ops_mlp_wgrad_problem* problems, void* stream) {
@@ -912,9 +908,7 @@ extern "C" int ops_mlp_repack_weights(int nmat, const ops_mlp_repack_entry* entr
   long nb = (tot + 255) / 256;
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(mlp_repack_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, tb);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return launch_status();
 }
 
 static int gather_launch(int B, int F, const float* X, const long long* idx, const float* sigma, unsigned long long seed,
@@ -932,9 +926,7 @@ static int gather_launch(int B, int F, const float* X, const long long* idx, con
     hipLaunchKernelGGL(mlp_gather_noise_kernel<false>, dim3((unsigned)ngb), dim3(256), 0, (hipStream_t)stream, B, F, X, idx, sigma, seed,
                        counter, (uint16_t*)out, ld, (uint16_t*)out_t, nfb, Y, C, targets_t, ngb, nullptr, AdamRepack{}, TileJobs{});
   }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return launch_status();
 }
 
 extern "C" int ops_mlp_gather_noise(int B, int F, const float* X, const long long* idx, const float* sigma, unsigned long long seed,

@@ -422,13 +422,6 @@ __global__ __launch_bounds__(256) void act_dropout_bwd_kernel(long n, const uint
 
 using namespace opsamd;
 
-static int sq_check(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  (void)what;
-  return OPS_AMD_OK;
-}
-
 // samples per workgroup: as many as 512 threads (one per sample x head x token) and 64 KB of LDS hold
 static int sa_samples_per_wg(int S, int H, size_t lds_per_sample) {
   int nb = SA_THREADS / (S * H);
@@ -450,7 +443,7 @@ extern "C" int ops_seq_attention_fwd(int Bn, int S, int H, int dh, const void* q
   const dim3 grid((unsigned)((Bn + NB - 1) / NB));
   if (DHP == 16) hipLaunchKernelGGL(seq_attention_fwd_kernel<16>, grid, dim3(SA_THREADS), lds, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(seq_attention_fwd_kernel<32>, grid, dim3(SA_THREADS), lds, (hipStream_t)stream, a);
-  return sq_check("seq_attention_fwd_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_seq_attention_bwd(int Bn, int S, int H, int dh, const void* qkv, const void* dctx, void* dqkv, float p_drop,
@@ -467,7 +460,7 @@ extern "C" int ops_seq_attention_bwd(int Bn, int S, int H, int dh, const void* q
   const dim3 grid((unsigned)((Bn + NB - 1) / NB));
   if (DHP == 16) hipLaunchKernelGGL(seq_attention_bwd_kernel<16>, grid, dim3(SA_THREADS), lds, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(seq_attention_bwd_kernel<32>, grid, dim3(SA_THREADS), lds, (hipStream_t)stream, a);
-  return sq_check("seq_attention_bwd_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_dropout_add_layernorm_fwd(int T, int d, const void* x, const void* res, int res_is_bf16, const float* gamma, const float* beta,
@@ -485,7 +478,7 @@ extern "C" int ops_dropout_add_layernorm_fwd(int T, int d, const void* x, const 
   int grid = (T + 3) / 4;
   if (grid > 2048) grid = 2048;
   hipLaunchKernelGGL(dropout_add_ln_fwd_kernel, dim3((unsigned)grid), dim3(LN_THREADS), 0, (hipStream_t)stream, a);
-  return sq_check("dropout_add_ln_fwd_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_dropout_add_layernorm_bwd(int T, int d, const float* dy32, const void* dy16, const float* z, const float* mean, const float* rstd,
@@ -500,7 +493,7 @@ extern "C" int ops_dropout_add_layernorm_bwd(int T, int d, const float* dy32, co
   a.rstd = (float*)rstd; a.dy32 = dy32; a.dy16 = (const uint16_t*)dy16; a.dx = (uint16_t*)dx; a.dres = dres; a.dgamma = dgamma; a.dbeta = dbeta;
   hipLaunchKernelGGL(dropout_add_ln_bwd_kernel, dim3((unsigned)((T + LN_ROWS_PER_WG - 1) / LN_ROWS_PER_WG)), dim3(LN_BWD_THREADS), 0,
                      (hipStream_t)stream, a);
-  return sq_check("dropout_add_ln_bwd_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_act_dropout_fwd(long n, const void* x, void* y, float slope, float p_drop, unsigned long long seed, unsigned long long* counter,
@@ -510,7 +503,7 @@ extern "C" int ops_act_dropout_fwd(long n, const void* x, void* y, float slope, 
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(act_dropout_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, n, (const uint16_t*)x, (uint16_t*)y, slope,
                      p_drop, seed, counter, used_call);
-  return sq_check("act_dropout_fwd_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_act_dropout_bwd(long n, const void* x, const void* dy, void* dx, float slope, float p_drop, unsigned long long seed,
@@ -520,7 +513,7 @@ extern "C" int ops_act_dropout_bwd(long n, const void* x, const void* dy, void* 
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(act_dropout_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, n, (const uint16_t*)x, (const uint16_t*)dy,
                      (uint16_t*)dx, slope, p_drop, seed, (const unsigned long long*)used_call);
-  return sq_check("act_dropout_bwd_kernel");
+  return launch_status();
 }
 
 // ================================================================================================================================
@@ -789,7 +782,7 @@ extern "C" int ops_linear_wgrad_accumulate(int T, int N, int K, const void* dY, 
   const int det = opsamd::deterministic_mode();
   const dim3 grid((unsigned)((N + 63) / 64), (unsigned)((K + 63) / 64), (unsigned)opsamd::wg_row_splits(T, det));
   hipLaunchKernelGGL(opsamd::wgrad_tn_kernel, grid, dim3(256), 0, (hipStream_t)stream, T, N, K, (const uint16_t*)dY, (const uint16_t*)X, dW, dbias, det);
-  return sq_check("wgrad_tn_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_linear_wgrad_accumulate_group(int nprob, const ops_wgrad_problem* problems, void* stream) {
@@ -851,7 +844,7 @@ extern "C" int ops_linear_wgrad_accumulate_group(int nprob, const ops_wgrad_prob
   }
   const unsigned grid = g.nunit > 0 ? 8u * (unsigned)g.qmax : (unsigned)tot;
   hipLaunchKernelGGL(opsamd::wgrad_tn_group_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, g);
-  return sq_check("wgrad_tn_group_kernel");
+  return launch_status();
 }
 
 // ================================================================================================================================
@@ -969,7 +962,7 @@ extern "C" int ops_diffusion_noise(long rows, int d, const float* x, const long 
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(opsamd::diffusion_noise_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, rows, d, x, t, eps, alpha_cumprod, xn32,
                      (uint16_t*)xn16, sa, sb);
-  return sq_check("diffusion_noise_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_diffusion_noise_draw(long rows, int d, int T, const float* x, const float* alpha_cumprod, unsigned long long seed,
@@ -980,7 +973,7 @@ extern "C" int ops_diffusion_noise_draw(long rows, int d, int T, const float* x,
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(opsamd::diffusion_noise_draw_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, rows, d, T, x, alpha_cumprod, seed,
                      counter, xn32, (uint16_t*)xn16, sa, sb, t_out, eps_out);
-  return sq_check("diffusion_noise_draw_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_diffusion_combine_fwd(int B, int Nc, int d, const void* m, const float* xn32, const float* sa, const float* sb, const float* cls,
@@ -990,7 +983,7 @@ extern "C" int ops_diffusion_combine_fwd(int B, int Nc, int d, const void* m, co
   if (nb > 2048) nb = 2048;
   hipLaunchKernelGGL(opsamd::diffusion_combine_fwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, B, Nc, d, (const uint16_t*)m, xn32,
                      sa, sb, cls, pe, z, (uint16_t*)z16);
-  return sq_check("diffusion_combine_fwd_kernel");
+  return launch_status();
 }
 
 extern "C" int ops_diffusion_combine_bwd(int B, int Nc, int d, const float* g, const void* g16, const float* sa, const float* sb, void* dm, float* dcls,
@@ -1001,5 +994,5 @@ extern "C" int ops_diffusion_combine_bwd(int B, int Nc, int d, const float* g, c
   if (nb < 64) nb = 64;
   hipLaunchKernelGGL(opsamd::diffusion_combine_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, B, Nc, d, g, (const uint16_t*)g16, sa, sb,
                      (uint16_t*)dm, dcls);
-  return sq_check("diffusion_combine_bwd_kernel");
+  return launch_status();
 }

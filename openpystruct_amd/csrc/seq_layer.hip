@@ -1490,9 +1490,7 @@ extern "C" int ops_tfd_encoder_layer_fwd(const ops_tfd_layer_args* a, void* stre
   const int spw = 16 / a->S;
   const unsigned grid = (unsigned)((a->Bn + spw - 1) / spw);
   hipLaunchKernelGGL(opsamd::tfd_layer_fwd_kernel, dim3(grid), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 static int tfd_layer_args_check(const ops_tfd_layer_args* a) {
@@ -1515,9 +1513,7 @@ extern "C" int ops_tfd_encoder_layer_pair_fwd(const ops_tfd_layer_args* a, const
   const int spw = 16 / a->S;
   const unsigned grid = (unsigned)((a->Bn + spw - 1) / spw);
   hipLaunchKernelGGL(opsamd::tfd_layer_pair_fwd_kernel, dim3(grid), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a, *b);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 extern "C" int ops_tfd_encoder_layer_bwd(const ops_tfd_layer_bwd_args* a, void* stream) {
@@ -1537,9 +1533,7 @@ extern "C" int ops_tfd_encoder_layer_bwd(const ops_tfd_layer_bwd_args* a, void* 
   if (a->g32 && a->g16) hipLaunchKernelGGL((opsamd::tfd_layer_bwd_kernel<true, true>), grid, block, 0, (hipStream_t)stream, *a);
   else if (a->g32) hipLaunchKernelGGL((opsamd::tfd_layer_bwd_kernel<true, false>), grid, block, 0, (hipStream_t)stream, *a);
   else hipLaunchKernelGGL((opsamd::tfd_layer_bwd_kernel<false, true>), grid, block, 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 extern "C" int ops_tfd_encoder_layer_pair_bwd(const ops_tfd_layer_bwd_args* a, const ops_tfd_layer_bwd_args* b, void* stream) {
@@ -1562,9 +1556,7 @@ extern "C" int ops_tfd_encoder_layer_pair_bwd(const ops_tfd_layer_bwd_args* a, c
   if (a->g32 && a->g16) hipLaunchKernelGGL((opsamd::tfd_layer_pair_bwd_kernel<true, true>), grid, block, 0, (hipStream_t)stream, *a, *b);
   else if (a->g32) hipLaunchKernelGGL((opsamd::tfd_layer_pair_bwd_kernel<true, false>), grid, block, 0, (hipStream_t)stream, *a, *b);
   else hipLaunchKernelGGL((opsamd::tfd_layer_pair_bwd_kernel<false, true>), grid, block, 0, (hipStream_t)stream, *a, *b);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 extern "C" int ops_tfd_head_fwd(const ops_tfd_head_args* a, void* stream) {
@@ -1576,9 +1568,7 @@ extern "C" int ops_tfd_head_fwd(const ops_tfd_head_args* a, void* stream) {
     return OPS_AMD_ERR_UNSUPPORTED;
   if (a->targets && (!a->grad || !a->loss_part || !a->alpha || ((uintptr_t)a->grad & 7) != 0)) return OPS_AMD_ERR_INVALID_ARG;
   hipLaunchKernelGGL(opsamd::tfd_head_fwd_kernel, dim3((unsigned)((a->B + 15) / 16)), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 extern "C" int ops_tfd_head_bwd(const ops_tfd_head_bwd_args* a, void* stream) {
@@ -1591,9 +1581,7 @@ extern "C" int ops_tfd_head_bwd(const ops_tfd_head_bwd_args* a, void* stream) {
   if (a->loss_part && (!a->alpha || !a->loss)) return OPS_AMD_ERR_INVALID_ARG;
   if (opsamd::deterministic_mode() && !a->ln_part) return OPS_AMD_ERR_INVALID_ARG;      // (atomics would add the workgroups in arrival order)
   hipLaunchKernelGGL(opsamd::tfd_head_bwd_kernel, dim3((unsigned)((a->B + 15) / 16)), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 extern "C" int ops_tfd_front_fwd(const ops_tfd_front_args* a, void* stream) {
@@ -1606,9 +1594,7 @@ extern "C" int ops_tfd_front_fwd(const ops_tfd_front_args* a, void* stream) {
     return OPS_AMD_ERR_UNSUPPORTED;
   const long rows = (long)a->B * a->Nc;
   hipLaunchKernelGGL(opsamd::tfd_front_fwd_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }
 
 extern "C" int ops_tfd_front_bwd(const ops_tfd_front_bwd_args* a, void* stream) {
@@ -1618,7 +1604,5 @@ extern "C" int ops_tfd_front_bwd(const ops_tfd_front_bwd_args* a, void* stream) 
     return OPS_AMD_ERR_UNSUPPORTED;
   const long rows = (long)a->B * a->Nc;
   hipLaunchKernelGGL(opsamd::tfd_front_bwd_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(64 * opsamd::SL_NW), 0, (hipStream_t)stream, *a, opsamd::deterministic_mode());
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { opsamd::set_last_error(hipGetErrorString(e)); return OPS_AMD_ERR_LAUNCH; }
-  return OPS_AMD_OK;
+  return opsamd::launch_status();
 }

@@ -192,11 +192,7 @@ extern "C" int ops_beam_sizing_grad_f64(int B, int Ne, const double* x, long x_b
   else if (t->P == 64 && t->M == 4) err = launch_grad<64, 4>(p, s);
   else if (t->P == 64 && t->M == 8) err = launch_grad<64, 8>(p, s);
   else err = launch_grad<64, 16>(p, s);
-  if (err != hipSuccess) {
-    set_last_error(hipGetErrorString(err));
-    return OPS_AMD_ERR_LAUNCH;
-  }
-  return OPS_AMD_OK;
+  return launch_status(err);
 }
 
 extern "C" int ops_beam_sizing_step_grad_f32(int B, int Ne, float* I, double* I64, const double* V, const double* M,
@@ -204,13 +200,12 @@ extern "C" int ops_beam_sizing_step_grad_f32(int B, int Ne, float* I, double* I6
                                              float* best_loss, int32_t* patience_cnt, int32_t* epochs_run, uint8_t* active,
                                              float* last_loss, float* V32, float* M32, const ops_sizing_params* hp,
                                              const float* schedule, void* stream) {
-  if (B < 0 || Ne < 1 || Ne > 512) return Ne > 512 ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
+  if (B < 0 || Ne < 1 || Ne > kSizingMaxElems) return Ne > kSizingMaxElems ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
   if (B == 0) return OPS_AMD_OK;
   if (!I || !I64 || !V || !M || !grad || !exp_avg || !exp_avg_sq || !best_loss || !patience_cnt || !epochs_run || !active ||
       !last_loss || ((V32 == nullptr) != (M32 == nullptr)) || !hp)
     return OPS_AMD_ERR_INVALID_ARG;
-  const unsigned grid = (unsigned)((B + 3) / 4);
-  const SizingArgs a{I, I64, nullptr, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, V32, M32, *hp, schedule};
-  hipLaunchKernelGGL(sizing_step_grad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, Ne, V, M, grad, loss_extra, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  SizingArgs a = sizing_args(I, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, hp);
+  a.I64 = I64; a.V32 = V32; a.M32 = M32; a.schedule = schedule;
+  return launch_wave_rows(sizing_step_grad_kernel, B, stream, B, Ne, V, M, grad, loss_extra, a);
 }

@@ -1,6 +1,8 @@
 // One optimiser epoch of ONE case, executed by a whole 64-lane wavefront: shared by the stand-alone step kernel
 // (csrc/sizing_step.hip) and the fused solve + step kernel (csrc/beam_solve.hip).  See sizing_step.hip for the reference
 // lines this follows.  getV(e) / getM(e): this case's shear / moment of element e, already rounded to float32.
+// At the end, host only: what the step entries of the family state once (the element cap, the SizingArgs maker, the launch of a
+// wavefront per row, the elements-per-lane dispatch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,6 +11,7 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -148,6 +151,40 @@ __device__ __forceinline__ void sizing_case(int lane, long b, int Ne, const Sizi
   CaseRegs<8> r;
   load_case<8>(lane, b, Ne, a, r);
   step_case<8>(lane, b, Ne, a, r, getV, getM, gsrc);
+}
+
+// ---- host side, stated once for the step entries of the family: sizing_step.hip, sizing_grad.hip, sizing_multicase.hip,
+// frame_designs.hip, frame_groups.hip (the fused epoch of beam_solve.hip has the solve's launch and takes sizing_args alone) ----
+
+constexpr int kSizingMaxElems = 512;      // eight elements per lane
+
+// the fields every entry passes; the optional ones (I64, I_last, V32, M32, schedule) are NULL until the entry sets them by name
+inline SizingArgs sizing_args(float* I, float* exp_avg, float* exp_avg_sq, float* best_loss, int32_t* patience_cnt, int32_t* epochs_run,
+                              uint8_t* active, float* last_loss, const ops_sizing_params* hp) {
+  SizingArgs a{};
+  a.I = I; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq;
+  a.best_loss = best_loss; a.patience_cnt = patience_cnt; a.epochs_run = epochs_run; a.active = active; a.last_loss = last_loss;
+  a.hp = *hp;
+  return a;
+}
+
+// one 64-lane wavefront per row, four rows per 256-thread block, no LDS: the mapping of every step kernel of the family
+template <class... Params, class... Args>
+int launch_wave_rows(void (*kernel)(Params...), int rows, void* stream, const Args&... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, args...);
+  return launch_status();
+}
+
+// K = 1, 2, 4, 8: the elements per lane that serve Ne <= kSizingMaxElems; with f, handed to it as std::integral_constant<int, K>
+inline int sizing_lane_elems(int Ne) { return Ne <= 64 ? 1 : Ne <= 128 ? 2 : Ne <= 256 ? 4 : 8; }
+template <class F>
+int sizing_lane_elems(int Ne, F f) {
+  switch (sizing_lane_elems(Ne)) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
 }
 
 }  // namespace opsamd

@@ -43,19 +43,13 @@ extern "C" int ops_beam_sizing_step_multicase_f32(int G, int C, int Ne, float* I
   if (G < 0 || C < 1 || Ne < 1) return OPS_AMD_ERR_INVALID_ARG;
   if (aggregate != 0 && aggregate != 1) return OPS_AMD_ERR_INVALID_ARG;
   if (aggregate == 1 && weights) return OPS_AMD_ERR_INVALID_ARG;
-  if (Ne > 512 || C > kMultiCaseMax) return OPS_AMD_ERR_UNSUPPORTED;
+  if (Ne > kSizingMaxElems || C > kMultiCaseMax) return OPS_AMD_ERR_UNSUPPORTED;
   if (G == 0) return OPS_AMD_OK;
   if (!I || !I64_rows || !V || !M || !grad || !exp_avg || !exp_avg_sq || !best_loss || !patience_cnt || !epochs_run || !active ||
       !active_rows || !last_loss || !hp)
     return OPS_AMD_ERR_INVALID_ARG;
-  const unsigned grid = (unsigned)((G + 3) / 4);
-  const MultiCaseArgs a{{I, I64_rows, nullptr, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, nullptr,
-                         nullptr, *hp, schedule},
-                        C, aggregate, V, M, grad, loss_extra, weights, active_rows, case_penalty, governing};
-  hipStream_t s = (hipStream_t)stream;
-  if (Ne <= 64) hipLaunchKernelGGL(sizing_multicase_kernel<1>, dim3(grid), dim3(256), 0, s, G, Ne, a);
-  else if (Ne <= 128) hipLaunchKernelGGL(sizing_multicase_kernel<2>, dim3(grid), dim3(256), 0, s, G, Ne, a);
-  else if (Ne <= 256) hipLaunchKernelGGL(sizing_multicase_kernel<4>, dim3(grid), dim3(256), 0, s, G, Ne, a);
-  else hipLaunchKernelGGL(sizing_multicase_kernel<8>, dim3(grid), dim3(256), 0, s, G, Ne, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  MultiCaseArgs a{sizing_args(I, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, hp),
+                  C, aggregate, V, M, grad, loss_extra, weights, active_rows, case_penalty, governing};
+  a.s.I64 = I64_rows; a.s.schedule = schedule;
+  return sizing_lane_elems(Ne, [&](auto K) { return launch_wave_rows(sizing_multicase_kernel<K>, G, stream, G, Ne, a); });
 }

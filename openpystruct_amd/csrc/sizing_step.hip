@@ -24,7 +24,6 @@
 
 namespace opsamd {
 
-
 template <typename TVM>   // double: the solver's rows; float: rows the solver already rounded (ops_beam_solve_forces_f32)
 __global__ __launch_bounds__(256) void sizing_step_kernel(int B, int Ne, const TVM* __restrict__ V, const TVM* __restrict__ M,
                                                           const SizingArgs a) {
@@ -39,19 +38,20 @@ __global__ __launch_bounds__(256) void sizing_step_kernel(int B, int Ne, const T
 
 }  // namespace opsamd
 
+using namespace opsamd;
+
 extern "C" int ops_beam_sizing_step_f32(int B, int Ne, float* I, double* I64, const double* V, const double* M,
                                         float* exp_avg, float* exp_avg_sq, float* best_loss, int32_t* patience_cnt,
                                         int32_t* epochs_run, uint8_t* active, float* last_loss, float* V32, float* M32,
                                         const ops_sizing_params* hp, void* stream) {
-  if (B < 0 || Ne < 1 || Ne > 512) return Ne > 512 ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
+  if (B < 0 || Ne < 1 || Ne > kSizingMaxElems) return Ne > kSizingMaxElems ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
   if (B == 0) return OPS_AMD_OK;
   if (!I || !I64 || !V || !M || !exp_avg || !exp_avg_sq || !best_loss || !patience_cnt || !epochs_run || !active ||
       !last_loss || ((V32 == nullptr) != (M32 == nullptr)) || !hp)
     return OPS_AMD_ERR_INVALID_ARG;
-  const unsigned grid = (unsigned)((B + 3) / 4);
-  const opsamd::SizingArgs a{I, I64, nullptr, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, V32, M32, *hp, nullptr};
-  hipLaunchKernelGGL(opsamd::sizing_step_kernel<double>, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, Ne, V, M, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  SizingArgs a = sizing_args(I, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, hp);
+  a.I64 = I64; a.V32 = V32; a.M32 = M32;
+  return launch_wave_rows(sizing_step_kernel<double>, B, stream, B, Ne, V, M, a);
 }
 
 // schedule[2 t] = (float)(lr gamma^t) / (float)(1 - beta1^(t+1)), schedule[2 t + 1] = (float)sqrt(1 - beta2^(t+1)), t < max_epochs
@@ -68,12 +68,11 @@ extern "C" int ops_beam_sizing_step_vm32_f32(int B, int Ne, float* I, double* I6
                                              float* exp_avg, float* exp_avg_sq, float* best_loss, int32_t* patience_cnt,
                                              int32_t* epochs_run, uint8_t* active, float* last_loss, const ops_sizing_params* hp,
                                              const float* schedule, void* stream) {
-  if (B < 0 || Ne < 1 || Ne > 512) return Ne > 512 ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
+  if (B < 0 || Ne < 1 || Ne > kSizingMaxElems) return Ne > kSizingMaxElems ? OPS_AMD_ERR_UNSUPPORTED : OPS_AMD_ERR_INVALID_ARG;
   if (B == 0) return OPS_AMD_OK;
   if (!I || !I64 || !V32 || !M32 || !exp_avg || !exp_avg_sq || !best_loss || !patience_cnt || !epochs_run || !active || !last_loss || !hp)
     return OPS_AMD_ERR_INVALID_ARG;
-  const unsigned grid = (unsigned)((B + 3) / 4);
-  const opsamd::SizingArgs a{I, I64, nullptr, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, nullptr, nullptr, *hp, schedule};
-  hipLaunchKernelGGL(opsamd::sizing_step_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, B, Ne, V32, M32, a);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  SizingArgs a = sizing_args(I, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active, last_loss, hp);
+  a.I64 = I64; a.schedule = schedule;
+  return launch_wave_rows(sizing_step_kernel<float>, B, stream, B, Ne, V32, M32, a);
 }

@@ -17,6 +17,7 @@
 
 #include "../../include/openpystruct_amd.h"
 #include "lane_common.hpp"
+#include "library.hpp"
 
 namespace opsamd {
 
@@ -203,7 +204,7 @@ extern "C" int ops_stencil3_bn1_fwd_f32(int B, int F, const float* x, const floa
   if (training) hipLaunchKernelGGL(stencil_bn_fwd_stats_kernel, dim3(G), dim3(SB_THREADS), 0, s, B, F, x, conv_w, conv_b, part);
   hipLaunchKernelGGL(stencil_bn_fwd_apply_kernel, dim3(G), dim3(SB_THREADS), 0, s, B, F, x, conv_w, conv_b, gamma, beta, eps, momentum, training,
                      part, G, running_mean, running_var, num_batches_tracked, z, z_is_bf16, save);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int ops_stencil3_bn1_bwd_f32(int B, int F, const float* x, const void* grad_z, int grad_is_bf16, const float* conv_w, const float* conv_b,
@@ -219,5 +220,5 @@ extern "C" int ops_stencil3_bn1_bwd_f32(int B, int F, const float* x, const void
   hipLaunchKernelGGL(stencil_bn_bwd_apply_kernel, dim3(G), dim3(SB_THREADS), 0, s, B, F, x, grad_z, grad_is_bf16, conv_w, conv_b, gamma, save, training, part, G,
                      dx, part4);
   hipLaunchKernelGGL(stencil_bn_bwd_params_kernel, dim3(1), dim3(64), 0, s, part, part4, G, dparams);
-  return hipGetLastError() == hipSuccess ? OPS_AMD_OK : OPS_AMD_ERR_LAUNCH;
+  return launch_status();
 }

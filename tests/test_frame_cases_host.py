@@ -28,7 +28,7 @@ def test_header_is_an_extension_and_changes_no_version():
     restype, argtypes = ext.functions["ops_frame_resolve_f64"]
     assert restype is ctypes.c_int and len(argtypes) == 23 and argtypes[:6] == [ctypes.c_int] * 6 and argtypes[13] is ctypes.c_long
     assert argtypes[21] is ctypes.c_size_t
-    deps = {os.path.relpath(p, ROOT) for p in build.HEADERS}
+    deps = {os.path.relpath(p, ROOT) for s in build.SOURCES for p in build._deps(s)}      # every file the build watches
     assert os.path.join("include", HEADER) in deps and os.path.join("openpystruct_amd", "csrc", "frame_resolve.hpp") in deps
     assert os.path.normpath(os.path.join(ROOT, "openpystruct_amd", "csrc", "frame_resolve.hpp")) in build._deps(
         os.path.join(ROOT, "openpystruct_amd", "csrc", "frame_solve.hip"))

@@ -32,7 +32,7 @@ def test_header_is_an_extension_and_changes_no_version():
     assert argtypes == rows[1][:1] + [i] + rows[1][1:]
     restype, argtypes = ext.functions["ops_frame_design_step_f32"]
     assert restype is i and argtypes == [i] * 4 + [p] * 13 + [i] + [p] * 10 + [hp, p, p]
-    deps = {os.path.relpath(q, ROOT) for q in build.HEADERS}
+    deps = {os.path.relpath(q, ROOT) for s in build.SOURCES for q in build._deps(s)}      # every file the build watches
     assert os.path.join("include", HEADER) in deps and os.path.join("openpystruct_amd", "csrc", "frame_designs_math.hpp") in deps
     src = os.path.join(ROOT, "openpystruct_amd", "csrc", "frame_designs.hip")
     assert src in build.SOURCES

@@ -35,7 +35,7 @@ def test_header_is_an_extension_and_changes_no_version():
     assert argtypes == design[1][:4] + [i] + design[1][4:7] + [p] * 4 + design[1][7:]
     text = open(os.path.join(ROOT, "include", HEADER)).read()
     assert "CANNOT VALIDATE" in text and "member_groups" in text
-    deps = {os.path.relpath(q, ROOT) for q in build.HEADERS}
+    deps = {os.path.relpath(q, ROOT) for s in build.SOURCES for q in build._deps(s)}      # every file the build watches
     assert os.path.join("include", HEADER) in deps and os.path.join("openpystruct_amd", "csrc", "frame_designs_math.hpp") in deps
     src = os.path.join(ROOT, "openpystruct_amd", "csrc", "frame_groups.hip")
     assert src in build.SOURCES
