@@ -18,14 +18,12 @@ import ctypes
 import types
 from typing import Dict, NamedTuple, Optional, Sequence
 
-import numpy as np
 import torch
 
 from . import _cabi
 from .beam import beam_solve
-from .multicase import AGGREGATES
 from .sizing import SizingConfig, _beam_sizing_grad_launch, sizing_tiling
-from .sizing_common import _ptr, checked_objective
+from .sizing_common import _ptr, checked_aggregate, checked_objective
 
 I_MIN = 1e-8        # the floor of a predicted inertia (train.py, physics.py: clamp_min(1e-8))
 
@@ -40,20 +38,12 @@ class DesignObjective(NamedTuple):
 
 def _checked(aggregate, weights, C, alpha_deflection, deflection_limit, dev):
     """(aggregate index, weights on the device or None, alpha_deflection, deflection_limit), refused as the C entry would."""
-    if aggregate not in AGGREGATES:
-        raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
-    if aggregate == "max" and weights is not None:
-        raise ValueError('aggregate="max" takes no weights: the governing case is the largest unweighted penalty')
+    agg, _ = checked_aggregate(aggregate, weights)          # its name; the weights' values after the objective and the case count
     _, aD, vlim = checked_objective("total", (("deflection", alpha_deflection, deflection_limit),))
     if C < 1 or C > _cabi.load().ops_design_loss_max_cases():
         raise ValueError(f"n_load_cases must be in [1, {_cabi.load().ops_design_loss_max_cases()}], got {C}")
-    w = None
-    if weights is not None:
-        wn = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
-        if wn.shape != (C,) or not np.isfinite(wn).all() or (wn < 0).any():
-            raise ValueError(f"weights must be {C} finite non-negative numbers")
-        w = torch.as_tensor(wn, dtype=torch.float64, device=dev)
-    return AGGREGATES.index(aggregate), w, aD, vlim
+    _, w = checked_aggregate(aggregate, weights, C)
+    return agg, None if w is None else torch.as_tensor(w, dtype=torch.float64, device=dev), aD, vlim
 
 
 def _shared(x, fix, E, wy, Ne, dev):

@@ -25,8 +25,7 @@ import torch
 from . import _cabi
 from . import frames
 from .frames import FrameCaseSolution, FrameConfig, FrameFactor, FrameTopology
-from .multicase import AGGREGATES
-from .sizing_common import _ptr, checked_objective, run_epochs
+from .sizing_common import _ptr, arm_optimiser_state, checked_aggregate, history_callback, new_optimiser_state, run_epochs, step_schedule
 
 
 class FrameDesigns(NamedTuple):
@@ -38,22 +37,7 @@ class FrameDesigns(NamedTuple):
 
 
 def _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit) -> "_cabi.FrameSizingObjective":
-    _, aS, s_lim, aD, d_lim = checked_objective("total", (("sway", alpha_sway, sway_limit), ("deflection", alpha_deflection, deflection_limit)))
-    return _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
-
-
-def _checked_aggregate(aggregate: str, weights, C: int) -> tuple:
-    """(the aggregate's index, weights as a float64 numpy [C] or None), checked as `multicase.MultiCaseState` checks them."""
-    if aggregate not in AGGREGATES:
-        raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
-    if aggregate == "max" and weights is not None:
-        raise ValueError('aggregate="max" takes no weights: the governing case is the largest unweighted penalty')
-    if weights is not None:
-        w = np.asarray(weights.cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
-        if w.shape != (C,) or not np.isfinite(w).all() or (w < 0).any():
-            raise ValueError(f"weights must be {C} finite non-negative numbers")
-        weights = w
-    return AGGREGATES.index(aggregate), weights
+    return frames._objective_struct(frames._objective("total", alpha_sway, sway_limit, alpha_deflection, deflection_limit))
 
 
 def _checked_limits(topo: FrameTopology, C: int) -> None:
@@ -95,19 +79,15 @@ class _DesignState:
         f64, f32, i32 = (dict(dtype=t, device=dev) for t in (torch.float64, torch.float32, torch.int32))
         self.topo, self.C, self.hp, self.obj, self.aggregate = topo, C, hp, obj, aggregate
         self.I, self.I64 = I, I64
-        self.exp_avg, self.exp_avg_sq = torch.zeros((G, Nv), **f32), torch.zeros((G, Nv), **f32)
-        self.best, self.last = torch.full((G,), float("inf"), **f32), torch.zeros((G,), **f32)
-        self.patience_cnt, self.epochs = torch.zeros((G,), **i32), torch.zeros((G,), **i32)
-        self.active = torch.ones((G,), dtype=torch.uint8, device=dev)
+        (self.exp_avg, self.exp_avg_sq, self.best, self.patience_cnt, self.epochs, self.active,
+         self.last) = arm_optimiser_state(new_optimiser_state(G, Nv, dev))
         self.case_penalty, self.governing = torch.zeros((G, C), **f32), torch.zeros((G,), **i32)
         self.weights = None if weights is None else torch.as_tensor(weights, **f64)
         self.rhs = torch.empty((G, C, topo.Nn, 3), **f64)
         self.lam = frames._empty_case_solution(topo, G, C, dev)           # disp = lambda; the adjoint's forces, V, M are not used
         self.loss_extra = torch.zeros((G, C), **f64) if obj.alpha_sway + obj.alpha_deflection > 0.0 else None
         self.grad = torch.empty((G, Nv), **f64) if with_grad else None
-        sched = np.zeros((max(int(hp.max_epochs), 1), 2), dtype=np.float32)
-        _cabi.load().ops_sizing_schedule_f32(ctypes.byref(hp), sched.ctypes.data)
-        self.schedule = torch.as_tensor(sched, device=dev)
+        self.schedule = step_schedule(hp, dev)
 
     def adjoint_rhs(self, fwd: FrameCaseSolution) -> None:
         """Step 4 of an epoch on the current stream: the adjoint right-hand sides (and the hinge values) of all G*C rows."""
@@ -151,7 +131,7 @@ def _checked_problem(topo: FrameTopology, loads, element_loads, n_designs, V0, v
                      who: str) -> types.SimpleNamespace:
     """The arguments of a designs run, checked in the order every entry keeps: every shape before any device, then where everything
     lives (with the loads, on the topology's device).  `V0`: the optional start [G, n_vars] (I0, or X0 of the grouped loop).
-    -> G, C, dev, loads, w (the checked tensors), agg, w_c (`_checked_aggregate`), nbytes (`_factor_bytes`)."""
+    -> G, C, dev, loads, w (the checked tensors), agg, w_c (`checked_aggregate`), nbytes (`_factor_bytes`)."""
     if torch.is_tensor(loads) and loads.dim() == 4:
         G = int(loads.shape[0])
     elif V0 is not None and torch.is_tensor(V0) and V0.dim() == 2:
@@ -172,7 +152,7 @@ def _checked_problem(topo: FrameTopology, loads, element_loads, n_designs, V0, v
     if V0 is not None and (not torch.is_tensor(V0) or tuple(V0.shape) != (G, n_vars)):
         raise ValueError(f"{v_name} must be [{G}, {n_vars}]")
     _checked_limits(topo, C)
-    agg, w_c = _checked_aggregate(aggregate, weights, C)
+    agg, w_c = checked_aggregate(aggregate, weights, C)
     nbytes = _factor_bytes(topo, G)
     if loads.is_cuda and topo.device.type == "cuda" and topo.device.index in (None, loads.device.index):
         dev = loads.device
@@ -227,6 +207,27 @@ class _Forward:
             _cabi.check(rc, "ops_frame_load_forces_f64")
 
 
+def _start_values(V0: Optional[torch.Tensor], G: int, n_vars: int, cfg: FrameConfig, dev) -> torch.Tensor:
+    """The variables a designs loop starts from, float32 [G, n_vars] on `dev`: a copy of `V0`, or cfg.I0 everywhere."""
+    return V0.to(dtype=torch.float32, device=dev).clone() if V0 is not None else torch.full((G, n_vars), cfg.I0, dtype=torch.float32, device=dev)
+
+
+def _run_design_loop(st: _DesignState, q: types.SimpleNamespace, n_max: int, poll_every: int, loss_history: Optional[list]) -> _Forward:
+    """The loop of a designs run on the state `st` (its `step` is the design's or the groups'): up to `n_max` epochs of the forward
+    and `st.gradient_and_step`, then the forward once more -- I64 froze when a design stopped: every design's last solve, all C cases
+    -- and a device synchronise.  Returns the forward, whose `fwd` is that solve; with no designs nothing is launched."""
+    fw = _Forward(st.topo, st.I64, q)
+    if q.G:
+        def epoch():
+            fw()
+            st.gradient_and_step(fw.factor, fw.fwd)
+
+        run_epochs(epoch, n_max, poll_every, st.active, history_callback(loss_history, st.last))
+        fw()
+        torch.cuda.synchronize(q.dev)
+    return fw
+
+
 def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loads: Optional[torch.Tensor] = None, *,
                            n_designs: Optional[int] = None, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
                            aggregate: str = "sum", weights: Optional[Sequence[float]] = None, alpha_sway: float = 0.0,
@@ -244,23 +245,33 @@ def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loa
     cfg = cfg or FrameConfig()
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
     q = _checked_problem(topo, loads, element_loads, n_designs, I0, "I0", topo.Ne, aggregate, weights, "optimize_frame_designs")
-    G, C, dev = q.G, q.C, q.dev
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
-    hp = frames._sizing_params(cfg, n_max)
-    I = I0.to(dtype=torch.float32, device=dev).clone() if I0 is not None else torch.full((G, topo.Ne), cfg.I0, dtype=torch.float32, device=dev)
-    st = _DesignState(topo, I, I.double(), C, hp, obj, q.agg, q.w_c, with_grad=False)
-    fw = _Forward(topo, st.I64, q)
-    if G == 0:
-        return FrameDesigns(I, fw.fwd, st.epochs, st.governing, st.case_penalty)
-
-    def epoch():
-        fw()
-        st.gradient_and_step(fw.factor, fw.fwd)
-
-    run_epochs(epoch, n_max, poll_every, st.active, (lambda: loss_history.append(st.last.clone())) if loss_history is not None else None)
-    fw()                                          # I64 froze when a design stopped: every design's last solve, all C cases
-    torch.cuda.synchronize(dev)
+    I = _start_values(I0, q.G, topo.Ne, cfg, q.dev)
+    st = _DesignState(topo, I, I.double(), q.C, frames._sizing_params(cfg, n_max), obj, q.agg, q.w_c, with_grad=False)
+    fw = _run_design_loop(st, q, n_max, poll_every, loss_history)
     return FrameDesigns(I, fw.fwd, st.epochs, st.governing, st.case_penalty)
+
+
+def _checked_gradient_inputs(factor: FrameFactor, sol: FrameCaseSolution, hp, aggregate: str, weights, who: str) -> types.SimpleNamespace:
+    """The arguments of a gradient entry `who`, checked in the order both keep: the factor's inertias, the solution's shapes, the
+    limits, the aggregate, then where everything lives.  -> topo, I64 (factor.I), G, C, agg, w_c (`checked_aggregate`), hp (an
+    `ops_sizing_params`)."""
+    topo, I64 = factor.topo, factor.I
+    if not torch.is_tensor(I64) or I64.dtype != torch.float64 or I64.dim() != 2 or I64.shape[1] != topo.Ne:
+        raise ValueError(f"factor.I must be float64 [G, {topo.Ne}]")
+    G = I64.shape[0]
+    for name, t, tail, dt in (("sol.disp", sol.disp, (topo.Nn, 3), torch.float64), ("sol.V", sol.V, (topo.Ne,), torch.float64),
+                              ("sol.M", sol.M, (topo.Ne,), torch.float64), ("sol.status", sol.status, (), torch.int32)):
+        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 2 + len(tail) or t.shape[0] != G or tuple(t.shape[2:]) != tail or \
+                t.shape[1] != sol.disp.shape[1] or not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous {str(dt).split('.')[-1]} [{G}, C{''.join(', ' + str(n) for n in tail)}]")
+    C = int(sol.disp.shape[1])
+    _checked_limits(topo, C)
+    agg, w_c = checked_aggregate(aggregate, weights, C)
+    if not I64.is_cuda or any(not t.is_cuda for t in (sol.disp, sol.V, sol.M, sol.status)):
+        raise RuntimeError(f"{who} needs GPU tensors: openpystruct_amd has no CPU fallback")
+    hp = frames._sizing_params(hp) if isinstance(hp, FrameConfig) else hp
+    return types.SimpleNamespace(topo=topo, I64=I64, G=G, C=C, agg=agg, w_c=w_c, hp=hp)
 
 
 def frame_design_gradient(factor: FrameFactor, sol: FrameCaseSolution, hp, *, aggregate: str = "sum",
@@ -272,26 +283,20 @@ def frame_design_gradient(factor: FrameFactor, sol: FrameCaseSolution, hp, *, ag
     `FrameConfig` or an `ops_sizing_params`.  Returns (grad, loss_extra [G,C] -- the value of the displacement terms per case, None
     when both alphas are 0 --, governing [G] int32).  "sum": grad = 1 + sum_c w_c dP_c/dI; "max": 1 + dP_c*/dI of the governing
     case.  Rows of a design with a failed factorisation (or, under "sum", any failed case) are NaN."""
-    topo, I64 = factor.topo, factor.I
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
-    if not torch.is_tensor(I64) or I64.dtype != torch.float64 or I64.dim() != 2 or I64.shape[1] != topo.Ne:
-        raise ValueError(f"factor.I must be float64 [G, {topo.Ne}]")
-    G, dev = I64.shape[0], I64.device
-    for name, t, tail, dt in (("sol.disp", sol.disp, (topo.Nn, 3), torch.float64), ("sol.V", sol.V, (topo.Ne,), torch.float64),
-                              ("sol.M", sol.M, (topo.Ne,), torch.float64), ("sol.status", sol.status, (), torch.int32)):
-        if not torch.is_tensor(t) or t.dtype != dt or t.dim() != 2 + len(tail) or t.shape[0] != G or tuple(t.shape[2:]) != tail or \
-                t.shape[1] != sol.disp.shape[1] or not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous {str(dt).split('.')[-1]} [{G}, C{''.join(', ' + str(n) for n in tail)}]")
-    C = int(sol.disp.shape[1])
-    _checked_limits(topo, C)
-    agg, w_c = _checked_aggregate(aggregate, weights, C)
-    if not I64.is_cuda or any(not t.is_cuda for t in (sol.disp, sol.V, sol.M, sol.status)):
-        raise RuntimeError("frame_design_gradient needs GPU tensors: openpystruct_amd has no CPU fallback")
-    hp = frames._sizing_params(hp) if isinstance(hp, FrameConfig) else hp
-    st = _DesignState(topo, I64.float(), I64.clone(), C, hp, obj, agg, w_c, with_grad=True)
-    if G:
+    q = _checked_gradient_inputs(factor, sol, hp, aggregate, weights, "frame_design_gradient")
+    st = _DesignState(q.topo, q.I64.float(), q.I64.clone(), q.C, q.hp, obj, q.agg, q.w_c, with_grad=True)
+    if q.G:
         st.gradient_and_step(factor, sol)
     return st.grad, st.loss_extra, st.governing
+
+
+def _dataset_fields(r, lateral: np.ndarray, vertical: np.ndarray, G: int, C: int) -> dict:
+    """The CPU tensors both dataset generators return, from a designs result `r` and the draws of its G * C load cases."""
+    sol = r.solution
+    return dict(I=r.I.cpu(), lateral=torch.as_tensor(lateral).reshape(G, C), vertical=torch.as_tensor(vertical).reshape(G, C),
+                V=sol.V.cpu(), M=sol.M.cpu(), disp=sol.disp.cpu(), epochs=r.epochs.cpu(), status=sol.status.cpu(),
+                governing=r.governing.cpu(), case_penalty=r.case_penalty.cpu())
 
 
 def generate_frame_design_dataset(num_bays: int, num_stories: int, n_designs: int, n_load_cases: int, cfg: Optional[FrameConfig] = None,
@@ -309,7 +314,4 @@ def generate_frame_design_dataset(num_bays: int, num_stories: int, n_designs: in
     loads, w = frames.grid_load_cases(topo, lateral, vertical)
     r = optimize_frame_designs(topo, loads.reshape(G, C, topo.Nn, 3), w.reshape(G, C, topo.Ne, 2), n_designs=G, cfg=cfg, aggregate=aggregate,
                                weights=weights, max_epochs=max_epochs, **objective)
-    sol = r.solution
-    return dict(I=r.I.cpu(), lateral=torch.as_tensor(lateral).reshape(G, C), vertical=torch.as_tensor(vertical).reshape(G, C),
-                V=sol.V.cpu(), M=sol.M.cpu(), disp=sol.disp.cpu(), epochs=r.epochs.cpu(), status=sol.status.cpu(),
-                governing=r.governing.cpu(), case_penalty=r.case_penalty.cpu())
+    return _dataset_fields(r, lateral, vertical, G, C)

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 
 from . import _cabi
-from .sizing_common import GRADIENTS, _ptr, _sizing_step, _StepState, checked_objective, run_epochs  # noqa: F401  (GRADIENTS: public here)
+from .sizing_common import (GRADIENTS, _ptr, _sizing_step, _StepState, arm_optimiser_state, checked_objective,  # noqa: F401  (GRADIENTS: public here)
+                            history_callback, new_optimiser_state, run_epochs)
 
 
 @dataclass
@@ -335,7 +336,6 @@ def frame_solve_vjp(topo: FrameTopology, I: torch.Tensor, disp: torch.Tensor, g_
     g_forces, gV, gM = _checked_cotangents(topo, B, dev, g_forces, gV, gM)
     status = _checked("status", status, torch.int32, (B,), dev, optional=True)
     adj = _adjoint_tables(topo)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     rhs = torch.empty((B, topo.Nn, 3), dtype=torch.float64, device=dev)
     gI = torch.empty((B, topo.Ne), dtype=torch.float64, device=dev)
     if B == 0:
@@ -343,14 +343,14 @@ def frame_solve_vjp(topo: FrameTopology, I: torch.Tensor, disp: torch.Tensor, g_
     stream = torch.cuda.current_stream(dev).cuda_stream
     with torch.cuda.device(dev):
         rc = lib.ops_frame_adjoint_rhs_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
-                                           adj.conn.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), I.data_ptr(), ptr(g_disp),
-                                           ptr(g_forces), ptr(gV), ptr(gM), rhs.data_ptr(), stream)
+                                           adj.conn.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), I.data_ptr(), _ptr(g_disp),
+                                           _ptr(g_forces), _ptr(gV), _ptr(gM), rhs.data_ptr(), stream)
     _cabi.check(rc, "ops_frame_adjoint_rhs_f64")
     sol = _empty_solution(topo, B, dev)                     # disp = lambda; the adjoint's forces, V, M are not used
     _run_solve(topo, I, rhs, topo.Nn * 3, sol, adj.zero_w, "_ws_adjoint")
     with torch.cuda.device(dev):
         rc = lib.ops_frame_grad_contract_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(),
-                                             disp.data_ptr(), sol.disp.data_ptr(), ptr(g_forces), ptr(gV), ptr(gM), ptr(status),
+                                             disp.data_ptr(), sol.disp.data_ptr(), _ptr(g_forces), _ptr(gV), _ptr(gM), _ptr(status),
                                              sol.status.data_ptr(), gI.data_ptr(), stream)
     _cabi.check(rc, "ops_frame_grad_contract_f64")
     return gI, sol.disp, sol.status
@@ -376,11 +376,10 @@ def frame_element_load_vjp(topo: FrameTopology, lam: torch.Tensor, g_forces: Opt
     g_forces, gV, gM = _checked_cotangents(topo, B, dev, g_forces, gV, gM)
     status, status_adj = (_checked(k, v, torch.int32, (B,), dev, optional=True) for k, v in (("status", status), ("status_adj", status_adj)))
     adj = _adjoint_tables(topo)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     g_w = torch.empty((B, topo.Ne, 2), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.ops_frame_load_vjp_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.conn.data_ptr(), lam.data_ptr(), ptr(g_forces),
-                                        ptr(gV), ptr(gM), ptr(status), ptr(status_adj), g_w.data_ptr(),
+        rc = lib.ops_frame_load_vjp_f64(B, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.conn.data_ptr(), lam.data_ptr(), _ptr(g_forces),
+                                        _ptr(gV), _ptr(gM), _ptr(status), _ptr(status_adj), g_w.data_ptr(),
                                         torch.cuda.current_stream(dev).cuda_stream)
     _cabi.check(rc, "ops_frame_load_vjp_f64")
     return g_w
@@ -566,7 +565,6 @@ def frame_solve_cases_vjp(factor: FrameFactor, sol: FrameCaseSolution, g_disp: O
     if B == 0 or C == 0:
         return gI.zero_(), lam.disp, g_w
     adj = _adjoint_tables(topo)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     R = B * C
     I_rows = I.repeat_interleave(C, 0)
     rhs = torch.empty((B, C, topo.Nn, 3), **f64)
@@ -574,17 +572,17 @@ def frame_solve_cases_vjp(factor: FrameFactor, sol: FrameCaseSolution, g_disp: O
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         rc = lib.ops_frame_adjoint_rhs_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_EA.data_ptr(), topo.d_E.data_ptr(),
-                                           adj.conn.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), I_rows.data_ptr(), ptr(g_disp),
-                                           ptr(g_forces), ptr(gV), ptr(gM), rhs.data_ptr(), stream)
+                                           adj.conn.data_ptr(), adj.ptr.data_ptr(), adj.idx.data_ptr(), I_rows.data_ptr(), _ptr(g_disp),
+                                           _ptr(g_forces), _ptr(gV), _ptr(gM), rhs.data_ptr(), stream)
     _cabi.check(rc, "ops_frame_adjoint_rhs_f64")
     _resolve_launch(factor, C, rhs, C * topo.Nn * 3, lam)
     with torch.cuda.device(dev):
         rc = lib.ops_frame_grad_contract_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), adj.conn.data_ptr(),
-                                             disp.data_ptr(), lam.disp.data_ptr(), ptr(g_forces), ptr(gV), ptr(gM), st_fwd.data_ptr(),
+                                             disp.data_ptr(), lam.disp.data_ptr(), _ptr(g_forces), _ptr(gV), _ptr(gM), st_fwd.data_ptr(),
                                              lam.status.data_ptr(), gI_rows.data_ptr(), stream)
         _cabi.check(rc, "ops_frame_grad_contract_f64")
-        rc = lib.ops_frame_load_vjp_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.conn.data_ptr(), lam.disp.data_ptr(), ptr(g_forces),
-                                        ptr(gV), ptr(gM), st_fwd.data_ptr(), lam.status.data_ptr(), g_w.data_ptr(), stream)
+        rc = lib.ops_frame_load_vjp_f64(R, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), adj.conn.data_ptr(), lam.disp.data_ptr(), _ptr(g_forces),
+                                        _ptr(gV), _ptr(gM), st_fwd.data_ptr(), lam.status.data_ptr(), g_w.data_ptr(), stream)
     _cabi.check(rc, "ops_frame_load_vjp_f64")
     gI.copy_(gI_rows[:, 0])
     for c in range(1, C):                                      # the case axis in index order
@@ -608,6 +606,12 @@ def _objective(gradient: str, alpha_sway: float, sway_limit: Optional[float], al
     reference's gradient (M and V held fixed), which cannot see a displacement term; "total": the gradient of the loss through the
     solve.  The limits are penalties, not constraints."""
     return checked_objective(gradient, (("sway", alpha_sway, sway_limit), ("deflection", alpha_deflection, deflection_limit)))
+
+
+def _objective_struct(objective: tuple) -> "_cabi.FrameSizingObjective":
+    """The penalties of a checked objective (`_objective`) as the launches read them."""
+    _, aS, s_lim, aD, d_lim = objective
+    return _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
 
 
 def _sizing_params(cfg: FrameConfig, max_epochs: Optional[int] = None) -> "_cabi.SizingParams":
@@ -666,15 +670,14 @@ def frame_sizing_gradient(topo: FrameTopology, I: torch.Tensor, sol: FrameSoluti
     a frame with sol.status != 0).  Rows of frames with active[b] == 0 are not written."""
     I = _checked("I", I, torch.float64, (None, topo.Ne), gpu_for="frame_sizing_gradient", in_place=True)
     B, dev = I.shape[0], I.device
-    _, aS, s_lim, aD, d_lim = _objective("total", alpha_sway, sway_limit, alpha_deflection, deflection_limit)
+    obj = _objective_struct(_objective("total", alpha_sway, sway_limit, alpha_deflection, deflection_limit))
     hp = _sizing_params(hp) if isinstance(hp, FrameConfig) else hp
     for name, t, shape in (("sol.disp", sol.disp, (B, topo.Nn, 3)), ("sol.V", sol.V, (B, topo.Ne)), ("sol.M", sol.M, (B, topo.Ne))):
         _checked(name, t, torch.float64, shape, dev, in_place=True)
     sol = sol._replace(status=_checked("sol.status", sol.status, torch.int32, (B,), dev))
     active = _checked("active", active, torch.uint8, (B,), dev, optional=True)
-    buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
+    buf = _sizing_grad_buffers(topo, B, dev, obj.alpha_sway + obj.alpha_deflection > 0.0)
     if B:
-        obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
         _sizing_grad_launches(topo, I, sol, hp, obj, active, buf)
     return buf.grad, buf.loss_extra, buf.adj.status
 
@@ -694,15 +697,13 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
     loss through the solve (five launches per epoch, two factorisations) and may add the penalties
     `alpha_sway * sum_n (max(0, |ux_n| - sway_limit) / sway_limit)^2` and, in uy, `alpha_deflection` / `deflection_limit` to the loss."""
     cfg = cfg or FrameConfig()
-    _, aS, s_lim, aD, d_lim = _objective(gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit)
+    obj = _objective_struct(_objective(gradient, alpha_sway, sway_limit, alpha_deflection, deflection_limit))
     if gradient == "total" and topo.Ne > 512:
         raise ValueError(f'gradient="total" serves up to 512 elements per frame (the optimiser step kernel), got {topo.Ne}')
     dev, Ne = topo.device, topo.Ne
-    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
     I = (I0.to(**f32).clone() if I0 is not None else torch.full((B, Ne), cfg.I0, **f32))
-    st = _StepState(I, I.double(), torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32), torch.full((B,), float("inf"), **f32),
-                    torch.zeros((B,), **i32), torch.zeros((B,), **i32), torch.ones((B,), dtype=torch.uint8, device=dev),
-                    torch.zeros((B,), **f32), torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32))
+    st = _StepState(I, I.double(), *arm_optimiser_state(new_optimiser_state(B, Ne, dev)), torch.zeros((B, Ne), **f32), torch.zeros((B, Ne), **f32))
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
     hp = _sizing_params(cfg, n_max)
     if loads is not None:
@@ -726,8 +727,7 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
         forward = lambda out: frame_solve(topo, st.I64, loads, out=out)  # noqa: E731
     buf = grad = loss_extra = None      # the explicit step forms its gradient from (V, M)
     if gradient == "total":
-        buf = _sizing_grad_buffers(topo, B, dev, aS + aD > 0.0)
-        obj = _cabi.FrameSizingObjective(alpha_sway=aS, sway_limit=s_lim, alpha_deflection=aD, deflection_limit=d_lim)
+        buf = _sizing_grad_buffers(topo, B, dev, obj.alpha_sway + obj.alpha_deflection > 0.0)
         grad, loss_extra = buf.grad, buf.loss_extra
 
     def epoch():
@@ -737,7 +737,7 @@ def optimize_frames(topo: FrameTopology, B: int, cfg: Optional[FrameConfig] = No
             _sizing_grad_launches(topo, st.I64, sol, hp, obj, st.active, buf)
         _sizing_step(st, sol.V, sol.M, hp, grad, loss_extra)
 
-    run_epochs(epoch, n_max, poll_every, st.active, (lambda: loss_history.append(st.last.clone())) if loss_history is not None else None)
+    run_epochs(epoch, n_max, poll_every, st.active, history_callback(loss_history, st.last))
     torch.cuda.synchronize(dev)
     return I, sol, st.epochs
 

@@ -22,11 +22,10 @@ import torch
 
 from . import _cabi
 from .beam import BeamSolution, beam_solve
-from .sizing import (RECORD_KEYS, Cases, SizingConfig, _beam_sizing_grad_launch, _shared_rows, make_cases,  # noqa: F401
+from .sizing import (RECORD_KEYS, Cases, SizingConfig, _beam_sizing_grad_launch, _case_record_fields, _shared_rows, make_cases,  # noqa: F401
                      sizing_tiling)
-from .sizing_common import _ptr, checked_objective, replay_epochs, run_epochs
-
-AGGREGATES = ("sum", "max")
+from .sizing_common import (AGGREGATES, _ptr, arm_optimiser_state, checked_aggregate, checked_objective, new_optimiser_state,  # noqa: F401  (AGGREGATES: public here)
+                            run_sizing_loop, step_schedule)
 
 
 def check_design_groups(cases: Cases, n_load_cases: int) -> int:
@@ -74,10 +73,7 @@ class MultiCaseState:
 
     def __init__(self, cases: Cases, cfg: SizingConfig, device: torch.device, n_load_cases: int, aggregate: str = "sum",
                  weights: Optional[Sequence[float]] = None, alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
-        if aggregate not in AGGREGATES:
-            raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
-        if aggregate == "max" and weights is not None:
-            raise ValueError('aggregate="max" takes no weights: the governing case is the largest unweighted penalty')
+        self.aggregate, _ = checked_aggregate(aggregate, weights)          # its name; the weights' values after the device and the shapes
         self.objective = checked_objective("total", (("deflection", alpha_deflection, deflection_limit),))
         device = torch.device(device)
         if device.type != "cuda" or cases.Fy.device.type != "cuda":
@@ -90,16 +86,12 @@ class MultiCaseState:
         Ne = N - 1
         if Ne > 512:
             raise ValueError(f"multi-case sizing serves up to 512 elements per beam (the optimiser step kernel), got {Ne}")
-        if weights is not None:
-            w = np.asarray(weights, dtype=np.float64).reshape(-1)
-            if w.shape != (C,) or not np.isfinite(w).all() or (w < 0).any():
-                raise ValueError(f"weights must be {C} finite non-negative numbers")
+        _, w = checked_aggregate(aggregate, weights, C)
         f64 = dict(dtype=torch.float64, device=device)
         f32 = dict(dtype=torch.float32, device=device)
         i32 = dict(dtype=torch.int32, device=device)
         self.G, self.C, self.B, self.N, self.Ne, self.device, self.cfg = G, C, B, N, Ne, device, cfg
-        self.aggregate = AGGREGATES.index(aggregate)
-        self.weights = None if weights is None else torch.as_tensor(w, **f64)
+        self.weights = None if w is None else torch.as_tensor(w, **f64)
         shared_geom, shared_fix = _shared_rows(cases) if B else (True, True)
         self._solve_tiling = sizing_tiling(N, shared_geometry=False)      # the "total" mode's: beam_solve.hip's 16 lanes while they fit
         self.x = (cases.node_positions[0] if shared_geom else cases.node_positions).to(device).contiguous()
@@ -108,10 +100,8 @@ class MultiCaseState:
         self.E, self.wy = torch.full((), cfg.E, **f64), torch.full((), cfg.uniform_udl, **f64)
         # the design [G, ...]
         self.I = torch.full((G, Ne), cfg.I_0, **f32)
-        self.exp_avg, self.exp_avg_sq = torch.zeros((G, Ne), **f32), torch.zeros((G, Ne), **f32)
-        self.best_loss, self.last_loss = torch.full((G,), float("inf"), **f32), torch.zeros((G,), **f32)
-        self.patience_cnt, self.epochs_run = torch.zeros((G,), **i32), torch.zeros((G,), **i32)
-        self.active = torch.ones((G,), dtype=torch.uint8, device=device)
+        (self.exp_avg, self.exp_avg_sq, self.best_loss, self.patience_cnt, self.epochs_run, self.active,
+         self.last_loss) = arm_optimiser_state(new_optimiser_state(G, Ne, device))
         self.case_penalty = torch.zeros((G, C), **f32)
         self.governing = torch.zeros((G,), **i32)
         # its beam rows [G*C, ...]
@@ -122,9 +112,7 @@ class MultiCaseState:
         self._obj = _cabi.SizingObjective(alpha_deflection=self.objective[1], deflection_limit=self.objective[2])
         self._grad_status = torch.zeros((B,), **i32)
         self._hp = cfg.c_params()
-        sched = np.zeros((max(int(cfg.max_e), 1), 2), dtype=np.float32)
-        _cabi.load().ops_sizing_schedule_f32(ctypes.byref(self._hp), sched.ctypes.data)
-        self._schedule = torch.as_tensor(sched, device=device)
+        self._schedule = step_schedule(self._hp, device)
         self.sol: Optional[BeamSolution] = None
         self.V32 = self.M32 = None
 
@@ -167,19 +155,10 @@ def optimize_designs(cases: Cases, cfg: SizingConfig, device, n_load_cases: int,
     st = MultiCaseState(cases, cfg, device, n_load_cases, aggregate, weights, alpha_deflection, deflection_limit)
     if st.G == 0:
         return st
+    _, history = run_sizing_loop(st.epoch, cfg.max_e, poll_every, st.active, st.last_loss, device,
+                                 use_graph=use_graph and poll_every > 1 and not record_loss, record=record_loss)
     if record_loss:
-        use_graph = False
-    if use_graph and poll_every > 1:
-        from .runtime import capture_graph
-        # one eager epoch as the warm-up outside capture (it allocates the solution buffers)
-        graph, _ = capture_graph(torch.cuda.Stream(device=device), device, lambda: [st.epoch() for _ in range(poll_every)], 1, warm=st.epoch)
-        replay_epochs(graph, cfg.max_e, poll_every, 1, st.active, torch.zeros(2, dtype=torch.uint8).pin_memory(),
-                      [torch.cuda.Event(), torch.cuda.Event()])
-    else:
-        hist = []
-        run_epochs(st.epoch, cfg.max_e, poll_every, st.active, (lambda: hist.append(st.last_loss.clone())) if record_loss else None)
-        if record_loss:
-            st.loss_history = torch.stack(hist) if hist else torch.zeros((0, st.G), dtype=torch.float32, device=device)
+        st.loss_history = history
     st.finalize()
     torch.cuda.synchronize(device)
     return st
@@ -198,31 +177,13 @@ def generate_multicase_dataset(n_designs: int, n_load_cases: int, cfg: Optional[
     cases = make_design_cases(G, C, cfg, seed, device=device)
     st = optimize_designs(cases, cfg, device, C, aggregate=aggregate, weights=weights, alpha_deflection=alpha_deflection,
                           deflection_limit=deflection_limit, poll_every=poll_every)
-    sol = st.sol
-    rot, defl = sol.theta.clone(), sol.v.clone()
-    if cfg.zero_last_node:
-        rot[:, -1] = 0.0
-        defl[:, -1] = 0.0
-    xs = cases.node_positions
-    x_at = lambda nodes: torch.gather(xs, 1, (nodes - 1).clamp_min(0)) * (nodes > 0)   # noqa: E731
     return {
-        "roller_x_locations": x_at(cases.roller_nodes_t),
-        "force_x_locations": x_at(cases.force_nodes_t),
-        "force_values": cases.force_values_t,
+        **_case_record_fields(cases, cfg, st.sol),
         "I_values": st.I.repeat_interleave(C, dim=0),      # one design, C rows
         "shear_forces": st.V32,
         "bending_moments": st.M32,
-        "node_positions": xs,
-        "roller_nodes": cases.roller_nodes_t,
-        "force_nodes": cases.force_nodes_t,
-        "num_nodes": cfg.num_nodes,
-        "L": cases.L,
-        "rotations": rot,
-        "deflections": defl,
-        "n_rollers": cases.n_rollers,
-        "n_forces": cases.n_forces,
         "epochs_run": st.epochs_run,
-        "status": sol.status,
+        "status": st.sol.status,
         "I_solved": st.I64_rows,
         "design_ids": torch.from_numpy(np.repeat(np.arange(G, dtype=np.int64), C)),
         "governing_case": st.governing,

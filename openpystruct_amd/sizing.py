@@ -31,7 +31,8 @@ import torch
 
 from . import _cabi
 from .beam import BeamSolution, _check_inputs, _rows, beam_solve
-from .sizing_common import GRADIENTS, _ptr, _sizing_step, _StepState, checked_objective, replay_epochs, run_epochs  # noqa: F401  (GRADIENTS: public here)
+from .sizing_common import (GRADIENTS, _ptr, _sizing_step, _StepState, arm_optimiser_state, checked_objective,  # noqa: F401  (GRADIENTS: public here)
+                            new_optimiser_state, poll_flags, run_sizing_loop, step_schedule)
 
 
 @dataclass
@@ -410,10 +411,9 @@ class SizingState:
         # fused epochs keep no widened copy: the kernel records, once per case, the float32 inertias of its last solve
         self.I_last = torch.empty((B, Ne), **f32) if self._fused else None
         self.I64 = None if self._fused else torch.empty((B, Ne), **f64)     # separate launches: the solver's input
-        self.exp_avg, self.exp_avg_sq = torch.empty((B, Ne), **f32), torch.empty((B, Ne), **f32)
-        self.best_loss, self.last_loss = torch.empty((B,), **f32), torch.empty((B,), **f32)          # :170
-        self.patience_cnt, self.epochs_run, self._status = torch.empty((B,), **i32), torch.empty((B,), **i32), torch.empty((B,), **i32)
-        self.active = torch.empty((B,), dtype=torch.uint8, device=device)
+        self._opt = new_optimiser_state(B, Ne, device)                   # Adam and the early stop (:170)
+        self.exp_avg, self.exp_avg_sq, self.best_loss, self.patience_cnt, self.epochs_run, self.active, self.last_loss = self._opt
+        self._status = torch.empty((B,), dtype=torch.int32, device=device)
         self.sol: Optional[BeamSolution] = None      # V32, M32 (set by `_arm`) and sol: filled by finalize()
         # what each epoch overwrites before it is read
         self._V = torch.empty((B, Ne), **f32)         # element end forces of the epoch's solve, rounded like :189-190
@@ -424,12 +424,9 @@ class SizingState:
             self._obj = _cabi.SizingObjective(alpha_deflection=self.objective[1], deflection_limit=self.objective[2])
             self._grad_status = torch.zeros((B,), **i32)
         if not self._fused:
-            self._step = _StepState(self.I, self.I64, self.exp_avg, self.exp_avg_sq, self.best_loss, self.patience_cnt,
-                                    self.epochs_run, self.active, self.last_loss, None, None)     # aliases; V32 / M32: finalize rounds them
+            self._step = _StepState(self.I, self.I64, *self._opt, None, None)     # aliases; V32 / M32: finalize rounds them
         self._hp = cfg.c_params()
-        sched = np.zeros((max(int(cfg.max_e), 1), 2), dtype=np.float32)          # per-epoch step size / bias correction
-        _cabi.load().ops_sizing_schedule_f32(ctypes.byref(self._hp), sched.ctypes.data)
-        self._schedule = torch.as_tensor(sched, device=device)
+        self._schedule = step_schedule(self._hp, device)
         self._arm(cases, cfg)
 
     def _arm(self, cases: Cases, cfg: SizingConfig) -> None:
@@ -447,10 +444,8 @@ class SizingState:
             self.I_last.fill_(cfg.I_0)
         else:
             self.I64.fill_(float(np.float32(cfg.I_0)))
-        for t in (self.exp_avg, self.exp_avg_sq, self.patience_cnt, self.epochs_run, self.last_loss, self._status):
-            t.zero_()
-        self.best_loss.fill_(float("inf"))
-        self.active.fill_(1)
+        arm_optimiser_state(self._opt)
+        self._status.zero_()
         self.V32 = self.M32 = None
 
     def reset(self, cases: Cases, cfg: SizingConfig, gradient: str = "explicit", alpha_deflection: float = 0.0,
@@ -546,26 +541,16 @@ def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25
         st = SizingState(cases, cfg, device, gradient, alpha_deflection, deflection_limit)
     if st.B == 0:
         return st
-    epochs_done = 0
-    if graph is None and use_graph and poll_every > 1:
-        # the epoch body is launch-bound (two short kernels): replay `poll_every` epochs as one HIP graph
-        from .runtime import capture_graph
-        # one eager epoch as the warm-up outside capture (it allocates the solution buffers)
-        graph, _ = capture_graph(torch.cuda.Stream(device=device), device, lambda: [st.epoch() for _ in range(poll_every)], 1, warm=st.epoch)
-        epochs_done = 1
-        if reuse:
-            _EPOCH_GRAPHS[key] = (st, graph)
-    if graph is not None:
-        # the "any case still active?" poll lags one replay (sizing_common.replay_epochs)
-        if key not in _POLL_FLAGS:          # (pinned allocations are slow: one pair of flags and events per device and thread)
-            _POLL_FLAGS[key] = (torch.zeros(2, dtype=torch.uint8).pin_memory(), [torch.cuda.Event(), torch.cuda.Event()])
-        replay_epochs(graph, cfg.max_e, poll_every, epochs_done, st.active, *_POLL_FLAGS[key],
-                      lag=0 if os.environ.get("OPS_AMD_SIZING_POLL_LAG", "1") == "0" else 1)
-    else:
-        hist = []
-        run_epochs(st.epoch, cfg.max_e, poll_every, st.active, (lambda: hist.append(st.last_loss.clone())) if record_loss else None)
-        if record_loss:
-            st.loss_history = torch.stack(hist) if hist else torch.zeros((0, st.B), dtype=torch.float32, device=device)
+    use_graph = use_graph and poll_every > 1
+    if use_graph and key not in _POLL_FLAGS:          # one pair of flags and events per device and thread
+        _POLL_FLAGS[key] = poll_flags()
+    # the "any case still active?" poll lags one replay (sizing_common.replay_epochs)
+    graph, history = run_sizing_loop(st.epoch, cfg.max_e, poll_every, st.active, st.last_loss, device, use_graph=use_graph, record=record_loss,
+                                     graph=graph, poll=_POLL_FLAGS.get(key), lag=0 if os.environ.get("OPS_AMD_SIZING_POLL_LAG", "1") == "0" else 1)
+    if reuse and graph is not None:
+        _EPOCH_GRAPHS[key] = (st, graph)
+    if record_loss:
+        st.loss_history = history
     # a case that is still active here ran out of max_e inside the step kernel already (it clears `active`)
     st.finalize()
     torch.cuda.synchronize(device)
@@ -575,6 +560,33 @@ def optimize_cases(cases: Cases, cfg: SizingConfig, device, poll_every: int = 25
 RECORD_KEYS = ("roller_x_locations", "force_x_locations", "force_values", "I_values", "shear_forces",
                "bending_moments", "node_positions", "roller_nodes", "force_nodes", "num_nodes", "L",
                "rotations", "deflections")   # SingleCore.py:73-87
+
+
+def _case_record_fields(cases: Cases, cfg: SizingConfig, sol: BeamSolution) -> Dict[str, object]:
+    """The record fields that are the cases' own or the last solve's displacements (copies), whatever loop sized the cases: the
+    generators add the inertias, the forces and their bookkeeping."""
+    rot, defl = sol.theta.clone(), sol.v.clone()
+    if cfg.zero_last_node:
+        rot[:, -1] = 0.0
+        defl[:, -1] = 0.0
+    xs = cases.node_positions
+    x_at = lambda nodes: torch.gather(xs, 1, (nodes - 1).clamp_min(0)) * (nodes > 0)   # noqa: E731  zero-padded like the ids
+    return {
+        # ragged fields as zero-padded tensors + counts: exactly the arrays the reference's pad_sequences builds
+        # (PINN:66-76); `records_to_reference_json` turns them back into the ragged lists of the wire format
+        "roller_x_locations": x_at(cases.roller_nodes_t),
+        "force_x_locations": x_at(cases.force_nodes_t),
+        "force_values": cases.force_values_t,
+        "node_positions": xs,
+        "roller_nodes": cases.roller_nodes_t,
+        "force_nodes": cases.force_nodes_t,
+        "num_nodes": cfg.num_nodes,
+        "L": cases.L,
+        "rotations": rot,
+        "deflections": defl,
+        "n_rollers": cases.n_rollers,
+        "n_forces": cases.n_forces,
+    }
 
 
 def generate_dataset(n_cases: int, cfg: Optional[SizingConfig] = None, device="cuda", seed: int = 20250307,
@@ -591,33 +603,13 @@ def generate_dataset(n_cases: int, cfg: Optional[SizingConfig] = None, device="c
     cases = make_cases(n_cases, cfg, seed, device=device, lo=lo, hi=hi)     # generated on the GPU: only the blocks this range touches
     st = optimize_cases(cases, cfg, device, poll_every=poll_every, reuse=True, gradient=gradient, alpha_deflection=alpha_deflection,
                         deflection_limit=deflection_limit)     # everything handed out below is a copy
-    sol = st.sol
-    rot, defl = sol.theta.clone(), sol.v.clone()
-    if cfg.zero_last_node:
-        rot[:, -1] = 0.0
-        defl[:, -1] = 0.0
-    xs = cases.node_positions
-    x_at = lambda nodes: torch.gather(xs, 1, (nodes - 1).clamp_min(0)) * (nodes > 0)   # noqa: E731  zero-padded like the ids
     return {
-        # ragged fields as zero-padded tensors + counts: exactly the arrays the reference's pad_sequences builds
-        # (PINN:66-76); `records_to_reference_json` turns them back into the ragged lists of the wire format
-        "roller_x_locations": x_at(cases.roller_nodes_t),
-        "force_x_locations": x_at(cases.force_nodes_t),
-        "force_values": cases.force_values_t,
+        **_case_record_fields(cases, cfg, st.sol),
         "I_values": st.I.clone(),                 # float32, AFTER the last Adam step (:239); (copies: the state is re-armed in place by the next shard)
         "shear_forces": st.V32,                   # float32, state of the last solve (:240)
         "bending_moments": st.M32,
-        "node_positions": xs,
-        "roller_nodes": cases.roller_nodes_t,
-        "force_nodes": cases.force_nodes_t,
-        "num_nodes": cfg.num_nodes,
-        "L": cases.L,
-        "rotations": rot,
-        "deflections": defl,
-        "n_rollers": cases.n_rollers,
-        "n_forces": cases.n_forces,
         "epochs_run": st.epochs_run.clone(),
-        "status": sol.status.clone(),
+        "status": st.sol.status.clone(),
         # not a reference field: the float64 inertias the recorded V / M / rotations / deflections were solved with
         # (the state BEFORE the last Adam step; `I_values` is the state after it -- the reference's one-step lag)
         "I_solved": st.I64 if st._fused else st.I64.clone(),

@@ -1,17 +1,21 @@
-"""What the two sizing loops share on the host (beams: sizing.py, frames: frames.py): the check of the objective's arguments, the one
-launch of the optimiser step (csrc/sizing_step.hip, csrc/sizing_grad.hip: both loops use one step-kernel family), the eager
-"run epochs, poll `active` every k" loop and the replay loop of a captured poll interval with its lagging poll.  Nothing here knows
-a beam from a frame."""
+"""What the sizing loops share on the host (beams: sizing.py, multicase.py; frames: frames.py, frame_designs.py, frame_groups.py; the
+design loss beside them): the checks of the objective's and the aggregate's arguments, the optimiser state every loop starts from and
+its step-size table, the one launch of the optimiser step (csrc/sizing_step.hip, csrc/sizing_grad.hip: one step-kernel family), the
+eager "run epochs, poll `active` every k" loop, the replay loop of a captured poll interval with its lagging poll, and the driver
+that chooses between the two.  Nothing here knows a beam from a frame."""
 from __future__ import annotations
 
+import collections
 import ctypes
 from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _cabi
 
 GRADIENTS = ("explicit", "total")
+AGGREGATES = ("sum", "max")
 
 
 def checked_objective(gradient: str, terms: Sequence[Tuple[str, float, Optional[float]]]) -> tuple:
@@ -35,6 +39,28 @@ def checked_objective(gradient: str, terms: Sequence[Tuple[str, float, Optional[
     return tuple(out)
 
 
+def checked_aggregate(aggregate: str, weights, C: Optional[int] = None) -> tuple:
+    """(the aggregate's index, `weights` -- a sequence, an array or a tensor -- as a float64 numpy [C] or None), checked.  C None: the
+    name alone, for a caller that has other refusals to make before the weights' values, and calls again with C."""
+    if aggregate not in AGGREGATES:
+        raise ValueError(f"aggregate must be one of {AGGREGATES}, got {aggregate!r}")
+    if aggregate == "max" and weights is not None:
+        raise ValueError('aggregate="max" takes no weights: the governing case is the largest unweighted penalty')
+    if weights is not None and C is not None:
+        weights = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+        if weights.shape != (C,) or not np.isfinite(weights).all() or (weights < 0).any():
+            raise ValueError(f"weights must be {C} finite non-negative numbers")
+    return AGGREGATES.index(aggregate), weights
+
+
+def step_schedule(hp, device) -> torch.Tensor:
+    """The tabulated Adam step sizes of `hp` (an `ops_sizing_params`) on `device`: [max(max_epochs, 1), 2] float32, per epoch the
+    step size and the bias correction."""
+    sched = np.zeros((max(int(hp.max_epochs), 1), 2), dtype=np.float32)
+    _cabi.load().ops_sizing_schedule_f32(ctypes.byref(hp), sched.ctypes.data)
+    return torch.as_tensor(sched, device=device)
+
+
 class _StepState(NamedTuple):
     """The tensors the optimiser step kernels update in place, one row per case (beam or frame)."""
     I: torch.Tensor                 # [B,Ne] float32: the design
@@ -48,6 +74,27 @@ class _StepState(NamedTuple):
     last: torch.Tensor              # [B] float32: the epoch's total_loss
     V32: Optional[torch.Tensor]     # [B,Ne] float32 records of the step's rounded forces; both None: not recorded
     M32: Optional[torch.Tensor]
+
+
+# what Adam and the early stop keep per row (a case, a frame or a design -- [rows, n_vars] and [rows]), in the step entry points' order
+OptimiserState = collections.namedtuple("OptimiserState", _StepState._fields[2:9])
+
+
+def new_optimiser_state(rows: int, n_vars: int, device) -> OptimiserState:
+    """The tensors of an `OptimiserState`, allocated and not yet armed."""
+    f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+    return OptimiserState(torch.empty((rows, n_vars), **f32), torch.empty((rows, n_vars), **f32), torch.empty((rows,), **f32),
+                          torch.empty((rows,), **i32), torch.empty((rows,), **i32), torch.empty((rows,), dtype=torch.uint8, device=device),
+                          torch.empty((rows,), **f32))
+
+
+def arm_optimiser_state(s: OptimiserState) -> OptimiserState:
+    """The state before the first epoch, written IN PLACE (a captured graph may point at these tensors): the one statement of it."""
+    for t in (s.exp_avg, s.exp_avg_sq, s.patience_cnt, s.epochs, s.last):
+        t.zero_()
+    s.best.fill_(float("inf"))
+    s.active.fill_(1)
+    return s
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -111,3 +158,33 @@ def replay_epochs(graph, n_max: int, poll_every: int, done: int, active: torch.T
                 break
         k += 1
     return done
+
+
+def poll_flags() -> tuple:
+    """The (pinned flag pair, two events) `replay_epochs` polls through.  Pinned allocations are slow: a caller that runs many loops
+    keeps one."""
+    return torch.zeros(2, dtype=torch.uint8).pin_memory(), [torch.cuda.Event(), torch.cuda.Event()]
+
+
+def history_callback(history: Optional[list], last: torch.Tensor) -> Optional[Callable[[], None]]:
+    """The `after_epoch` that appends a copy of `last` (the epoch's loss per row) to `history`; None without a list."""
+    return None if history is None else lambda: history.append(last.clone())
+
+
+def run_sizing_loop(epoch: Callable[[], None], n_max: int, poll_every: int, active: torch.Tensor, last: torch.Tensor, device, *,
+                    use_graph: bool, record: bool = False, graph=None, poll: Optional[tuple] = None, lag: int = 1) -> tuple:
+    """The beam loops' driver.  `use_graph`: `poll_every` epochs replayed as one HIP graph (the epoch body is launch-bound) through
+    `replay_epochs` with `poll` (None: a new `poll_flags()`) and `lag` -- `graph` when the caller kept one of this very `epoch`, else
+    captured here after one eager epoch, the warm-up outside capture (it allocates the solution buffers).  Otherwise `run_epochs`,
+    with `record` keeping every epoch's `last`.  Returns (the graph used or None, the history [epochs, rows] or None)."""
+    if use_graph:
+        done = 0
+        if graph is None:
+            from .runtime import capture_graph
+            graph, _ = capture_graph(torch.cuda.Stream(device=device), device, lambda: [epoch() for _ in range(poll_every)], 1, warm=epoch)
+            done = 1
+        replay_epochs(graph, n_max, poll_every, done, active, *(poll or poll_flags()), lag=lag)
+        return graph, None
+    history = [] if record else None
+    run_epochs(epoch, n_max, poll_every, active, history_callback(history, last))
+    return None, (torch.stack(history) if history else last.new_zeros((0, last.shape[0]))) if record else None
