@@ -25,7 +25,32 @@
  *   loads [Nn,3] (loads_bstride 0) or [B,Nn,3] (loads_bstride 3 Nn); elem_w [Ne,2] (w_bstride 0) or [B,Ne,2] (w_bstride 2 Ne).
  * No atomics: the results are reproducible and depend neither on B nor on a frame's place in the batch.  B == 0: OK, nothing is
  * launched; a negative size, n_nodes < 2, n_elems < 1, a stride other than the two allowed values or a NULL required pointer:
- * ERR_INVALID_ARG, nothing is written.  One launch each.  Never throws, never blocks. */
+ * ERR_INVALID_ARG, nothing is written.  One launch each.  Never throws, never blocks.
+ *
+ * Natural frequencies and mode shapes on the kept factorisation: three more entry points on the same node-walk
+ * tables, same conventions.  The problem is K(I) phi = lambda M phi on the free DOFs, K the matrix ops_frame_factor_solve_f64
+ * (include/openpystruct_amd_frame_cases.h) factorises, M = element mass (mass per unit length elem_mass [Ne]; consistent != 0: the
+ * rotated consistent 6 x 6 matrix, 0: lumped, elem_mass L / 2 on the four translations) + nodal masses; M does not depend on I.
+ * One iteration of the subspace iteration on p <= 8 vectors is three calls on one stream, R [B,p,Nn,3] = M Q of the iteration before
+ * (at the start M X0, X0 zero on constrained DOFs):
+ *   1. ops_frame_resolve_f64 with C = p, rhs = R (rhs_bstride = p * n_nodes * 3): disp = X = K^-1 R [B,p,Nn,3], status = row_status;
+ *   2. ops_frame_mass_apply_f64:  y[r] = M x[r] for R rows [R,Nn,3], one thread per (row, node): the node's own nodal term, then its
+ *      incident element ends in table order.  nodal_mass [Nn,3] (nodal_bstride 0), [B,Nn,3] (nodal_bstride 3 Nn; the frame of row r
+ *      is r / rows_per_frame) or NULL (none);
+ *   3. ops_frame_modes_ritz_f64:  one wavefront per frame.  Kr = sym(X^T R), Mr = X^T MX, Mr = G G^T, A = G^-1 Kr G^-T, cyclic Jacobi
+ *      on A in row-cyclic order until the off-diagonal sum of squares is at most (2^-52 trace)^2, or 16 sweeps; Ritz values
+ *      ascending into lambda [B,p]; Z = G^-T V; Q = X Z (M-orthonormal); R <- MX Z.  change [B,p] = |lambda - lambda_prev| / lambda
+ *      with lambda_prev what `lambda` held at the call: the caller fills it with +inf before the first iteration, which gives
+ *      change = +inf there.  status [B]: 0; 1 when any of the frame's p row_status is non-zero (the keeping solve or a re-solve row
+ *      failed); 2 when Mr is not positive definite (p exceeds the number of DOFs that carry mass).  A frame with a non-zero status
+ *      gets NaN in Q, lambda and change and keeps its R; no other frame is touched.  The dot products are per-lane strided partial
+ *      sums added by a fixed butterfly: no atomics, the same bits for every B and every place in the batch.
+ * ops_frame_modes_grad_f64: gI[b,e] = sum over j < m, in mode order, of g_lambda[b,j] phi_j,e . (K_b,e phi_j,e), K_b,e the bending part
+ * of the rotated stiffness per unit inertia; phi [B,p,Nn,3] M-normalised, g_lambda [B,m], 1 <= m <= p; a frame with status[b] != 0
+ * gets a NaN row.  One thread per (frame, element).
+ * R == 0 / B == 0: OK, nothing is launched; a negative size, rows_per_frame < 1, n_nodes < 2, n_elems < 1, p outside 1..8, m outside
+ * 1..p, a stride other than the two allowed values or a NULL pointer (nodal_mass alone may be NULL): ERR_INVALID_ARG, decided
+ * before any HIP call, nothing is written. */
 #ifndef OPENPYSTRUCT_AMD_FRAME_LOADS_H
 #define OPENPYSTRUCT_AMD_FRAME_LOADS_H
 
@@ -43,6 +68,14 @@ int ops_frame_load_forces_f64(int B, int n_elems, const double* elem_geo, const 
 int ops_frame_load_vjp_f64(int B, int n_nodes, int n_elems, const double* elem_geo, const int32_t* conn,
                            const double* lambda, const double* g_forces, const double* gV, const double* gM,
                            const int32_t* status_fwd, const int32_t* status_adj, double* g_w, void* stream);
+int ops_frame_mass_apply_f64(int R, int rows_per_frame, int n_nodes, int n_elems, const double* elem_geo, const int32_t* conn,
+                             const int32_t* node_elem_ptr, const int32_t* node_elem_idx, const double* elem_mass, int consistent,
+                             const double* nodal_mass, long nodal_bstride, const double* x, double* y, void* stream);
+int ops_frame_modes_ritz_f64(int B, int p, int n_nodes, const double* X, const double* MX, double* R, double* Q,
+                             double* lambda, double* change, const int32_t* row_status, int32_t* status, void* stream);
+int ops_frame_modes_grad_f64(int B, int m, int p, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
+                             const int32_t* conn, const double* phi, const double* g_lambda, const int32_t* status, double* gI,
+                             void* stream);
 
 #ifdef __cplusplus
 }

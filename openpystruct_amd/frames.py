@@ -405,10 +405,10 @@ class FrameFactor:
         self.topo, self.I, self.workspace, self.solution, self.status = topo, I, workspace, solution, solution.status
         self._scratch = {}
 
-    def _buffer(self, name: str, shape: tuple) -> torch.Tensor:
+    def _buffer(self, name: str, shape: tuple, dtype=torch.float64) -> torch.Tensor:
         t = self._scratch.get((name, shape))
         if t is None:
-            t = self._scratch[(name, shape)] = torch.empty(shape, dtype=torch.float64, device=self.I.device)
+            t = self._scratch[(name, shape)] = torch.empty(shape, dtype=dtype, device=self.I.device)
         return t
 
 

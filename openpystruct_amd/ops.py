@@ -6,7 +6,8 @@ Covers exactly the subset `setup_model` + `generate_sample` use
 (/root/reference/OpenPyStruct_BeamOpt_training_SingleCore.py:93-124, :176-190, :224-232):
 wipe, model, node, fix, geomTransf, element('elasticBeamColumn'), timeSeries, pattern, load,
 eleLoad('-beamUniform'), system, numberer, constraints, integrator, algorithm, analysis, analyze,
-eleResponse(e, 'forces'), nodeDisp.  Semantics kept: one process-global domain, 1-based tags,
+eleResponse(e, 'forces'), nodeDisp -- and, beyond the reference, mass, element(..., '-mass', m, ['-cMass']), eigen and
+nodeEigenvector (natural frequencies).  Semantics kept: one process-global domain, 1-based tags,
 `analyze` returns 0 on success and a non-zero code (never an exception) when the stiffness matrix is
 not positive definite, `eleResponse` returns a fresh list of 6 global end forces
 [Fx1, Fy1, Mz1, Fx2, Fy2, Mz2], `nodeDisp(node, dof)` a float (dof 1-based).
@@ -42,6 +43,9 @@ class _Domain:
         self.elements: Dict[int, tuple] = {}     # tag -> (ni, nj, A, E, Iz)
         self.loads: Dict[int, List[float]] = {}  # node -> [Fx, Fy, Mz]
         self.ele_loads: Dict[int, tuple] = {}    # ele -> (Wy, Wx)
+        self.masses: Dict[int, tuple] = {}       # node -> (mx, my, mz)
+        self.ele_mass: Dict[int, tuple] = {}     # ele -> (mass per unit length, consistent)
+        self.modes = None                        # (eigenvalues [n], shapes [n,Nn,3]) after eigen
         self.system = None
         self.analysis = None
         self.result = None                       # dict after a successful analyze
@@ -135,8 +139,17 @@ def geomTransf(kind, tag, *rest):
 def element(kind, tag, *args):
     if kind != "elasticBeamColumn":
         raise NotImplementedError("element 'elasticBeamColumn' only (SingleCore.py:107)")
-    ni, nj, A, E, Iz = args[:5]     # (ni, nj, A, E, Iz, transfTag)
+    ni, nj, A, E, Iz = args[:5]     # (ni, nj, A, E, Iz, transfTag, ['-mass', m, ['-cMass']])
     _dom.elements[int(tag)] = (int(ni), int(nj), float(A), float(E), float(Iz))
+    rest = list(args[5:])
+    _dom.ele_mass.pop(int(tag), None)
+    if "-mass" in rest:             # mass per unit length; '-cMass': the consistent matrix instead of OpenSees' default, lumped
+        _dom.ele_mass[int(tag)] = (float(rest[rest.index("-mass") + 1]), "-cMass" in rest)
+
+
+def mass(node_tag, mx, my, mz):
+    """Nodal mass on (ux, uy, rz), as OpenSees' `mass` command: a second call for a node replaces the first."""
+    _dom.masses[int(node_tag)] = (float(mx), float(my), float(mz))
 
 
 def timeSeries(kind, tag, *rest):
@@ -451,6 +464,49 @@ def nodeDisp(node_tag, dof):
         raise RuntimeError("no committed state: analyze() has not succeeded")
     key = {1: "ux", 2: "v", 3: "th"}[int(dof)]
     return float(_dom.result[key][int(node_tag) - 1])
+
+
+def eigen(*args):
+    """`eigen([solver,] n)`: the n lowest eigenvalues (omega^2) of the recorded model as a list, through the frame path with a batch
+    of one (`frame_modes.frame_solve_modes` with its defaults; straight beams go the same way).  Every element needs `-mass`; the
+    elements are all lumped (OpenSees' default) or all `-cMass`.  The solver name is accepted and ignored: the lowest modes come
+    from a subspace iteration on the kept factorisation.  The eigenvectors `nodeEigenvector` hands out are
+    M-normalised (phi^T M phi = 1) with the component of largest magnitude positive -- not OpenSees' own scaling."""
+    a = [v for v in args if not isinstance(v, str)]
+    if len(a) != 1 or int(a[0]) < 1:
+        raise ValueError("eigen([solver,] n) with n >= 1 expected")
+    n, d = int(a[0]), _dom
+    if _queue is not None:
+        raise NotImplementedError("eigen() inside deferred(): the modes are solved per model, call it outside")
+    fa = _frame_arrays(d)
+    kinds = {c for _, c in d.ele_mass.values()}
+    if len(kinds) > 1:
+        raise NotImplementedError("a model that mixes consistent and lumped element mass (-cMass on some elements only)")
+    if sorted(d.ele_mass) != sorted(d.elements):
+        raise NotImplementedError("every element needs -mass: the mass per unit length must be strictly positive")
+    from .frame_modes import FrameMass, frame_solve_modes
+    dev = _device_of(d)
+    topo = _topology(fa, dev)
+    nodal = np.zeros((len(d.nodes), 3))
+    for t, v in d.masses.items():
+        nodal[t - 1] = v
+    mbar = np.array([d.ele_mass[e][0] for e in range(1, len(d.elements) + 1)])
+    ms = FrameMass(topo, mbar, nodal if d.masses else None, kind="consistent" if kinds == {True} else "lumped")
+    with torch.cuda.device(dev):
+        r = frame_solve_modes(topo, torch.as_tensor(fa["I"][None], dtype=torch.float64, device=dev), ms, n_modes=n)
+        if int(r.status[0]) != 0:
+            d.modes = None
+            raise RuntimeError(f"eigen: the solve failed with status {int(r.status[0])}")
+        d.modes = (r.eigenvalues[0].cpu().numpy(), r.shapes[0].cpu().numpy())
+    return [float(v) for v in d.modes[0]]
+
+
+def nodeEigenvector(node_tag, mode, dof=None):
+    """The M-normalised eigenvector of `mode` (1-based) at a node: [ux, uy, rz], or one component with `dof` (1-based)."""
+    if _dom.modes is None:
+        raise RuntimeError("no eigenvectors: eigen() has not succeeded")
+    v = _dom.modes[1][int(mode) - 1, int(node_tag) - 1]
+    return [float(c) for c in v] if dof is None else float(v[int(dof) - 1])
 
 
 @contextmanager

@@ -18,10 +18,14 @@ its node count (the output shapes of the fake implementation); `frame_solve_auto
 in.  Gradients reach I and loads; status is not differentiable.
 
 `torch.ops.openpystruct_amd.frame_solve_loads` / `frame_solve_loads_vjp` are that pair with the element loads as one more tensor
-argument ([Ne,2] shared or [B,Ne,2]: DESIGN.md §9i, csrc/frame_loads.hip); gradients reach them too."""
+argument ([Ne,2] shared or [B,Ne,2]: DESIGN.md §9i, csrc/frame_loads.hip); gradients reach them too.
+
+`torch.ops.openpystruct_amd.frame_eigenvalues` / `frame_eigenvalues_vjp` are the lowest eigenvalues of K(I) phi = lambda M phi
+(`frame_modes.differentiable_frame_frequencies`); gradients reach I, the mode shapes carry none."""
 from __future__ import annotations
 
 import itertools
+import math
 import weakref
 from typing import Optional, Tuple
 
@@ -187,3 +191,79 @@ def frame_solve_autograd(topo: frames.FrameTopology, I: T, loads: Optional[T] = 
     if element_loads is not None:
         return frames.FrameSolution(*torch.ops.openpystruct_amd.frame_solve_loads(I, loads, element_loads, topo.Nn, _topology_id(topo)))
     return frames.FrameSolution(*torch.ops.openpystruct_amd.frame_solve(I, loads, topo.Nn, _topology_id(topo)))
+
+
+# ---- eigenvalues of K(I) phi = lambda M phi ----
+# A FrameMass is host state as a FrameTopology is: named by an integer, valid while the object lives.
+_masses = weakref.WeakValueDictionary()
+
+
+def _mass_id(mass) -> int:
+    mid = mass.__dict__.get("_op_id")
+    if mid is None:
+        mid = mass.__dict__["_op_id"] = next(_topology_ids)
+        _masses[mid] = mass
+    return mid
+
+
+@torch.library.custom_op("openpystruct_amd::frame_eigenvalues", mutates_args=(), device_types="cuda")
+def frame_eigenvalues_op(I: T, X0: Optional[T], n_modes: int, n_vectors: int, iters: int, tol: float, max_iters: int, poll_every: int,
+                         n_nodes: int, topology: int, mass: int) -> Tuple[T, T, T]:
+    """(eigenvalues [B,m], shapes [B,m,Nn,3], status [B]) of `frame_modes.frame_solve_modes`; n_vectors = 0: its default, iters = 0:
+    run to `tol`."""
+    from .frame_modes import frame_solve_modes
+    topo, ms = _topology(topology), _masses.get(mass)
+    if ms is None:
+        raise RuntimeError(f"openpystruct_amd::frame_eigenvalues: no live FrameMass is registered as {mass}")
+    if n_nodes != topo.Nn:
+        raise ValueError(f"openpystruct_amd::frame_eigenvalues: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
+    r = frame_solve_modes(topo, I.contiguous(), ms, n_modes=n_modes, n_vectors=n_vectors or None, iters=iters or None, tol=tol,
+                        max_iters=max_iters, poll_every=poll_every, X0=X0)
+    return r.eigenvalues, r.shapes, r.status
+
+
+@frame_eigenvalues_op.register_fake
+def _(I, X0, n_modes, n_vectors, iters, tol, max_iters, poll_every, n_nodes, topology, mass):
+    B = I.shape[0]
+    return I.new_empty((B, n_modes)), I.new_empty((B, n_modes, n_nodes, 3)), I.new_empty((B,), dtype=torch.int32)
+
+
+@torch.library.custom_op("openpystruct_amd::frame_eigenvalues_vjp", mutates_args=(), device_types="cuda")
+def frame_eigenvalues_vjp_op(shapes: T, status: T, g_eigenvalues: T, topology: int) -> T:
+    from .frame_modes import _modes_grad
+    return _modes_grad(_topology(topology), shapes, status, g_eigenvalues)
+
+
+@frame_eigenvalues_vjp_op.register_fake
+def _(shapes, status, g_eigenvalues, topology):
+    return shapes.new_empty((shapes.shape[0], _topology(topology).Ne))
+
+
+def _eigenvalues_setup_context(ctx, inputs, output):
+    ctx.mark_non_differentiable(output[1], output[2])          # the shapes carry no gradient
+    ctx.save_for_backward(output[1], output[2])
+    ctx.topo, ctx.mass, ctx.topology = _topologies.get(inputs[-2]), _masses.get(inputs[-1]), inputs[-2]
+
+
+def _eigenvalues_backward(ctx, g_eig, g_shapes, g_status):
+    shapes, status = ctx.saved_tensors
+    gI = torch.ops.openpystruct_amd.frame_eigenvalues_vjp(shapes, status, g_eig.contiguous(), ctx.topology) if ctx.needs_input_grad[0] else None
+    return (gI,) + (None,) * 10
+
+
+frame_eigenvalues_op.register_autograd(_eigenvalues_backward, setup_context=_eigenvalues_setup_context)
+
+
+def frame_frequencies_autograd(topo: frames.FrameTopology, I: T, mass, n_modes: int = 1, n_vectors: Optional[int] = None,
+                               iters: Optional[int] = None, tol: float = 1e-10, max_iters: int = 64, poll_every: int = 4,
+                               X0: Optional[T] = None):
+    from .frame_modes import FrameMass      # (the package's attribute `frame_modes` is the function of that name)
+    if not isinstance(mass, FrameMass) or mass.topo is not topo:
+        raise ValueError("mass must be a FrameMass of this topology")
+    if not torch.is_tensor(I) or I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne:
+        raise ValueError(f"I must be float64 [B, {topo.Ne}]")
+    if not I.is_cuda:
+        raise RuntimeError("differentiable_frame_frequencies needs GPU tensors: openpystruct_amd has no CPU fallback")
+    eig, _, _ = torch.ops.openpystruct_amd.frame_eigenvalues(I, X0, int(n_modes), int(n_vectors or 0), int(iters or 0), float(tol), int(max_iters),
+                                                             int(poll_every), topo.Nn, _topology_id(topo), _mass_id(mass))
+    return eig, torch.sqrt(eig) / (2.0 * math.pi)
