@@ -50,7 +50,35 @@
  * gets a NaN row.  One thread per (frame, element).
  * R == 0 / B == 0: OK, nothing is launched; a negative size, rows_per_frame < 1, n_nodes < 2, n_elems < 1, p outside 1..8, m outside
  * 1..p, a stride other than the two allowed values or a NULL pointer (nodal_mass alone may be NULL): ERR_INVALID_ARG, decided
- * before any HIP call, nothing is written. */
+ * before any HIP call, nothing is written.
+ *
+ * Linear buckling load factors on the kept factorisation: three more entry points, same tables, same conventions.
+ * The problem is K(I) phi = lambda S phi on the free DOFs, S = -K_g(N) the negated geometric stiffness of the axial forces
+ * N_e = ((c f3 + s f4) - (c f0 + s f1)) / 2 (tension positive) of `forces` [B,Ne,6], the global end forces of a reference static
+ * solve of the same frames; consistent != 0: N / (30 L) [[36, 3L, -36, 3L], [3L, 4L^2, -3L, -L^2], [-36, -3L, 36, -3L], [3L, -L^2,
+ * -3L, 4L^2]] on the local (v1, th1, v2, th2), rotated; 0: N / L [[1, -1], [-1, 1]] on (v1, v2), the linearised P-Delta matrix.  S is
+ * indefinite and may be rank deficient, so the iteration is the inverse iteration on K^-1 S, R [B,p,Nn,3] = S Q of the iteration
+ * before (at the start S X0, X0 zero on constrained DOFs):
+ *   1. ops_frame_resolve_f64 with C = p, rhs = R: disp = X = K^-1 R, status = row_status;
+ *   2. ops_frame_geom_apply_f64:  y[r] = S x[r] for R rows [R,Nn,3] (the frame of row r is r / rows_per_frame), one thread per (row,
+ *      node), the node's incident element ends in table order;
+ *   3. ops_frame_buckling_ritz_f64:  one wavefront per frame.  Kr = sym(X^T R) (= X^T K X), Sr = X^T SX, Kr = G G^T, A = G^-1 Sr G^-T,
+ *      cyclic Jacobi in row-cyclic order until the off-diagonal sum of squares is at most (2^-52)^2 times the sum of all squares of
+ *      A, or 16 sweeps; Ritz values DESCENDING into mu [B,p]; lambda [B,p] = 1 / mu where mu > 0, else +inf; Z = G^-T V; Q = X Z
+ *      (K-orthonormal: Q^T S Q = diag(mu)); R <- SX Z.  change [B,p] = |mu - mu_prev| / |mu| with mu_prev what `mu` held at the call
+ *      (the caller fills it with +inf before the first iteration).  status [B]: 0; 1 when any of the frame's p row_status is
+ *      non-zero; 2 when Kr is not positive definite: a Cholesky pivot at or below 2^-40 of its diagonal entry (p exceeds the rank
+ *      of S, or the start is dependent; in both the pivot is rounding noise of either sign).  A frame with a non-zero
+ *      status gets NaN in Q, mu, lambda and change and keeps its R; no other frame is touched.  No atomics, no LDS: the same bits for
+ *      every B and every place in the batch.
+ * ops_frame_buckling_grad_f64, one thread per (frame, element), the sums over j < m in mode order and over finite lambda alone:
+ *   gI_direct[b,e] = sum_j g_lambda[b,j] lambda[b,j] phi_j,e . (K_b,e phi_j,e),
+ *   g_forces[b,e,:] = (sum_j g_lambda[b,j] lambda[b,j]^2 phi_j,e . (k_g,unit,e phi_j,e)) (-c/2, -s/2, 0, c/2, s/2, 0),
+ * the cotangent of the reference solve's end forces: dlambda/dI = gI_direct + the gI of that solve's vector-Jacobian product
+ * (include/openpystruct_amd_frame_cases.h).  phi [B,p,Nn,3] K-normalised, lambda and g_lambda [B,m], 1 <= m <= p, `consistent` the
+ * kind of the geometric matrix; a frame with status[b] != 0 gets NaN rows.
+ * Refusals as above: R == 0 / B == 0: OK; a negative size, rows_per_frame < 1, n_nodes < 2, n_elems < 1, p outside 1..8, m outside
+ * 1..p or a NULL pointer: ERR_INVALID_ARG, decided before any HIP call, nothing is written. */
 #ifndef OPENPYSTRUCT_AMD_FRAME_LOADS_H
 #define OPENPYSTRUCT_AMD_FRAME_LOADS_H
 
@@ -76,6 +104,14 @@ int ops_frame_modes_ritz_f64(int B, int p, int n_nodes, const double* X, const d
 int ops_frame_modes_grad_f64(int B, int m, int p, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
                              const int32_t* conn, const double* phi, const double* g_lambda, const int32_t* status, double* gI,
                              void* stream);
+int ops_frame_geom_apply_f64(int R, int rows_per_frame, int n_nodes, int n_elems, const double* elem_geo, const int32_t* conn,
+                             const int32_t* node_elem_ptr, const int32_t* node_elem_idx, const double* forces, int consistent,
+                             const double* x, double* y, void* stream);
+int ops_frame_buckling_ritz_f64(int B, int p, int n_nodes, const double* X, const double* SX, double* R, double* Q, double* mu,
+                                double* lambda, double* change, const int32_t* row_status, int32_t* status, void* stream);
+int ops_frame_buckling_grad_f64(int B, int m, int p, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
+                                const int32_t* conn, int consistent, const double* phi, const double* lambda,
+                                const double* g_lambda, const int32_t* status, double* gI_direct, double* g_forces, void* stream);
 
 #ifdef __cplusplus
 }

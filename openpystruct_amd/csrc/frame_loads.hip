@@ -2,6 +2,8 @@
 // include/openpystruct_amd_frame_loads.h.  Arithmetic: frame_loads.hpp.  Design: DESIGN.md §9i.
 // Behind them, on the same node-walk tables: the three kernels of the natural frequencies on the kept factorisation (mass apply,
 // Ritz step, eigenvalue gradient).  Arithmetic: frame_modes.hpp.  Design: DESIGN.md §9p.
+// And the three kernels of the linear buckling load factors (geometric-stiffness apply, Ritz step of the swapped pencil, gradient
+// terms).  Arithmetic: frame_buckling.hpp.  Design: DESIGN.md §9q.
 //
 // The solve is linear in the element loads, so the band kernels stay as they are: the caller runs
 // ops_frame_solve_batched_f64_ex between the first two kernels (loads = rhs, per frame; elem_w = zeros).  All three kernels
@@ -11,6 +13,7 @@
 
 #include "../../include/openpystruct_amd_frame_loads.h"
 #include "frame_loads.hpp"
+#include "frame_buckling.hpp"
 #include "frame_modes.hpp"
 #include "sizing_math.hpp"
 
@@ -147,6 +150,92 @@ __global__ __launch_bounds__(256) void frame_modes_ritz_kernel(int B, int n_node
   if (lane == 0) a.status[b] = st;
 }
 
+// ---- linear buckling load factors on the kept factorisation ----
+struct FrameBucklingParams : FrameStreamTopo {  // B: the rows of the geometric apply, the frames of the gradient
+  const double* forces;            // [B,Ne,6] the reference solve's end forces
+  int consistent, rows_per_frame, m, p;
+  const double* x;                 // [R,Nn,3]; the gradient: phi [B,p,Nn,3]
+  double* y;                       // [R,Nn,3]
+  const double* lambda;            // [B,m]
+  const double* g_lambda;          // [B,m]
+  const int32_t* status;           // [B]
+  double* gI_direct;               // [B,Ne]
+  double* g_forces;                // [B,Ne,6]
+};
+
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_geom_apply_kernel(const FrameBucklingParams p) {
+  frame_stream_rows(p.B, p.Nn, [&](long i, long row, int n) {
+    double y[3];
+    fb_node_geom(p.Nn, p.Ne, p.elem_geo, p.conn, p.node_elem_ptr, p.node_elem_idx, p.forces, p.consistent, p.x, row,
+                 row / p.rows_per_frame, n, y);
+    double* o = p.y + i * 3;
+    o[0] = y[0]; o[1] = y[1]; o[2] = y[2];
+  });
+}
+
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_buckling_grad_kernel(const FrameBucklingParams p) {
+  frame_stream_rows(p.B, p.Ne, [&](long i, long b, int e) {
+    double d, gf[6];
+    fb_elem_grad(p.m, p.p, p.Nn, p.elem_geo, p.elem_E, p.conn, p.consistent, p.x, p.lambda, p.g_lambda, b, e, &d, gf);
+    const bool bad = p.status[b] != 0;
+    p.gI_direct[i] = bad ? __builtin_nan("") : d;
+    for (int k = 0; k < 6; ++k) p.g_forces[i * 6 + k] = bad ? __builtin_nan("") : gf[k];
+  });
+}
+
+struct FrameBucklingRitzArgs {
+  const double* X; const double* SX;     // [B,P,Nn,3]
+  double* R; double* Q;                  // [B,P,Nn,3]  R: read as S Q of the iteration before, written as the next one's
+  double* mu; double* lambda; double* change;   // [B,P]  mu: read as the iteration before's
+  const int32_t* row_status;             // [B,P]
+  int32_t* status;                       // [B]
+};
+
+// one wavefront per frame, as frame_modes_ritz_kernel: partial sums, the fixed butterfly, the small part on every lane, the update
+template <int P>
+__global__ __launch_bounds__(256) void frame_buckling_ritz_kernel(int B, int n_nodes, const FrameBucklingRitzArgs a) {
+  const long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63;
+  const long n = 3L * n_nodes, base = b * P * n;
+  const double *x = a.X + base, *sx = a.SX + base;
+  double *r = a.R + base, *q = a.Q + base;
+  int st = 0;
+  for (int j = 0; j < P; ++j) st |= a.row_status[b * P + j] != 0;
+  double Z[P * P], mu[P], lam[P], change[P];
+  if (st == 0) {
+    double acc[FmRitz<P>::NACC];
+    fm_ritz_partials<P>(n, x, sx, r, lane, acc);
+#pragma unroll
+    for (int k = 0; k < FmRitz<P>::NACC; ++k)
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    double prev[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) prev[j] = a.mu[b * P + j];
+    int sweeps;
+    st = fb_ritz_small<P>(acc, prev, Z, mu, lam, change, &sweeps);
+  }
+  if (st != 0) {      // NaN for this frame alone; R stays, so the next iteration fails the same way with the same status
+    const double nan = __builtin_nan("");
+    for (long t = lane; t < P * n; t += 64) q[t] = nan;
+#pragma unroll
+    for (int j = 0; j < P; ++j) mu[j] = lam[j] = change[j] = nan;
+  } else {
+    fm_ritz_update<P>(n, x, sx, Z, lane, q, r);
+  }
+  if (lane < P) {
+    double u = mu[0], l = lam[0], c = change[0];
+#pragma unroll
+    for (int j = 1; j < P; ++j)
+      if (lane == j) { u = mu[j]; l = lam[j]; c = change[j]; }
+    a.mu[b * P + lane] = u;
+    a.lambda[b * P + lane] = l;
+    a.change[b * P + lane] = c;
+  }
+  if (lane == 0) a.status[b] = st;
+}
+
 }  // namespace opsamd
 
 using namespace opsamd;
@@ -232,4 +321,47 @@ extern "C" int ops_frame_modes_grad_f64(int B, int m, int p, int n_nodes, int n_
   q.elem_geo = elem_geo; q.elem_E = elem_E; q.conn = conn;
   q.m = m; q.p = p; q.x = phi; q.g_lambda = g_lambda; q.status = status; q.gI = gI;
   return frame_stream_launch(frame_modes_grad_kernel, q, (long)B * n_elems, stream);
+}
+
+extern "C" int ops_frame_geom_apply_f64(int R, int rows_per_frame, int n_nodes, int n_elems, const double* elem_geo,
+                                        const int32_t* conn, const int32_t* node_elem_ptr, const int32_t* node_elem_idx,
+                                        const double* forces, int consistent, const double* x, double* y, void* stream) {
+  if (R < 0 || rows_per_frame < 1 || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
+  if (R == 0) return OPS_AMD_OK;
+  if (!elem_geo || !conn || !node_elem_ptr || !node_elem_idx || !forces || !x || !y) return OPS_AMD_ERR_INVALID_ARG;
+  FrameBucklingParams p{};
+  p.B = R; p.Nn = n_nodes; p.Ne = n_elems;
+  p.elem_geo = elem_geo; p.conn = conn; p.node_elem_ptr = node_elem_ptr; p.node_elem_idx = node_elem_idx;
+  p.forces = forces; p.consistent = consistent != 0; p.rows_per_frame = rows_per_frame; p.x = x; p.y = y;
+  return frame_stream_launch(frame_geom_apply_kernel, p, (long)R * n_nodes, stream);
+}
+
+extern "C" int ops_frame_buckling_ritz_f64(int B, int p, int n_nodes, const double* X, const double* SX, double* R, double* Q,
+                                           double* mu, double* lambda, double* change, const int32_t* row_status,
+                                           int32_t* status, void* stream) {
+  if (B < 0 || p < 1 || p > FM_MAX_VECTORS || n_nodes < 2) return OPS_AMD_ERR_INVALID_ARG;
+  if (B == 0) return OPS_AMD_OK;
+  if (!X || !SX || !R || !Q || !mu || !lambda || !change || !row_status || !status) return OPS_AMD_ERR_INVALID_ARG;
+  const FrameBucklingRitzArgs a{X, SX, R, Q, mu, lambda, change, row_status, status};
+  void (*kernel)(int, int, const FrameBucklingRitzArgs) =
+      p == 1 ? frame_buckling_ritz_kernel<1> : p == 2 ? frame_buckling_ritz_kernel<2> : p == 3 ? frame_buckling_ritz_kernel<3>
+      : p == 4 ? frame_buckling_ritz_kernel<4> : p == 5 ? frame_buckling_ritz_kernel<5> : p == 6 ? frame_buckling_ritz_kernel<6>
+      : p == 7 ? frame_buckling_ritz_kernel<7> : frame_buckling_ritz_kernel<8>;
+  return launch_wave_rows(kernel, B, stream, B, n_nodes, a);
+}
+
+extern "C" int ops_frame_buckling_grad_f64(int B, int m, int p, int n_nodes, int n_elems, const double* elem_geo,
+                                           const double* elem_E, const int32_t* conn, int consistent, const double* phi,
+                                           const double* lambda, const double* g_lambda, const int32_t* status,
+                                           double* gI_direct, double* g_forces, void* stream) {
+  if (B < 0 || p < 1 || p > FM_MAX_VECTORS || m < 1 || m > p || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
+  if (B == 0) return OPS_AMD_OK;
+  if (!elem_geo || !elem_E || !conn || !phi || !lambda || !g_lambda || !status || !gI_direct || !g_forces)
+    return OPS_AMD_ERR_INVALID_ARG;
+  FrameBucklingParams q{};
+  q.B = B; q.Nn = n_nodes; q.Ne = n_elems;
+  q.elem_geo = elem_geo; q.elem_E = elem_E; q.conn = conn; q.consistent = consistent != 0;
+  q.m = m; q.p = p; q.x = phi; q.lambda = lambda; q.g_lambda = g_lambda; q.status = status;
+  q.gI_direct = gI_direct; q.g_forces = g_forces;
+  return frame_stream_launch(frame_buckling_grad_kernel, q, (long)B * n_elems, stream);
 }

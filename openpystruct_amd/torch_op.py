@@ -21,7 +21,11 @@ in.  Gradients reach I and loads; status is not differentiable.
 argument ([Ne,2] shared or [B,Ne,2]: DESIGN.md §9i, csrc/frame_loads.hip); gradients reach them too.
 
 `torch.ops.openpystruct_amd.frame_eigenvalues` / `frame_eigenvalues_vjp` are the lowest eigenvalues of K(I) phi = lambda M phi
-(`frame_modes.differentiable_frame_frequencies`); gradients reach I, the mode shapes carry none."""
+(`frame_modes.differentiable_frame_frequencies`); gradients reach I, the mode shapes carry none.
+
+`torch.ops.openpystruct_amd.frame_buckling_factors` / `frame_buckling_factors_vjp` are the lowest critical load factors of
+K(I) phi = lambda S(N) phi under the topology's own loads (`frame_buckling.differentiable_frame_buckling`); gradients
+reach I through the direct term and one adjoint re-solve on a factorisation of the backward's own."""
 from __future__ import annotations
 
 import itertools
@@ -267,3 +271,72 @@ def frame_frequencies_autograd(topo: frames.FrameTopology, I: T, mass, n_modes: 
     eig, _, _ = torch.ops.openpystruct_amd.frame_eigenvalues(I, X0, int(n_modes), int(n_vectors or 0), int(iters or 0), float(tol), int(max_iters),
                                                              int(poll_every), topo.Nn, _topology_id(topo), _mass_id(mass))
     return eig, torch.sqrt(eig) / (2.0 * math.pi)
+
+
+# ---- load factors of K(I) phi = lambda S(N) phi ----
+@torch.library.custom_op("openpystruct_amd::frame_buckling_factors", mutates_args=(), device_types="cuda")
+def frame_buckling_factors_op(I: T, X0: Optional[T], n_modes: int, consistent: int, n_vectors: int, iters: int, tol: float, max_iters: int,
+                              poll_every: int, n_nodes: int, topology: int) -> Tuple[T, T, T]:
+    """(load_factors [B,m], shapes [B,m,Nn,3], status [B]) of `frame_buckling.frame_solve_buckling` under the topology's own loads;
+    consistent = 0: the P-Delta matrix, n_vectors = 0: its default, iters = 0: run to `tol`."""
+    from .frame_buckling import frame_solve_buckling
+    topo = _topology(topology)
+    if n_nodes != topo.Nn:
+        raise ValueError(f"openpystruct_amd::frame_buckling_factors: n_nodes = {n_nodes}, the topology registered as {topology} has {topo.Nn}")
+    r = frame_solve_buckling(topo, I.contiguous(), n_modes=n_modes, kind="consistent" if consistent else "pdelta", n_vectors=n_vectors or None,
+                             iters=iters or None, tol=tol, max_iters=max_iters, poll_every=poll_every, X0=X0)
+    return r.load_factors, r.shapes, r.status
+
+
+@frame_buckling_factors_op.register_fake
+def _(I, X0, n_modes, consistent, n_vectors, iters, tol, max_iters, poll_every, n_nodes, topology):
+    B = I.shape[0]
+    return I.new_empty((B, n_modes)), I.new_empty((B, n_modes, n_nodes, 3)), I.new_empty((B,), dtype=torch.int32)
+
+
+@torch.library.custom_op("openpystruct_amd::frame_buckling_factors_vjp", mutates_args=(), device_types="cuda")
+def frame_buckling_factors_vjp_op(I: T, load_factors: T, shapes: T, status: T, g_load_factors: T, consistent: int, topology: int) -> T:
+    """gI [B,Ne]: the keeping solve once more (the reference state and the factor the adjoint re-solve runs on), then
+    `frame_buckling.frame_buckling_vjp`."""
+    from .frame_buckling import FrameBuckling, frame_buckling_vjp
+    fac = frames.frame_factor(_topology(topology), I.contiguous())
+    res = FrameBuckling(load_factors, None, shapes, None, 0, status, fac.solution, "consistent" if consistent else "pdelta")
+    return frame_buckling_vjp(fac, res, g_load_factors)[0]
+
+
+@frame_buckling_factors_vjp_op.register_fake
+def _(I, load_factors, shapes, status, g_load_factors, consistent, topology):
+    return I.new_empty(I.shape)
+
+
+def _buckling_setup_context(ctx, inputs, output):
+    ctx.mark_non_differentiable(output[1], output[2])          # the shapes carry no gradient
+    ctx.save_for_backward(inputs[0], *output)
+    ctx.topo, ctx.topology, ctx.consistent = _topologies.get(inputs[-1]), inputs[-1], inputs[3]
+
+
+def _buckling_backward(ctx, g_lam, g_shapes, g_status):
+    I, lam, shapes, status = ctx.saved_tensors
+    gI = None
+    if ctx.needs_input_grad[0]:
+        gI = torch.ops.openpystruct_amd.frame_buckling_factors_vjp(I, lam, shapes, status, g_lam.contiguous(), ctx.consistent, ctx.topology)
+    return (gI,) + (None,) * 10
+
+
+frame_buckling_factors_op.register_autograd(_buckling_backward, setup_context=_buckling_setup_context)
+
+
+def frame_buckling_autograd(topo: frames.FrameTopology, I: T, n_modes: int = 1, kind: str = "consistent", n_vectors: Optional[int] = None,
+                            iters: Optional[int] = None, tol: float = 1e-10, max_iters: int = 64, poll_every: int = 4,
+                            X0: Optional[T] = None) -> T:
+    from .frame_buckling import KINDS
+    if kind not in KINDS:
+        raise ValueError(f"kind must be one of {KINDS}")
+    if not torch.is_tensor(I) or I.dtype != torch.float64 or I.dim() != 2 or I.shape[1] != topo.Ne:
+        raise ValueError(f"I must be float64 [B, {topo.Ne}]")
+    if not I.is_cuda:
+        raise RuntimeError("differentiable_frame_buckling needs GPU tensors: openpystruct_amd has no CPU fallback")
+    lam, _, _ = torch.ops.openpystruct_amd.frame_buckling_factors(I, X0, int(n_modes), int(kind == "consistent"), int(n_vectors or 0),
+                                                                  int(iters or 0), float(tol), int(max_iters), int(poll_every), topo.Nn,
+                                                                  _topology_id(topo))
+    return lam
