@@ -18,6 +18,7 @@ from .frame_modes import (FrameMass, FrameModes, differentiable_frame_frequencie
                           frame_solve_modes)
 from .frame_buckling import (FrameBuckling, differentiable_frame_buckling, frame_buckling, frame_buckling_vjp,  # noqa: F401
                              frame_solve_buckling)
+from .frame_frequency import FrequencyFloor  # noqa: F401
 from . import torch_op  # noqa: F401  (registers torch.ops.openpystruct_amd.beam_solve / frame_solve, their VJP ops and autograd formulas)
 
 __all__ = ["BeamSolution", "beam_solve", "beam_solve_vjp", "differentiable_beam_solve", "kernel_name",
@@ -29,4 +30,4 @@ __all__ = ["BeamSolution", "beam_solve", "beam_solve_vjp", "differentiable_beam_
            "GroupedFrameDesigns", "DiscreteDesigns", "FrameDesignValues", "optimize_grouped_frame_designs", "frame_group_gradient",
            "evaluate_frame_designs", "snap_to_catalogue", "generate_grouped_frame_design_dataset", "FrameMass", "FrameModes", "frame_modes",
            "frame_solve_modes", "frame_modes_vjp", "differentiable_frame_frequencies", "FrameBuckling", "frame_buckling", "frame_solve_buckling",
-           "frame_buckling_vjp", "differentiable_frame_buckling"]
+           "frame_buckling_vjp", "differentiable_frame_buckling", "FrequencyFloor"]

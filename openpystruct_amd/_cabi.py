@@ -19,6 +19,8 @@ HEADER_PATH = os.path.join(_INCLUDE, "openpystruct_amd.h")
 # this order: a header may name the structs of the headers before it
 EXTENSION_HEADER_PATHS = tuple(os.path.join(_INCLUDE, f"openpystruct_amd_{name}.h") for name in (
     "frame_vjp", "frame_sizing", "frame_loads", "sizing_multicase", "frame_cases", "frame_designs", "design_loss", "frame_groups", "sizing_grad"))
+# extension headers added after the list above was pinned by name and length (tests/test_launch_status.py): read after it, the same way
+LATER_EXTENSION_HEADER_PATHS = tuple(os.path.join(_INCLUDE, f"openpystruct_amd_{name}.h") for name in ("frame_frequency",))
 # OPS_AMD_LIB lets A/B kernel experiments point at another build of the same C ABI
 LIB_PATH = os.environ.get("OPS_AMD_LIB") or os.path.join(_PKG, "lib", "libopenpystruct_amd.so")
 
@@ -134,7 +136,7 @@ EXPORTS = tuple(_abi.functions)     # every symbol include/openpystruct_amd.h de
 # prototypes and the argument structs that are new with them (they may name the structs of the main header and of the extension
 # headers listed before them, not redeclare them)
 _extensions, _known_structs = {}, dict(_abi.structs)
-for _path in EXTENSION_HEADER_PATHS:
+for _path in EXTENSION_HEADER_PATHS + LATER_EXTENSION_HEADER_PATHS:
     _extensions[_path] = _read_abi(_path, _known_structs)
     _known_structs.update(_extensions[_path].structs)
 for _path, _ext in _extensions.items():

@@ -12,6 +12,7 @@
 #include "frame_stream.hpp"
 
 #include "../../include/openpystruct_amd_frame_designs.h"
+#include "../../include/openpystruct_amd_frame_frequency.h"
 #include "frame_designs_math.hpp"
 
 namespace opsamd {
@@ -57,13 +58,15 @@ __global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_design_rhs_kernel(co
   }
 }
 
-template <int K, bool SUM>
-__global__ __launch_bounds__(256) void frame_design_step_kernel(int G, int Ne, const FrameDesignArgs a) {
+// DYN: the step of ops_frame_design_step_dyn_f32, which takes a gradient and a penalty formed outside it (FrameStepExtras)
+template <int K, bool SUM, bool DYN = false>
+__global__ __launch_bounds__(256) void frame_design_step_kernel(int G, int Ne, const FrameDesignKernelArgs<DYN> ka) {
+  const FrameDesignArgs& a = fd_plain(ka);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const long g = (long)blockIdx.x * 4 + wave;      // a scalar: every row base of the design is one
   if (g >= G) return;
   if (!a.s.active[g]) return;   // wave-uniform
-  frame_design_step<K, SUM>(lane, g, Ne, a);
+  frame_design_step<K, SUM, DYN>(lane, g, Ne, a, fd_extras(ka));
 }
 
 }  // namespace opsamd
@@ -112,5 +115,29 @@ extern "C" int ops_frame_design_step_f32(int G, int C, int n_nodes, int n_elems,
   void (*kernel)(int, int, const FrameDesignArgs) = nullptr;
   if (aggregate == 0) kernel = K == 1 ? frame_design_step_kernel<1, true> : K == 2 ? frame_design_step_kernel<2, true> : K == 4 ? frame_design_step_kernel<4, true> : frame_design_step_kernel<8, true>;
   else kernel = K == 1 ? frame_design_step_kernel<1, false> : K == 2 ? frame_design_step_kernel<2, false> : K == 4 ? frame_design_step_kernel<4, false> : frame_design_step_kernel<8, false>;
+  return launch_wave_rows(kernel, G, stream, G, n_elems, a);
+}
+
+// behind the plain step's eight kernels, in the same order: K = 1, 2, 4, 8 under "sum", then under "max"
+extern "C" int ops_frame_design_step_dyn_f32(int G, int C, int n_nodes, int n_elems, const double* elem_geo, const double* elem_E,
+                                             const int32_t* conn, float* I, double* I64, const double* disp, const double* V,
+                                             const double* M, const double* lambda, const double* loss_extra,
+                                             const int32_t* status_fwd, const int32_t* status_adj, const double* weights,
+                                             int aggregate, float* exp_avg, float* exp_avg_sq, float* best_loss,
+                                             int32_t* patience_cnt, int32_t* epochs_run, uint8_t* active, float* last_loss,
+                                             float* case_penalty, int32_t* governing, double* grad_out, const ops_sizing_params* hp,
+                                             const float* schedule, const double* grad_extra, const double* penalty_extra,
+                                             void* stream) {
+  FrameDesignDynArgs a{};
+  const int rc = frame_design_args(G, C, n_nodes, n_elems, elem_geo, elem_E, conn, I, I64, disp, V, M, lambda, loss_extra, status_fwd,
+                                   status_adj, weights, aggregate, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active,
+                                   last_loss, case_penalty, governing, grad_out, hp, schedule, &a.a);
+  if (rc != OPS_AMD_OK || G == 0) return rc;
+  if (!grad_extra || !penalty_extra) return OPS_AMD_ERR_INVALID_ARG;
+  a.x = FrameStepExtras{grad_extra, penalty_extra};
+  const int K = sizing_lane_elems(n_elems);
+  void (*kernel)(int, int, const FrameDesignDynArgs) = nullptr;
+  if (aggregate == 0) kernel = K == 1 ? frame_design_step_kernel<1, true, true> : K == 2 ? frame_design_step_kernel<2, true, true> : K == 4 ? frame_design_step_kernel<4, true, true> : frame_design_step_kernel<8, true, true>;
+  else kernel = K == 1 ? frame_design_step_kernel<1, false, true> : K == 2 ? frame_design_step_kernel<2, false, true> : K == 4 ? frame_design_step_kernel<4, false, true> : frame_design_step_kernel<8, false, true>;
   return launch_wave_rows(kernel, G, stream, G, n_elems, a);
 }

@@ -57,6 +57,8 @@ FA_HD double fd_elem_grad(const SizingObj& o, const FdElemGeo& t, double Ie, con
 }  // namespace opsamd
 
 #if defined(__HIPCC__)
+#include <type_traits>
+
 #include "sizing_multicase_math.hpp"
 
 namespace opsamd {
@@ -75,6 +77,20 @@ struct FrameDesignArgs {
   int32_t* governing;                                  // [G] or NULL
   double* grad_out;                                    // [G,Ne] or NULL
 };
+
+// The two arrays of the *_dyn step entries (include/openpystruct_amd_frame_frequency.h), both required there: a gradient with respect
+// to the element inertias [G,Ne] and a penalty [G] formed outside the step (a frequency floor: DESIGN.md §9r).  They are kernel
+// arguments of the DYN instantiations alone, behind the plain arguments: the plain kernels' argument blocks are what they were
+struct FrameStepExtras {
+  const double* grad_extra;          // [G,Ne]
+  const double* penalty_extra;       // [G]
+};
+struct FrameDesignDynArgs { FrameDesignArgs a; FrameStepExtras x; };
+template <bool DYN> using FrameDesignKernelArgs = std::conditional_t<DYN, FrameDesignDynArgs, FrameDesignArgs>;
+__device__ __forceinline__ const FrameDesignArgs& fd_plain(const FrameDesignArgs& a) { return a; }
+__device__ __forceinline__ const FrameDesignArgs& fd_plain(const FrameDesignDynArgs& a) { return a.a; }
+__device__ __forceinline__ const FrameStepExtras* fd_extras(const FrameDesignArgs&) { return nullptr; }
+__device__ __forceinline__ const FrameStepExtras* fd_extras(const FrameDesignDynArgs& a) { return &a.x; }
 
 // one load case as the wavefront holds it: the row's scalars and K elements per lane
 template <int K>
@@ -304,11 +320,21 @@ __device__ __forceinline__ void fd_store_design(int lane, long g, const FrameDes
   }
 }
 
-template <int K, bool SUM>
-__device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, const FrameDesignArgs& a) {
+// What a DYN step adds once the walk has ended (gx, px: the design's extras as the lane loaded them): one float64 addition per
+// element before anything reads the gradient, and the penalty onto the loss, last, in float32
+template <int K>
+__device__ __forceinline__ void fd_add_extras(const double (&gx)[K], double px, FdWalk<K>& w) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) w.g64[k] += gx[k];
+  w.loss = w.loss + (float)px;
+}
+
+template <int K, bool SUM, bool DYN = false>
+__device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, const FrameDesignArgs& a, const FrameStepExtras* x = nullptr) {
   const SizingArgs& s = a.s;
   const ops_sizing_params& hp = s.hp;
   float I32[K], m[K], v[K];
+  [[maybe_unused]] double gx[K], px;
   FdWalk<K> w;
   fd_design_walk<K, SUM>(lane, g, Ne, a, I32, [&](int ee) { return s.I[g * Ne + ee]; }, [&]() {
 #pragma unroll
@@ -317,8 +343,11 @@ __device__ __forceinline__ void frame_design_step(int lane, long g, int Ne, cons
       const long o = g * Ne + (e < Ne ? e : 0);
       m[k] = s.exp_avg[o];
       v[k] = s.exp_avg_sq[o];
+      if constexpr (DYN) gx[k] = x->grad_extra[o];
     }
+    if constexpr (DYN) px = x->penalty_extra[g];
   }, w);
+  if constexpr (DYN) fd_add_extras<K>(gx, px, w);
 
   // Adam, clamp (step_case)
   const FdAdam z = fd_adam_sizes(s, w.t_ep);

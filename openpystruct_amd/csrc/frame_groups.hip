@@ -12,6 +12,7 @@
 #include "frame_stream.hpp"
 
 #include "../../include/openpystruct_amd_frame_groups.h"
+#include "../../include/openpystruct_amd_frame_frequency.h"
 #include "frame_designs_math.hpp"
 
 namespace opsamd {
@@ -25,9 +26,17 @@ struct FrameGroupArgs {
   float* X;                          // [G,Ng]
 };
 
-// gs: 64 K doubles, ws: 64 K words, both this wave's own
-template <int K, bool SUM>
-__device__ __forceinline__ void frame_group_step(int lane, long g, int Ne, const FrameGroupArgs& ga, double* gs, int32_t* ws) {
+struct FrameGroupDynArgs { FrameGroupArgs g; FrameStepExtras x; };      // the arguments of ops_frame_group_step_dyn_f32's kernels
+template <bool DYN> using FrameGroupKernelArgs = std::conditional_t<DYN, FrameGroupDynArgs, FrameGroupArgs>;
+__device__ __forceinline__ const FrameGroupArgs& fg_plain(const FrameGroupArgs& a) { return a; }
+__device__ __forceinline__ const FrameGroupArgs& fg_plain(const FrameGroupDynArgs& a) { return a.g; }
+__device__ __forceinline__ const FrameStepExtras* fg_extras(const FrameGroupArgs&) { return nullptr; }
+__device__ __forceinline__ const FrameStepExtras* fg_extras(const FrameGroupDynArgs& a) { return &a.x; }
+
+// gs: 64 K doubles, ws: 64 K words, both this wave's own.  DYN: the element gradients take x->grad_extra before the per-group sum
+template <int K, bool SUM, bool DYN = false>
+__device__ __forceinline__ void frame_group_step(int lane, long g, int Ne, const FrameGroupArgs& ga, double* gs, int32_t* ws,
+                                                 const FrameStepExtras* x = nullptr) {
   const FrameDesignArgs& a = ga.d;
   const SizingArgs& s = a.s;
   const ops_sizing_params& hp = s.hp;
@@ -35,6 +44,7 @@ __device__ __forceinline__ void frame_group_step(int lane, long g, int Ne, const
   float* Xg = ga.X + g * Ng;
   float I32[K], Xo[K], m[K], v[K];
   int ge[K], eg[K], gp0[K], gp1[K];
+  [[maybe_unused]] double gx[K], px;
   FdWalk<K> w;
   // the float32 inertia of element e is its group's variable (a label outside the table's range is held to it: the tables are the
   // caller's, and this is the one read of global memory they index)
@@ -50,8 +60,11 @@ __device__ __forceinline__ void frame_group_step(int lane, long g, int Ne, const
       gp1[k] = ga.group_ptr[jj + 1];
       ge[k] = ga.group_elems[ee];                 // this lane's elements: their slice of the CSR's element list, their group
       eg[k] = ga.elem_group[ee];
+      if constexpr (DYN) gx[k] = x->grad_extra[g * Ne + ee];
     }
+    if constexpr (DYN) px = x->penalty_extra[g];
   }, w);
+  if constexpr (DYN) fd_add_extras<K>(gx, px, w);
 
   // 1. the per-element gradients and the CSR's element list into the wave's strips
 #pragma unroll
@@ -115,15 +128,16 @@ __device__ __forceinline__ void frame_group_step(int lane, long g, int Ne, const
   fd_store_design(lane, g, a, w, stop);
 }
 
-template <int K, bool SUM>
-__global__ __launch_bounds__(256) void frame_group_step_kernel(int G, int Ne, const FrameGroupArgs a) {
+template <int K, bool SUM, bool DYN = false>
+__global__ __launch_bounds__(256) void frame_group_step_kernel(int G, int Ne, const FrameGroupKernelArgs<DYN> ka) {
+  const FrameGroupArgs& a = fg_plain(ka);
   __shared__ double gs[4][64 * K];
   __shared__ int32_t ws[4][64 * K];
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const long g = (long)blockIdx.x * 4 + wave;
   if (g >= G) return;
   if (!a.d.s.active[g]) return;   // wave-uniform
-  frame_group_step<K, SUM>(lane, g, Ne, a, gs[wave], ws[wave]);
+  frame_group_step<K, SUM, DYN>(lane, g, Ne, a, gs[wave], ws[wave], fg_extras(ka));
 }
 
 }  // namespace opsamd
@@ -152,5 +166,32 @@ extern "C" int ops_frame_group_step_f32(int G, int C, int n_nodes, int n_elems, 
   void (*kernel)(int, int, const FrameGroupArgs) = nullptr;
   if (aggregate == 0) kernel = K == 1 ? frame_group_step_kernel<1, true> : K == 2 ? frame_group_step_kernel<2, true> : K == 4 ? frame_group_step_kernel<4, true> : frame_group_step_kernel<8, true>;
   else kernel = K == 1 ? frame_group_step_kernel<1, false> : K == 2 ? frame_group_step_kernel<2, false> : K == 4 ? frame_group_step_kernel<4, false> : frame_group_step_kernel<8, false>;
+  return launch_wave_rows(kernel, G, stream, G, n_elems, a);
+}
+
+// behind the plain step's eight kernels, in the same order
+extern "C" int ops_frame_group_step_dyn_f32(int G, int C, int n_nodes, int n_elems, int n_groups, const double* elem_geo,
+                                            const double* elem_E, const int32_t* conn, const int32_t* elem_group,
+                                            const int32_t* group_ptr, const int32_t* group_elems, float* X, float* I, double* I64,
+                                            const double* disp, const double* V, const double* M, const double* lambda,
+                                            const double* loss_extra, const int32_t* status_fwd, const int32_t* status_adj,
+                                            const double* weights, int aggregate, float* exp_avg, float* exp_avg_sq, float* best_loss,
+                                            int32_t* patience_cnt, int32_t* epochs_run, uint8_t* active, float* last_loss,
+                                            float* case_penalty, int32_t* governing, double* grad_out, const ops_sizing_params* hp,
+                                            const float* schedule, const double* grad_extra, const double* penalty_extra,
+                                            void* stream) {
+  if (n_groups < 1 || n_groups > n_elems) return OPS_AMD_ERR_INVALID_ARG;
+  FrameGroupDynArgs a{};
+  const int rc = frame_design_args(G, C, n_nodes, n_elems, elem_geo, elem_E, conn, I, I64, disp, V, M, lambda, loss_extra, status_fwd,
+                                   status_adj, weights, aggregate, exp_avg, exp_avg_sq, best_loss, patience_cnt, epochs_run, active,
+                                   last_loss, case_penalty, governing, grad_out, hp, schedule, &a.g.d);
+  if (rc != OPS_AMD_OK || G == 0) return rc;
+  if (!elem_group || !group_ptr || !group_elems || !X || !grad_extra || !penalty_extra) return OPS_AMD_ERR_INVALID_ARG;
+  a.g.Ng = n_groups; a.g.elem_group = elem_group; a.g.group_ptr = group_ptr; a.g.group_elems = group_elems; a.g.X = X;
+  a.x = FrameStepExtras{grad_extra, penalty_extra};
+  const int K = sizing_lane_elems(n_elems);
+  void (*kernel)(int, int, const FrameGroupDynArgs) = nullptr;
+  if (aggregate == 0) kernel = K == 1 ? frame_group_step_kernel<1, true, true> : K == 2 ? frame_group_step_kernel<2, true, true> : K == 4 ? frame_group_step_kernel<4, true, true> : frame_group_step_kernel<8, true, true>;
+  else kernel = K == 1 ? frame_group_step_kernel<1, false, true> : K == 2 ? frame_group_step_kernel<2, false, true> : K == 4 ? frame_group_step_kernel<4, false, true> : frame_group_step_kernel<8, false, true>;
   return launch_wave_rows(kernel, G, stream, G, n_elems, a);
 }

@@ -4,6 +4,8 @@
 // Ritz step, eigenvalue gradient).  Arithmetic: frame_modes.hpp.  Design: DESIGN.md §9p.
 // And the three kernels of the linear buckling load factors (geometric-stiffness apply, Ritz step of the swapped pencil, gradient
 // terms).  Arithmetic: frame_buckling.hpp.  Design: DESIGN.md §9q.
+// Last, the kernel of the natural-frequency floor of design sizing (the hinge on the eigenvalues and its gradient).  Arithmetic:
+// frame_modes.hpp.  C ABI: include/openpystruct_amd_frame_frequency.h.  Design: DESIGN.md §9r.
 //
 // The solve is linear in the element loads, so the band kernels stay as they are: the caller runs
 // ops_frame_solve_batched_f64_ex between the first two kernels (loads = rhs, per frame; elem_w = zeros).  All three kernels
@@ -12,6 +14,7 @@
 #include "frame_stream.hpp"
 
 #include "../../include/openpystruct_amd_frame_loads.h"
+#include "../../include/openpystruct_amd_frame_frequency.h"
 #include "frame_loads.hpp"
 #include "frame_buckling.hpp"
 #include "frame_modes.hpp"
@@ -364,4 +367,53 @@ extern "C" int ops_frame_buckling_grad_f64(int B, int m, int p, int n_nodes, int
   q.m = m; q.p = p; q.x = phi; q.lambda = lambda; q.g_lambda = g_lambda; q.status = status;
   q.gI_direct = gI_direct; q.g_forces = g_forces;
   return frame_stream_launch(frame_buckling_grad_kernel, q, (long)B * n_elems, stream);
+}
+
+// ---- the natural-frequency floor of design sizing (C ABI: include/openpystruct_amd_frame_frequency.h) ----
+// Behind every other kernel of this file: their order in the code object stays what it was.
+namespace opsamd {
+
+struct FrameFloorParams : FrameStreamTopo {     // B: the designs
+  int m, p;
+  const double* phi;               // [G,p,Nn,3]
+  const double* lambda;            // [G,p]
+  const int32_t* status;           // [G]
+  const double* floor;             // [1] or [G]
+  long floor_stride;
+  double alpha;
+  const uint8_t* active;           // [G] or NULL
+  double* grad_extra;              // [G,Ne]
+  double* penalty;                 // [G]
+};
+
+// one thread per (design, element), as frame_modes_grad_kernel; the m coefficients live in registers; no LDS, no atomics
+__global__ __launch_bounds__(FRAME_STREAM_BLOCK) void frame_frequency_floor_kernel(const FrameFloorParams p) {
+  frame_stream_rows(p.B, p.Ne, [&](long i, long g, int e) {
+    if (p.active && !p.active[g]) return;
+    double pen;
+    const double v = fm_elem_floor(p.m, p.p, p.Nn, p.elem_geo, p.elem_E, p.conn, p.phi, p.lambda, p.floor[g * p.floor_stride],
+                                   p.alpha, g, e, &pen);
+    const bool bad = p.status[g] != 0;
+    p.grad_extra[i] = bad ? __builtin_nan("") : v;
+    if (e == 0) p.penalty[g] = bad ? __builtin_nan("") : pen;
+  });
+}
+
+}  // namespace opsamd
+
+extern "C" int ops_frame_frequency_floor_f64(int G, int m, int p, int n_nodes, int n_elems, const double* elem_geo,
+                                             const double* elem_E, const int32_t* conn, const double* phi, const double* lambda,
+                                             const int32_t* status, const double* floor, long floor_stride, double alpha,
+                                             const uint8_t* active, double* grad_extra, double* penalty, void* stream) {
+  if (G < 0 || p < 1 || p > FM_MAX_VECTORS || m < 1 || m > p || n_nodes < 2 || n_elems < 1) return OPS_AMD_ERR_INVALID_ARG;
+  if (!(alpha >= 0.0) || (floor_stride != 0 && floor_stride != 1)) return OPS_AMD_ERR_INVALID_ARG;
+  if (G == 0) return OPS_AMD_OK;
+  if (!elem_geo || !elem_E || !conn || !phi || !lambda || !status || !floor || !grad_extra || !penalty) return OPS_AMD_ERR_INVALID_ARG;
+  FrameFloorParams q{};
+  q.B = G; q.Nn = n_nodes; q.Ne = n_elems;
+  q.elem_geo = elem_geo; q.elem_E = elem_E; q.conn = conn;
+  q.m = m; q.p = p; q.phi = phi; q.lambda = lambda; q.status = status;
+  q.floor = floor; q.floor_stride = floor_stride; q.alpha = alpha; q.active = active;
+  q.grad_extra = grad_extra; q.penalty = penalty;
+  return frame_stream_launch(frame_frequency_floor_kernel, q, (long)G * n_elems, stream);
 }

@@ -11,6 +11,8 @@
 //             that the caller adds over the 64 lanes by a fixed butterfly; the small dense part (fm_ritz_small) is the same
 //             arithmetic on every lane; fm_ritz_update writes the lane's entries of Q and R.
 //   gradient  dlambda_j/dI_e = phi_j,e . (K_b,e phi_j,e) for M-normalised phi (M does not depend on I: no adjoint solve).
+//   floor     the natural-frequency floor of design sizing: the hinge of the m lowest eigenvalues against a floor and
+//             its gradient, the gradient above with coefficients formed from lambda (fm_elem_floor).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -72,6 +74,34 @@ FA_HD double fm_elem_grad(int m, int p, int n_nodes, const double* elem_geo, con
     for (int k = 0; k < 6; ++k) q += u[k] * y[k];
     acc += g_lambda[b * m + j] * q;
   }
+  return acc;
+}
+
+// ---- the natural-frequency floor of design sizing ----
+// h = max(0, 1 - lambda / floor); a NaN lambda stays NaN
+FA_HD double fm_floor_hinge(double lam, double floor) {
+  const double h = 1.0 - lam / floor;
+  return h < 0.0 ? 0.0 : h;
+}
+
+// dP_f/dI of element e of design b, P_f = alpha sum over j < m of h_j^2: the sum over the m tracked modes, in mode order, of
+// (-2 alpha h_j / floor) phi_j,e . (K_b,e phi_j,e), the coefficients formed here from lambda [B,p]; phi [B,p,Nn,3].  *penalty: P_f.
+// With every hinge off the sum is +0.0 (a sum of zeros of either sign that starts from +0.0) and P_f is 0.0
+FA_HD double fm_elem_floor(int m, int p, int n_nodes, const double* elem_geo, const double* elem_E, const int32_t* conn,
+                           const double* phi, const double* lambda, double floor, double alpha, long b, int e, double* penalty) {
+  double acc = 0.0, pen = 0.0;
+  for (int j = 0; j < m; ++j) {
+    const double h = fm_floor_hinge(lambda[b * p + j], floor);
+    pen += h * h;
+    const double coef = -2.0 * alpha * h / floor;
+    double u[6], y[6];
+    fa_gather(n_nodes, conn, phi, b * p + j, e, u);
+    fa_apply_k(elem_geo[3 * e], elem_geo[3 * e + 1], elem_geo[3 * e + 2], 0.0, elem_E[e], u, y);
+    double q = 0.0;
+    for (int k = 0; k < 6; ++k) q += u[k] * y[k];
+    acc += coef * q;
+  }
+  *penalty = alpha * pen;
   return acc;
 }
 

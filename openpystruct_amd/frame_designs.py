@@ -24,6 +24,7 @@ import torch
 
 from . import _cabi
 from . import frames
+from .frame_frequency import FrequencyFloor
 from .frames import FrameCaseSolution, FrameConfig, FrameFactor, FrameTopology
 from .sizing_common import _ptr, arm_optimiser_state, checked_aggregate, history_callback, new_optimiser_state, run_epochs, step_schedule
 
@@ -88,6 +89,7 @@ class _DesignState:
         self.loss_extra = torch.zeros((G, C), **f64) if obj.alpha_sway + obj.alpha_deflection > 0.0 else None
         self.grad = torch.empty((G, Nv), **f64) if with_grad else None
         self.schedule = step_schedule(hp, dev)
+        self.extras = None                        # (grad_extra [G,Ne], penalty_extra [G]) of a term formed outside the step: the dyn entry
 
     def adjoint_rhs(self, fwd: FrameCaseSolution) -> None:
         """Step 4 of an epoch on the current stream: the adjoint right-hand sides (and the hinge values) of all G*C rows."""
@@ -109,8 +111,18 @@ class _DesignState:
         frames._resolve_launch(factor, self.C, self.rhs, self.C * self.topo.Nn * 3, self.lam)
         self.step(fwd, self.lam.disp, self.lam.status)
 
+    def _step_entry(self, name: str):
+        """(the step entry `ops_frame_<name>_step[_dyn]_f32`, its name): the dyn one when a term's `extras` are set."""
+        name = f"ops_frame_{name}_step_dyn_f32" if self.extras is not None else f"ops_frame_{name}_step_f32"
+        return getattr(_cabi.load(), name), name
+
     def _step_tail(self, fwd: FrameCaseSolution, lam: torch.Tensor, status_adj: Optional[torch.Tensor]) -> tuple:
-        """The arguments of a step entry from `disp` on: the same in ops_frame_design_step_f32 and ops_frame_group_step_f32."""
+        """The arguments of a step entry from `disp` on: the same in ops_frame_design_step_f32 and ops_frame_group_step_f32, and in
+        their dyn forms with the two extras before the stream."""
+        tail = self._plain_tail(fwd, lam, status_adj)
+        return tail if self.extras is None else tail[:-1] + tuple(t.data_ptr() for t in self.extras) + tail[-1:]
+
+    def _plain_tail(self, fwd: FrameCaseSolution, lam: torch.Tensor, status_adj: Optional[torch.Tensor]) -> tuple:
         return (fwd.disp.data_ptr(), fwd.V.data_ptr(), fwd.M.data_ptr(), lam.data_ptr(), _ptr(self.loss_extra), fwd.status.data_ptr(),
                 _ptr(status_adj), _ptr(self.weights), self.aggregate,
                 *(t.data_ptr() for t in (self.exp_avg, self.exp_avg_sq, self.best, self.patience_cnt, self.epochs, self.active, self.last,
@@ -120,17 +132,17 @@ class _DesignState:
     def step(self, fwd: FrameCaseSolution, lam: torch.Tensor, status_adj: Optional[torch.Tensor]) -> None:
         """The design step on the current stream (`lam` [G,C,Nn,3]: the adjoint displacements)."""
         topo, I = self.topo, self.I
+        entry, name = self._step_entry("design")
         with torch.cuda.device(I.device):
-            rc = _cabi.load().ops_frame_design_step_f32(
-                I.shape[0], self.C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), frames._adjoint_tables(topo).conn.data_ptr(),
-                I.data_ptr(), self.I64.data_ptr(), *self._step_tail(fwd, lam, status_adj))
-        _cabi.check(rc, "ops_frame_design_step_f32")
+            rc = entry(I.shape[0], self.C, topo.Nn, topo.Ne, topo.d_geo.data_ptr(), topo.d_E.data_ptr(), frames._adjoint_tables(topo).conn.data_ptr(),
+                       I.data_ptr(), self.I64.data_ptr(), *self._step_tail(fwd, lam, status_adj))
+        _cabi.check(rc, name)
 
 
 def _checked_problem(topo: FrameTopology, loads, element_loads, n_designs, V0, v_name: str, n_vars: int, aggregate: str, weights,
-                     who: str) -> types.SimpleNamespace:
+                     who: str, frequency=None) -> types.SimpleNamespace:
     """The arguments of a designs run, checked in the order every entry keeps: every shape before any device, then where everything
-    lives (with the loads, on the topology's device).  `V0`: the optional start [G, n_vars] (I0, or X0 of the grouped loop).
+    lives (with the loads, on the topology's device); a `frequency` term is checked against the problem with the shapes.  `V0`: the optional start [G, n_vars] (I0, or X0 of the grouped loop).
     -> G, C, dev, loads, w (the checked tensors), agg, w_c (`checked_aggregate`), nbytes (`_factor_bytes`)."""
     if torch.is_tensor(loads) and loads.dim() == 4:
         G = int(loads.shape[0])
@@ -154,6 +166,7 @@ def _checked_problem(topo: FrameTopology, loads, element_loads, n_designs, V0, v
     _checked_limits(topo, C)
     agg, w_c = checked_aggregate(aggregate, weights, C)
     nbytes = _factor_bytes(topo, G)
+    _checked_frequency(frequency, topo, G)
     if loads.is_cuda and topo.device.type == "cuda" and topo.device.index in (None, loads.device.index):
         dev = loads.device
     loads = frames._checked_cases("loads", loads, G, (topo.Nn, 3), dev, who)
@@ -212,19 +225,46 @@ def _start_values(V0: Optional[torch.Tensor], G: int, n_vars: int, cfg: FrameCon
     return V0.to(dtype=torch.float32, device=dev).clone() if V0 is not None else torch.full((G, n_vars), cfg.I0, dtype=torch.float32, device=dev)
 
 
-def _run_design_loop(st: _DesignState, q: types.SimpleNamespace, n_max: int, poll_every: int, loss_history: Optional[list]) -> _Forward:
+def _checked_frequency(frequency: Optional[FrequencyFloor], topo: FrameTopology, G: int) -> Optional[FrequencyFloor]:
+    """The `frequency=` of an entry, checked against its problem before any device call."""
+    if frequency is not None:
+        if not isinstance(frequency, FrequencyFloor):
+            raise ValueError("frequency must be a FrequencyFloor or None")
+        frequency.check(topo, G)
+    return frequency
+
+
+def _run_design_loop(st: _DesignState, q: types.SimpleNamespace, n_max: int, poll_every: int, loss_history: Optional[list],
+                     frequency: Optional[FrequencyFloor] = None) -> _Forward:
     """The loop of a designs run on the state `st` (its `step` is the design's or the groups'): up to `n_max` epochs of the forward
     and `st.gradient_and_step`, then the forward once more -- I64 froze when a design stopped: every design's last solve, all C cases
-    -- and a device synchronise.  Returns the forward, whose `fwd` is that solve; with no designs nothing is launched."""
+    -- and a device synchronise.  Returns the forward, whose `fwd` is that solve; with no designs nothing is launched.
+    With `frequency` the step is the dyn one, and between the forward and the step the term's iteration advances on the epoch's
+    factor (`start_iters` in the first epoch, `iters` after it, continuing from the last Ritz step's R) and the floor kernel runs on
+    the active designs; after the last forward it advances once more and the floor kernel fills `.modes` / `.penalty` for all.  The
+    term's buffers are allocated before the loop."""
     fw = _Forward(st.topo, st.I64, q)
     if q.G:
+        if frequency is not None:
+            frequency.bind(q.G, q.dev)
+            frequency.start()
+            st.extras = frequency.extras
+
         def epoch():
             fw()
+            if frequency is not None:
+                frequency.advance(fw.factor)
+                frequency.floor_launch(st.active)
             st.gradient_and_step(fw.factor, fw.fwd)
 
         run_epochs(epoch, n_max, poll_every, st.active, history_callback(loss_history, st.last))
         fw()
+        if frequency is not None:
+            frequency.advance(fw.factor)
+            frequency.floor_launch(None)
         torch.cuda.synchronize(q.dev)
+        if frequency is not None:
+            frequency.finish()
     return fw
 
 
@@ -232,7 +272,8 @@ def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loa
                            n_designs: Optional[int] = None, cfg: Optional[FrameConfig] = None, I0: Optional[torch.Tensor] = None,
                            aggregate: str = "sum", weights: Optional[Sequence[float]] = None, alpha_sway: float = 0.0,
                            sway_limit: Optional[float] = None, alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None,
-                           max_epochs: Optional[int] = None, poll_every: int = 25, loss_history: Optional[list] = None) -> FrameDesigns:
+                           max_epochs: Optional[int] = None, poll_every: int = 25, loss_history: Optional[list] = None,
+                           frequency: Optional[FrequencyFloor] = None) -> FrameDesigns:
     """Size G frame designs, each under its C load cases, on the exact gradient of the aggregated loss.
     `loads`: float64 [G,C,Nn,3], or [C,Nn,3] shared by the designs (then `n_designs` or `I0` [G,Ne] says how many there are);
     `element_loads`: float64 [G,C,Ne,2] or [C,Ne,2] (wy, wx), None = the topology's `wy` / `wx` in every case, as in `frame_resolve`.
@@ -241,18 +282,21 @@ def optimize_frame_designs(topo: FrameTopology, loads: torch.Tensor, element_loa
     once per design on its aggregated loss.  Six launches and ONE factorisation per epoch (the rows path: five launches and two
     factorisations per ROW); every buffer is allocated before the loop; `poll_every` as in `optimize_frames`.  `loss_history`: a
     list that receives every epoch's design loss [G].  Served: half bandwidth <= 55 (`frame_factor`), C <= 64, Ne <= 512.
+    `frequency`: a `FrequencyFloor` adds its penalty on the lowest natural frequencies (frame_frequency.py) -- a
+    penalty, not a constraint; with None every launch is the one made without the keyword.
     Returns `FrameDesigns` (I, the last solve of every design and case, epochs, governing case, case penalties)."""
     cfg = cfg or FrameConfig()
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
-    q = _checked_problem(topo, loads, element_loads, n_designs, I0, "I0", topo.Ne, aggregate, weights, "optimize_frame_designs")
+    q = _checked_problem(topo, loads, element_loads, n_designs, I0, "I0", topo.Ne, aggregate, weights, "optimize_frame_designs", frequency)
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
     I = _start_values(I0, q.G, topo.Ne, cfg, q.dev)
     st = _DesignState(topo, I, I.double(), q.C, frames._sizing_params(cfg, n_max), obj, q.agg, q.w_c, with_grad=False)
-    fw = _run_design_loop(st, q, n_max, poll_every, loss_history)
+    fw = _run_design_loop(st, q, n_max, poll_every, loss_history, frequency)
     return FrameDesigns(I, fw.fwd, st.epochs, st.governing, st.case_penalty)
 
 
-def _checked_gradient_inputs(factor: FrameFactor, sol: FrameCaseSolution, hp, aggregate: str, weights, who: str) -> types.SimpleNamespace:
+def _checked_gradient_inputs(factor: FrameFactor, sol: FrameCaseSolution, hp, aggregate: str, weights, who: str, frequency=None,
+                             modes=None) -> types.SimpleNamespace:
     """The arguments of a gradient entry `who`, checked in the order both keep: the factor's inertias, the solution's shapes, the
     limits, the aggregate, then where everything lives.  -> topo, I64 (factor.I), G, C, agg, w_c (`checked_aggregate`), hp (an
     `ops_sizing_params`)."""
@@ -268,6 +312,9 @@ def _checked_gradient_inputs(factor: FrameFactor, sol: FrameCaseSolution, hp, ag
     C = int(sol.disp.shape[1])
     _checked_limits(topo, C)
     agg, w_c = checked_aggregate(aggregate, weights, C)
+    _checked_frequency(frequency, topo, G)
+    if modes is not None and frequency is None:
+        raise ValueError("modes= is for a frequency= term")
     if not I64.is_cuda or any(not t.is_cuda for t in (sol.disp, sol.V, sol.M, sol.status)):
         raise RuntimeError(f"{who} needs GPU tensors: openpystruct_amd has no CPU fallback")
     hp = frames._sizing_params(hp) if isinstance(hp, FrameConfig) else hp
@@ -276,19 +323,38 @@ def _checked_gradient_inputs(factor: FrameFactor, sol: FrameCaseSolution, hp, ag
 
 def frame_design_gradient(factor: FrameFactor, sol: FrameCaseSolution, hp, *, aggregate: str = "sum",
                           weights: Optional[Sequence[float]] = None, alpha_sway: float = 0.0, sway_limit: Optional[float] = None,
-                          alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
+                          alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None,
+                          frequency: Optional[FrequencyFloor] = None, modes=None):
     """dL/dI [G,Ne] (float64) of the aggregated design objective from a caller's `frame_factor(topo, I)` and the solution `sol` of
     `frame_resolve(factor, ...)`: steps 4 to 6 of an epoch of `optimize_frame_designs` -- the adjoint right-hand sides, ONE re-solve
     on the kept factor, the design step -- with the step's state in scratch tensors: nothing of the caller's is written.  `hp`: a
     `FrameConfig` or an `ops_sizing_params`.  Returns (grad, loss_extra [G,C] -- the value of the displacement terms per case, None
     when both alphas are 0 --, governing [G] int32).  "sum": grad = 1 + sum_c w_c dP_c/dI; "max": 1 + dP_c*/dI of the governing
-    case.  Rows of a design with a failed factorisation (or, under "sum", any failed case) are NaN."""
+    case.  Rows of a design with a failed factorisation (or, under "sum", any failed case) are NaN.  `frequency`: a `FrequencyFloor`
+    adds dP_f/dI from a cold iteration of its `start_iters` on `factor`, or, with `modes` (a `FrameModes` of the caller for these
+    inertias, at least the term's n_modes), from those and no iteration; a design whose mode status is non-zero gets a NaN row."""
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
-    q = _checked_gradient_inputs(factor, sol, hp, aggregate, weights, "frame_design_gradient")
+    q = _checked_gradient_inputs(factor, sol, hp, aggregate, weights, "frame_design_gradient", frequency, modes)
     st = _DesignState(q.topo, q.I64.float(), q.I64.clone(), q.C, q.hp, obj, q.agg, q.w_c, with_grad=True)
     if q.G:
+        _frequency_extras(st, frequency, factor, modes)
         st.gradient_and_step(factor, sol)
+        if frequency is not None and modes is None:
+            frequency.finish()
     return st.grad, st.loss_extra, st.governing
+
+
+def _frequency_extras(st: _DesignState, frequency: Optional[FrequencyFloor], factor: FrameFactor, modes=None) -> None:
+    """The term of a one-shot entry on the current stream, into the state's `extras`: a cold iteration on `factor`, or the caller's modes."""
+    if frequency is None:
+        return
+    G, dev = st.I.shape[0], st.I.device
+    if modes is not None:
+        frequency.from_modes(modes, G, dev)
+    else:
+        frequency.bind(G, dev)
+        frequency.cold(factor)
+    st.extras = frequency.extras
 
 
 def _dataset_fields(r, lateral: np.ndarray, vertical: np.ndarray, G: int, C: int) -> dict:

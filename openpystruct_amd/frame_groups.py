@@ -21,8 +21,9 @@ import torch
 
 from . import _cabi
 from . import frames
-from .frame_designs import (_checked_gradient_inputs, _checked_problem, _dataset_fields, _DesignState, _Forward, _penalties, _run_design_loop,
-                            _start_values)
+from .frame_designs import (_checked_gradient_inputs, _checked_problem, _dataset_fields, _DesignState, _Forward,
+                            _frequency_extras, _penalties, _run_design_loop, _start_values)
+from .frame_frequency import FrequencyFloor
 from .frames import FrameCaseSolution, FrameConfig, FrameFactor, FrameTopology
 
 
@@ -170,28 +171,30 @@ class _GroupState(_DesignState):
 
     def step(self, fwd: FrameCaseSolution, lam: torch.Tensor, status_adj: Optional[torch.Tensor]) -> None:
         topo, I = self.topo, self.I
+        entry, name = self._step_entry("group")
         with torch.cuda.device(I.device):
-            rc = _cabi.load().ops_frame_group_step_f32(
-                I.shape[0], self.C, topo.Nn, topo.Ne, self.groups.Ng, topo.d_geo.data_ptr(), topo.d_E.data_ptr(),
-                frames._adjoint_tables(topo).conn.data_ptr(), *(t.data_ptr() for t in self.tables), self.X.data_ptr(), I.data_ptr(),
-                self.I64.data_ptr(), *self._step_tail(fwd, lam, status_adj))
-        _cabi.check(rc, "ops_frame_group_step_f32")
+            rc = entry(I.shape[0], self.C, topo.Nn, topo.Ne, self.groups.Ng, topo.d_geo.data_ptr(), topo.d_E.data_ptr(),
+                       frames._adjoint_tables(topo).conn.data_ptr(), *(t.data_ptr() for t in self.tables), self.X.data_ptr(), I.data_ptr(),
+                       self.I64.data_ptr(), *self._step_tail(fwd, lam, status_adj))
+        _cabi.check(rc, name)
 
 
 def evaluate_frame_designs(topo: FrameTopology, I: torch.Tensor, loads: torch.Tensor, element_loads: Optional[torch.Tensor] = None, *,
                            cfg: Optional[FrameConfig] = None, aggregate: str = "sum", weights: Optional[Sequence[float]] = None,
                            alpha_sway: float = 0.0, sway_limit: Optional[float] = None, alpha_deflection: float = 0.0,
-                           deflection_limit: Optional[float] = None) -> FrameDesignValues:
+                           deflection_limit: Optional[float] = None, frequency: Optional[FrequencyFloor] = None) -> FrameDesignValues:
     """The objective of `optimize_frame_designs` for any designs I [G,Ne] (float32 or float64) under `loads` / `element_loads` (as
     there): one forward pass -- the keeping solve, the re-solve of the G*C rows, the correction for the element loads -- the hinge
     values when a displacement term is on, and the design step's loss on scratch state (the step is given no adjoint: its loss,
     penalties and governing case do not depend on one).  The existing launches, nothing of the caller's written.  The penalties are
-    formed in float32 on I.float(), the solve runs on I.double().  Returns `FrameDesignValues`."""
+    formed in float32 on I.float(), the solve runs on I.double().  `frequency`: a `FrequencyFloor`; the value then is the plain value
+    + (float)P_f of a cold iteration of the term's `start_iters` on this forward's factor, and the term's `.modes` / `.penalty` are
+    those.  Returns `FrameDesignValues`."""
     cfg = cfg or FrameConfig()
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
     if not torch.is_tensor(I) or I.dim() != 2 or I.shape[1] != topo.Ne or I.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"I must be float32 or float64 [G, {topo.Ne}]")
-    q = _checked_problem(topo, loads, element_loads, None, I, "I", topo.Ne, aggregate, weights, "evaluate_frame_designs")
+    q = _checked_problem(topo, loads, element_loads, None, I, "I", topo.Ne, aggregate, weights, "evaluate_frame_designs", frequency)
     dev = q.dev
     hp = frames._sizing_params(cfg, 1)
     st = _DesignState(topo, I.to(dtype=torch.float32, device=dev).clone(), I.to(dtype=torch.float64, device=dev).clone(), q.C, hp, obj,
@@ -202,8 +205,11 @@ def evaluate_frame_designs(topo: FrameTopology, I: torch.Tensor, loads: torch.Te
         if st.loss_extra is not None:
             st.adjoint_rhs(fw.fwd)
         st.rhs.zero_()                            # no adjoint: the step's loss does not read it
+        _frequency_extras(st, frequency, fw.factor)
         st.step(fw.fwd, st.rhs, None)
         torch.cuda.synchronize(dev)
+        if frequency is not None:
+            frequency.finish()
     return FrameDesignValues(st.last, st.case_penalty, st.governing, fw.fwd, fw.fwd.status)
 
 
@@ -212,14 +218,16 @@ def optimize_grouped_frame_designs(topo: FrameTopology, groups, loads: torch.Ten
                                    cfg: Optional[FrameConfig] = None, aggregate: str = "sum", weights: Optional[Sequence[float]] = None,
                                    alpha_sway: float = 0.0, sway_limit: Optional[float] = None, alpha_deflection: float = 0.0,
                                    deflection_limit: Optional[float] = None, max_epochs: Optional[int] = None, poll_every: int = 25,
-                                   loss_history: Optional[list] = None) -> GroupedFrameDesigns:
+                                   loss_history: Optional[list] = None, frequency: Optional[FrequencyFloor] = None) -> GroupedFrameDesigns:
     """`optimize_frame_designs` with linked design variables.  `groups`: int [Ne], the label 0 .. Ng-1 of every
     element (`story_groups(topo)`: columns by story, beams by floor), or a `MemberGroups`.  `X0` [G,Ng] float32: the start (default
     cfg.I0).  The loop steps on X [G,Ng]; the element inertias are X[:, groups].  Six launches and one factorisation per epoch, as
     there, with ops_frame_group_step_f32 as the step; the other keywords, the limits (half bandwidth <= 55, C <= 64, Ne <= 512) and
     `loss_history` are those of `optimize_frame_designs`.  `catalogue`: a strictly ascending sequence of positive inertias; after the
     loop X is snapped to it (`snap`: "up" or "nearest"), expanded, and both designs are evaluated (`evaluate_frame_designs`) into
-    `discrete`.  Returns `GroupedFrameDesigns`."""
+    `discrete`.  `frequency`: a `FrequencyFloor`, as in `optimize_frame_designs`; its gradient joins the element gradients before
+    the per-group sum, and with a `catalogue` both evaluations carry the term (its `.modes` / `.penalty` are then the continuous
+    design's, evaluated last).  Returns `GroupedFrameDesigns`."""
     cfg = cfg or FrameConfig()
     penalties = dict(alpha_sway=alpha_sway, sway_limit=sway_limit, alpha_deflection=alpha_deflection, deflection_limit=deflection_limit)
     obj = _penalties(**penalties)
@@ -228,17 +236,17 @@ def optimize_grouped_frame_designs(topo: FrameTopology, groups, loads: torch.Ten
         raise ValueError(f'snap must be "up" or "nearest", got {snap!r}')
     if catalogue is not None:
         _checked_catalogue(catalogue)
-    q = _checked_problem(topo, loads, element_loads, n_designs, X0, "X0", mg.Ng, aggregate, weights, "optimize_grouped_frame_designs")
+    q = _checked_problem(topo, loads, element_loads, n_designs, X0, "X0", mg.Ng, aggregate, weights, "optimize_grouped_frame_designs", frequency)
     n_max = max_epochs if max_epochs is not None else cfg.num_epochs
     X = _start_values(X0, q.G, mg.Ng, cfg, q.dev)
     I = mg.expand(X)
     st = _GroupState(mg, X, I, I.double(), q.C, frames._sizing_params(cfg, n_max), obj, q.agg, q.w_c, with_grad=False)
-    fw = _run_design_loop(st, q, n_max, poll_every, loss_history)
+    fw = _run_design_loop(st, q, n_max, poll_every, loss_history, frequency)
     discrete = None
     if catalogue is not None:
         Xd, section, clipped = snap_to_catalogue(X, catalogue, snap)
         Id = mg.expand(Xd)
-        ev = dict(cfg=cfg, aggregate=aggregate, weights=weights, **penalties)
+        ev = dict(cfg=cfg, aggregate=aggregate, weights=weights, frequency=frequency, **penalties)
         discrete = DiscreteDesigns(Xd, section, Id, evaluate_frame_designs(topo, Id, q.loads, q.w, **ev).value,
                                    evaluate_frame_designs(topo, I, q.loads, q.w, **ev).value, clipped)
     return GroupedFrameDesigns(X, I, fw.fwd, st.epochs, st.governing, st.case_penalty, discrete)
@@ -246,21 +254,26 @@ def optimize_grouped_frame_designs(topo: FrameTopology, groups, loads: torch.Ten
 
 def frame_group_gradient(factor: FrameFactor, sol: FrameCaseSolution, groups, hp, *, aggregate: str = "sum",
                          weights: Optional[Sequence[float]] = None, alpha_sway: float = 0.0, sway_limit: Optional[float] = None,
-                         alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None):
+                         alpha_deflection: float = 0.0, deflection_limit: Optional[float] = None,
+                         frequency: Optional[FrequencyFloor] = None, modes=None):
     """`frame_design_gradient` by group: dL/dX [G,Ng] (float64) of the aggregated design objective with X the groups' variables, from a
     caller's `frame_factor(topo, I)` with I = X[:, groups] and the solution `sol` of `frame_resolve(factor, ...)`.  The adjoint
     right-hand sides, one re-solve on the kept factor and the group step with its state in scratch tensors: nothing of the caller's
-    is written.  Returns (grad, loss_extra [G,C] or None, governing [G] int32)."""
+    is written.  `frequency`, `modes`: as there; the term's element gradient joins before the per-group sum.  Returns (grad,
+    loss_extra [G,C] or None, governing [G] int32)."""
     obj = _penalties(alpha_sway, sway_limit, alpha_deflection, deflection_limit)
     mg = member_groups(factor.topo, groups)
-    q = _checked_gradient_inputs(factor, sol, hp, aggregate, weights, "frame_group_gradient")
+    q = _checked_gradient_inputs(factor, sol, hp, aggregate, weights, "frame_group_gradient", frequency, modes)
     I64 = q.I64
     # the variables as the step reads them: a group's first element speaks for it (I = X[:, groups] is the caller's promise)
     first = torch.as_tensor(mg.elems[mg.ptr[:-1]].astype(np.int64), device=I64.device)
     X = I64[:, first].float().contiguous()
     st = _GroupState(mg, X, I64.float(), I64.clone(), q.C, q.hp, obj, q.agg, q.w_c, with_grad=True)
     if q.G:
+        _frequency_extras(st, frequency, factor, modes)
         st.gradient_and_step(factor, sol)
+        if frequency is not None and modes is None:
+            frequency.finish()
     return st.grad, st.loss_extra, st.governing
 
 

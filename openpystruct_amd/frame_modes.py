@@ -91,6 +91,59 @@ def _mass_apply(mass: FrameMass, rows: int, rows_per_frame: int, x: torch.Tensor
     _cabi.check(rc, "ops_frame_mass_apply_f64")
 
 
+class _ModeIteration:
+    """The subspace iteration of B frames on p vectors: its buffers (from `buffer(name, shape[, dtype])`, which keeps them by shape),
+    its start and `advance`.  After an advance `Q` [B,p,Nn,3] holds the M-normalised Ritz vectors, `lam` and `change` [B,p] the Ritz
+    values and their relative change against the values `lam` held before, `status` [B] the frames' status, and `R` = M Q: the next
+    advance -- on this factor or on another one of the same frames -- continues from it with no restart launch."""
+
+    def __init__(self, topo: FrameTopology, mass: FrameMass, B: int, p: int, buffer):
+        self.topo, self.mass, self.B, self.p = topo, mass, B, p
+        shape = self.shape = (B, p, topo.Nn, 3)
+        self.out = FrameCaseSolution(buffer("modes_X", shape), buffer("modes_forces", (B, p, topo.Ne, 6)), buffer("modes_V", (B, p, topo.Ne)),
+                                     buffer("modes_M", (B, p, topo.Ne)), buffer("modes_row_status", (B, p), torch.int32))
+        self.X, self.MX, self.R, self.Q = self.out.disp, buffer("modes_MX", shape), buffer("modes_R", shape), buffer("modes_Q", shape)
+        self.lam, self.change, self.status = buffer("modes_lambda", (B, p)), buffer("modes_change", (B, p)), buffer("modes_status", (B,), torch.int32)
+        self.n_run = 0
+
+    def start(self, X0: Optional[torch.Tensor] = None) -> None:
+        """R = M X0 (`default_start` without X0; the values on constrained DOFs zeroed), lambda = +inf: two launches and a fill."""
+        topo, p = self.topo, self.p
+        if X0 is None:
+            x0 = topo.__dict__.setdefault("_modes_x0", {}).get(p)
+            if x0 is None:
+                x0 = topo.__dict__["_modes_x0"][p] = torch.as_tensor(default_start(topo, p), dtype=torch.float64, device=self.X.device)
+            self.X.copy_(x0.expand(self.shape))
+        else:
+            torch.mul(X0.expand(self.shape), _free_mask(topo), out=self.X)
+        _mass_apply(self.mass, self.B * p, p, self.X, self.R)
+        self.lam.fill_(math.inf)
+        self.n_run = 0
+
+    def advance(self, factor: FrameFactor, n: int) -> None:
+        """n times (re-solve of the B * p rows on `factor`, mass apply, Ritz step) on the current stream: no readback, no allocation."""
+        topo, p, dev = self.topo, self.p, self.X.device
+        lib = _cabi.load()
+        for _ in range(n):
+            _resolve_launch(factor, p, self.R, p * topo.Nn * 3, self.out)
+            _mass_apply(self.mass, self.B * p, p, self.X, self.MX)
+            with torch.cuda.device(dev):
+                rc = lib.ops_frame_modes_ritz_f64(self.B, p, topo.Nn, self.X.data_ptr(), self.MX.data_ptr(), self.R.data_ptr(), self.Q.data_ptr(),
+                                                  self.lam.data_ptr(), self.change.data_ptr(), self.out.status.data_ptr(), self.status.data_ptr(),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+            _cabi.check(rc, "ops_frame_modes_ritz_f64")
+            self.n_run += 1
+
+    def result(self, m: int) -> FrameModes:
+        """The m lowest pairs as new tensors, the sign of a shape making its component of largest magnitude positive."""
+        shapes = self.Q[:, :m].clone(memory_format=torch.contiguous_format)
+        flat = shapes.view(self.B, m, -1)
+        lead = flat.gather(2, flat.abs().argmax(dim=2, keepdim=True))          # (the first of equal maxima)
+        flat.mul_(torch.where(lead < 0.0, -1.0, 1.0))
+        eig = self.lam[:, :m].clone()
+        return FrameModes(eig, torch.sqrt(eig) / (2.0 * math.pi), shapes, self.change[:, :m].clone(), self.n_run, self.status.clone())
+
+
 def frame_modes(factor: FrameFactor, mass: FrameMass, n_modes: int = 1, n_vectors: Optional[int] = None, iters: Optional[int] = None,
                 tol: float = 1e-10, max_iters: int = 64, poll_every: int = 4, X0: Optional[torch.Tensor] = None) -> FrameModes:
     """The `n_modes` lowest eigenpairs of K(I_b) phi = lambda M phi for the B frames of a kept factorisation, by subspace iteration on
@@ -132,40 +185,14 @@ def frame_modes(factor: FrameFactor, mass: FrameMass, n_modes: int = 1, n_vector
     if B == 0:
         e = torch.empty((0, m), **f64)
         return FrameModes(e, e.clone(), torch.empty((0, m, topo.Nn, 3), **f64), e.clone(), 0, torch.empty((0,), dtype=torch.int32, device=dev))
-    shape = (B, p, topo.Nn, 3)
-    out = FrameCaseSolution(factor._buffer("modes_X", shape), factor._buffer("modes_forces", (B, p, topo.Ne, 6)),
-                            factor._buffer("modes_V", (B, p, topo.Ne)), factor._buffer("modes_M", (B, p, topo.Ne)),
-                            factor._buffer("modes_row_status", (B, p), torch.int32))
-    X, MX, R, Q = out.disp, factor._buffer("modes_MX", shape), factor._buffer("modes_R", shape), factor._buffer("modes_Q", shape)
-    lam, change, status = factor._buffer("modes_lambda", (B, p)), factor._buffer("modes_change", (B, p)), factor._buffer("modes_status", (B,), torch.int32)
-    if X0 is None:
-        x0 = topo.__dict__.setdefault("_modes_x0", {}).get(p)
-        if x0 is None:
-            x0 = topo.__dict__["_modes_x0"][p] = torch.as_tensor(default_start(topo, p), **f64)
-        X.copy_(x0.expand(shape))
-    else:
-        torch.mul(X0.expand(shape), _free_mask(topo), out=X)
-    _mass_apply(mass, B * p, p, X, R)
-    lam.fill_(math.inf)
-    n_run = 0
-    for it in range(int(iters) if iters is not None else int(max_iters)):
-        _resolve_launch(factor, p, R, p * topo.Nn * 3, out)
-        _mass_apply(mass, B * p, p, X, MX)
-        with torch.cuda.device(dev):
-            rc = lib.ops_frame_modes_ritz_f64(B, p, topo.Nn, X.data_ptr(), MX.data_ptr(), R.data_ptr(), Q.data_ptr(), lam.data_ptr(),
-                                              change.data_ptr(), out.status.data_ptr(), status.data_ptr(),
-                                              torch.cuda.current_stream(dev).cuda_stream)
-        _cabi.check(rc, "ops_frame_modes_ritz_f64")
-        n_run = it + 1
-        if iters is None and n_run % int(poll_every) == 0:
-            if bool(((status != 0) | (change[:, :m] <= tol).all(dim=1)).all()):
+    it = _ModeIteration(topo, mass, B, p, factor._buffer)
+    it.start(X0)
+    for _ in range(int(iters) if iters is not None else int(max_iters)):
+        it.advance(factor, 1)
+        if iters is None and it.n_run % int(poll_every) == 0:
+            if bool(((it.status != 0) | (it.change[:, :m] <= tol).all(dim=1)).all()):
                 break
-    shapes = Q[:, :m].clone(memory_format=torch.contiguous_format)
-    flat = shapes.view(B, m, -1)
-    lead = flat.gather(2, flat.abs().argmax(dim=2, keepdim=True))          # (the first of equal maxima)
-    flat.mul_(torch.where(lead < 0.0, -1.0, 1.0))
-    eig = lam[:, :m].clone()
-    return FrameModes(eig, torch.sqrt(eig) / (2.0 * math.pi), shapes, change[:, :m].clone(), n_run, status.clone())
+    return it.result(m)
 
 
 def frame_solve_modes(topo: FrameTopology, I: torch.Tensor, mass: FrameMass, **kwargs) -> FrameModes:
